@@ -43,7 +43,7 @@ def test_downstream_project_finds_the_package_and_links():
         assert "libhexl-fpga.so" in out, "the imported target did not reach the link line"
 
 
-@pytest.mark.skipif(not REF_EXAMPLES.exists(), reason="reference tree not present (GPU box)")
+@pytest.mark.skipif(not os.path.isdir(REF_EXAMPLES), reason="reference tree not present or not readable")
 def test_reference_examples_cmakelists_configures_against_the_package():
     out = cmake_build(REF_EXAMPLES, BUILD_REF)
     assert "Intel HE Acceleration Library for FPGAs: found" in out          # examples/CMakeLists.txt:13-17

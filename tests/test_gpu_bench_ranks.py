@@ -19,7 +19,7 @@ ROOT = Path(__file__).resolve().parent.parent
 def run_ranks(port, *args):
     env = dict(os.environ, HEXL_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu", *args]
+           "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu", *args]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     print(out.stdout[-2000:], out.stderr[-2000:])
     assert out.returncode == 0
@@ -55,7 +55,7 @@ def test_gpus_flag_alone_launches_the_ranks():
     env = dict(os.environ, HEXL_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu", "--total-batch", "2048"]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu", "--total-batch", "2048"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     print(out.stdout[-2000:], out.stderr[-2000:])
     assert out.returncode == 0
@@ -88,7 +88,7 @@ def test_rccl_path_forced_on_one_gpu():
     env = dict(os.environ, HEXL_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "HEXL_BENCH_ONE_GPU"):
         env.pop(k, None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-pmc", "--light-extra",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu", "--no-pmc", "--light-extra",
            "--total-batch", "1024", "--barrier-per-step"]
     d = _one_json_line(subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT)))
     g = d["config"]["timing_group"]
@@ -108,7 +108,7 @@ def test_config_5_as_written_eight_ranks_batch_8192():
     env = dict(os.environ, HEXL_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "HEXL_BENCH_FORCE_DIST"):
         env.pop(k, None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--steps", "5", "--warmup", "1", "--cpu-seconds", "8"]
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "8", "--steps", "5", "--warmup", "1", "--full", "--cpu-seconds", "8"]
     d = _one_json_line(subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=str(ROOT)))
     assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["verified_vs_oracle"] is True
     assert d["config"]["global_batch"] == 8192 and d["config"]["batch_per_gpu"] == 1024

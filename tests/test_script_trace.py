@@ -1,6 +1,7 @@
 """CPU: the reference's runner scripts (tests/micro_*.sh, benchmark/micro_*.sh) are executed UNMODIFIED, as scripts, against recording
 stubs (tests/ref_harness/trace_scripts.py); the GPU suite replays what they executed. Only where the reference tree exists."""
 import json
+import os
 import sys
 from pathlib import Path
 
@@ -10,7 +11,7 @@ HARNESS = Path(__file__).resolve().parent / "ref_harness"
 REF = Path("/root/reference")
 
 
-@pytest.mark.skipif(not REF.exists(), reason="reference tree not present on this box")
+@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (or not readable) on this box")
 def test_reference_scripts_run_unmodified_and_trace(tmp_path):
     sys.path.insert(0, str(HARNESS))
     import trace_scripts
@@ -33,7 +34,7 @@ def test_reference_scripts_run_unmodified_and_trace(tmp_path):
 
 def test_committed_build_trace_matches_a_fresh_one_when_both_exist(tmp_path):
     built = HARNESS / "_build" / "script_trace.json"
-    if not (REF.exists() and built.exists()):
+    if not (os.path.isdir(REF) and built.exists()):
         pytest.skip("needs the reference tree and a built harness")
     sys.path.insert(0, str(HARNESS))
     import trace_scripts

@@ -1,6 +1,6 @@
 #!/bin/bash
 # profile_round.sh <tag> -- the round's evidence, written under gpurun_out/<tag>/ on the GPU box:
-#   kernel trace of the default bench.py run, PMC passes (one counter group per run, with --kernel-trace only)
+#   kernel trace of a bench.py --full run, PMC passes (one counter group per run, with --kernel-trace only)
 #   of tools/profile_ks.py, the text summaries and the traffic JSON that bench.py reads.
 TAG=${1:-r01}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -9,7 +9,7 @@ mkdir -p $OUT && cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/kt $OUT/pmc
 # one lane: the default schedule alternates chunks between two streams, whose kernels then overlap and stretch each
 # other's durations in the trace; one lane gives per-kernel durations that add up (bench.py's stage timers are one-lane too)
-HEXL_KS_ONE_LANE=1 rocprofv3 --kernel-trace --stats -d $OUT/kt -- python $R/bench.py --no-cpu --no-pmc > $OUT/bench_under_trace.log 2>&1
+HEXL_KS_ONE_LANE=1 rocprofv3 --kernel-trace --stats -d $OUT/kt -- python $R/bench.py --full --no-cpu --no-pmc > $OUT/bench_under_trace.log 2>&1
 # bench.py starts child processes (tests/cpp/bench_cxx_api for the end-to-end leg), each with its own database: the largest one is bench.py's
 DB=$(find $OUT/kt -name "*.db" -printf "%s %p\n" | sort -n | tail -1 | cut -d" " -f2-)
 python3 $R/tools/rocprof_summary.py $DB > $OUT/kernel_trace.txt 2>&1
@@ -31,5 +31,5 @@ python3 $R/tools/pmc_summary.py $OUT/pmc 256 7 > $OUT/pmc.txt 2>&1
 cp $OUT/pmc/traffic.json $OUT/traffic.json 2>/dev/null
 cp $OUT/pmc/alu.json $OUT/alu.json 2>/dev/null
 rm -rf $OUT/pmc $OUT/kt
-python $R/bench.py 2> $OUT/bench.err | tail -1 > $OUT/bench.json
+python $R/bench.py --full 2> $OUT/bench.err | tail -1 > $OUT/bench.json
 tail -3 $OUT/pmc.txt
