@@ -52,6 +52,9 @@ C_ABI = {
     "hexl_ks_range_check": [_vp],
     "hexl_ks_plan_tiers": [_vp, ctypes.POINTER(_i)],
     "hexl_multiply_relinearize": [_vp, _vp, _vp, _vp, _sz],
+    "hexl_apply_galois": [_vp, _vp, _vp, _sz, _u64, _u64],
+    "hexl_rescale": [_vp, _vp, _vp, _sz, _u64, _u64],
+    "hexl_rotate": [_vp, _vp, _vp, _sz, _u64],
     "hexl_ks_scratch_bytes": [_vp, _sz],
     "hexl_ntt_fwd_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64],
     "hexl_ntt_inv_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64, _u64, _u64],
@@ -170,6 +173,10 @@ class Context:
         _check(lib().hexl_dyadic_multiply(self.h, _ptr(out), _ptr(a), _ptr(b), batch, n, _ptr(moduli), n_moduli),
                "hexl_dyadic_multiply")
 
+    def apply_galois(self, out, inp, count: int, n: int, g: int):
+        """out[count][n] = X -> X^g of inp[count][n] in NTT form (a word permutation; out must not overlap inp)"""
+        _check(lib().hexl_apply_galois(self.h, _ptr(out), _ptr(inp), count, n, g), "hexl_apply_galois")
+
 
 class KeySwitchPlan:
     """Device state for one keyswitch parameter set (hexl_ks_plan): tables, constants, keys."""
@@ -211,8 +218,17 @@ class KeySwitchPlan:
         return list(out), rc == 1
 
     def multiply_relinearize(self, out, a, b, batch: int):
-        """out[batch][2][L][n] = (a0 b0, a0 b1 + a1 b0) + KeySwitch(a1 b1), one fused pass (N = 1024 ... 16384)"""
+        """out[batch][2][L][n] = (a0 b0, a0 b1 + a1 b0) + KeySwitch(a1 b1), one fused pass (N = 1024 ... 32768, moduli < 2^52)"""
         _check(lib().hexl_multiply_relinearize(self.h, _ptr(out), _ptr(a), _ptr(b), batch), "hexl_multiply_relinearize")
+
+    def rescale(self, out, inp, batch: int, n_limbs: int, n_components: int):
+        """out[batch][n_components][n_limbs - 1][n] = inp[batch][n_components][n_limbs][n] divided by q_(n_limbs - 1), rounded
+        (SEAL's rescale_to_next); moduli < 2^52, 2 <= n_limbs <= K - 1, no keys needed"""
+        _check(lib().hexl_rescale(self.h, _ptr(out), _ptr(inp), batch, n_limbs, n_components), "hexl_rescale")
+
+    def rotate(self, out, ct, batch: int, g: int):
+        """out[batch][2][L][n] = (sigma_g(c0), 0) + KeySwitch(sigma_g(c1)); the plan's keys switch from s(X^g) to s"""
+        _check(lib().hexl_rotate(self.h, _ptr(out), _ptr(ct), batch, g), "hexl_rotate")
 
     def keyswitch_host(self, results, t_targets):
         n = len(results)

@@ -320,6 +320,9 @@ extern "C" int hexl_ks_plan_destroy(hexl_ks_plan* p) {
     if (p->d_keys_nat) (void)hipFree(p->d_keys_nat);
     if (p->d_flag) (void)hipFree(p->d_flag);
     if (p->h_flag) (void)hipHostFree(p->h_flag);
+    if (p->d_rescale) (void)hipFree(p->d_rescale);
+    if (p->d_rs_s) (void)hipFree(p->d_rs_s);
+    if (p->d_rot_t) (void)hipFree(p->d_rot_t);
     delete p;
     return 0;
 }

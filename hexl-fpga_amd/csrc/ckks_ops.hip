@@ -1,0 +1,353 @@
+// ckks_ops.hip -- the two steps of a CKKS level beside multiply + relinearize, on the device (DESIGN.md "CKKS level operations"):
+//   rescale   divide by the last prime of the level and drop it (SEAL's rescale_to_next, rounding to nearest) -- the mod-down of the
+//             keyswitch (keyswitch_f64.hip k_ksf_intt_sp / k_ksf_moddown) with a data prime in place of the special prime:
+//               s   = (INTT_l(c_l) + half) mod q_l,  half = floor(q_l / 2)                                        k_rs_intt
+//               out = (c_i - NTT_i((s + fix_i) mod q_i)) * q_l^-1 mod q_i,  fix_i = q_i - (half mod q_i)          k_rs_down
+//             = NTT_i(round(X / q_l) mod q_i) for the CRT value X of every coefficient. FP64 plans only (moduli < 2^52).
+//   galois    X -> X^g on polynomials in NTT form: a pure index permutation of the transforms' bit-reversed output order,
+//               out[j] = in[brv(((2 brv(j) + 1) g mod 2n - 1) / 2)]                                              k_galois
+//             no arithmetic, no sign flips, no dependence on the root or the modulus.
+//   rotate    (sigma_g(c0), 0) + KeySwitch(sigma_g(c1)): one k_galois launch, then the keyswitch, per slice of instances.
+#include "hexl_internal.hpp"
+#include "ntt_core_f64.hpp"
+#include "number_theory.hpp"
+
+using namespace hx;
+
+struct RsArgs {
+    const KsModF64* mods;       // [K]
+    const double* tables;       // [K][4][n] (keyswitch_f64.hip KsArgsF)
+    const KsRescaleF64* rm;     // [l]: constants of the level that drops limb l
+    const u64* in;              // [nb][ncomp][l + 1][n]
+    u64* out;                   // [nb][ncomp][l][n]
+    double* s;                  // [nb][ncomp][n]  s = (INTT_l(c_l) + half) mod q_l, canonical, natural order
+    double half;                // floor(q_l / 2)
+    u32 l;                      // the limb dropped (n_limbs - 1)
+    unsigned long long tiermap; // LAZY = -1: nibble i = reduction period of limb i (keyswitch_f64.hip)
+};
+
+__device__ __forceinline__ u32 xcd_item_rs(u32 bid, u32 total) {   // XCD-contiguous work ranges, as keyswitch_f64.hip xcd_item_f
+    const u32 q = total >> 3, r = total & 7, xcd = bid & 7, j = bid >> 3;
+    return xcd * q + (xcd < r ? xcd : r) + j;
+}
+
+// one workgroup per (instance, component): s = (INTT_{q_l}(c_l) + half) mod q_l, as k_ksf_intt_sp does for the special prime
+template <int LOGN, int LOGE, int LAZY>
+__global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_rs_intt(RsArgs a) {
+    using G = Geom<LOGN, LOGE>;
+    extern __shared__ __attribute__((aligned(16))) double ldsd[];
+    const int tid = threadIdx.x;
+    const u32 item = blockIdx.x;                                  // b*ncomp + k
+    const u32 l = a.l;
+    const KsModF64 md = a.mods[l];
+    const Mod m = md.m;
+    const double* tb = a.tables + size_t(l) * 4 * G::N;
+    const u64* src = a.in + (size_t(item) * (l + 1) + l) * G::N;
+    const u32 tB = u32(G::idxB(0, tid));
+    double v[G::E];
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) v[r] = hxf::reduce(hxf::to_f64((src + G::idxB(r, 0))[tB]), m);
+    with_tier<LAZY, false>(a.tiermap, l, [&](auto T) {            // one transform per workgroup: FRESH
+        WgNttF64<LOGN, LOGE, decltype(T)::value>::template inverse<true>(v, ldsd, tid, tb + 2 * G::N, tb + 3 * G::N, m, md.sc);
+    });
+    double* dst = a.s + size_t(item) * G::N;
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) (dst + G::idxA(r, 0))[u32(tid)] = hxf::lift(hxf::reduce(hxf::lift(v[r], m) + a.half, m), m);
+}
+
+// one workgroup per (instance, component, i < l): w = NTT_{q_i}((s + fix_i) mod q_i); out = (c_i - w) * q_l^-1 mod q_i
+template <int LOGN, int LOGE, int LAZY>
+__global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_rs_down(RsArgs a) {
+    using G = Geom<LOGN, LOGE>;
+    extern __shared__ __attribute__((aligned(16))) double ldsd[];
+    const int tid = threadIdx.x;
+    const u32 l = a.l;
+    // (b*ncomp + k)*l + i, XCD-contiguous: the l transforms that read the same s run back to back on one XCD
+    const u32 item = __builtin_amdgcn_readfirstlane(xcd_item_rs(blockIdx.x, gridDim.x));
+    const u32 bk = item / l, i = item - bk * l;
+    const KsModF64 md = a.mods[i];
+    const KsRescaleF64 rc = a.rm[i];
+    const Mod m = md.m;
+    const double* tb = a.tables + size_t(i) * 4 * G::N;
+    const double* sk = a.s + size_t(bk) * G::N;
+    double v[G::E];
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) v[r] = hxf::reduce((sk + G::idxA(r, 0))[u32(tid)] + rc.fix, m);
+    const u64* ci = a.in + (size_t(bk) * (l + 1) + i) * G::N;
+    const u32 tB = u32(G::idxB(0, tid));
+    u64 craw[G::E];
+    // FINAL: w range-reduced (|w| <= p/2 + 2), so |c_i - w| <= p + 4 is inside mul_shoup's documented bound. Mixed tiers (LAZY = -1):
+    // two schedules, strict and period 3 (valid for every lazy limb), and c_i loaded behind the transform: the four schedules of N = 16384
+    // with c_i requested early spill (132 bytes per lane)
+    with_tier<LAZY, false>(a.tiermap, i, [&](auto T) {
+        using W = WgNttF64<LOGN, LOGE, decltype(T)::value>;
+        if constexpr (G::HALF_ONLY || LAZY < 0) {                  // N = 32768: no registers to hold c_i during the transform
+            W::template forward<true, true>(v, ldsd, tid, tb, tb + G::N, m);
+#pragma unroll
+            for (int r = 0; r < G::E; ++r) craw[r] = (ci + G::idxB(r, 0))[tB];
+        } else {                                                   // c_i requested behind the cross-wave re-deal
+            W::template forward<true, true>(v, ldsd, tid, tb, tb + G::N, m, [&] {
+#pragma unroll
+                for (int r = 0; r < G::E; ++r) craw[r] = (ci + G::idxB(r, 0))[tB];
+            });
+        }
+    });
+    u64* dst = a.out + (size_t(bk) * l + i) * G::N;
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) {
+        const double c = hxf::reduce(hxf::to_f64(craw[r]), m);
+        (dst + G::idxB(r, 0))[tB] = hxf::from_f64(hxf::lift(hxf::reduce(hxf::mul_shoup(c - v[r], rc.qlinv, rc.qlinv_p, m), m), m));
+    }
+}
+
+// ---- Galois automorphism in NTT form ----
+__device__ __forceinline__ u32 galois_src(u32 j, u32 logn, u32 g) {
+    const u32 rj = __builtin_bitreverse32(j) >> (32 - logn);
+    const u32 e = ((2 * rj + 1) * g) & ((2u << logn) - 1);      // (2 brv(j) + 1) g mod 2n; both factors < 2^16
+    return __builtin_bitreverse32((e - 1) >> 1) >> (32 - logn);
+}
+
+struct GaloisArgs {
+    const u64* in;              // [count][n]
+    u64* out;                   // [count][n]
+    u64* t;                     // rotate: [count / (2 L)][L][n] receives component 1; nullptr: every polynomial goes to `out`
+    size_t count;               // polynomials
+    u32 logn, g, L;
+};
+
+// Polynomial p of the input goes to polynomial p of `out`. Rotate (t != nullptr, p = (b*2 + k)*L + j): component 1 goes to t[b][j]
+// instead, and out[b][1][j] is zeroed -- the keyswitch then adds into (sigma(c0), 0).
+// LDS (n <= 16384, 128 KiB): a coalesced load of the whole polynomial, the gather from LDS, a coalesced store.
+// n = 32768 does not fit: the gather reads global memory (the sources of neighbouring outputs mostly lie within a few words).
+template <bool LDS>
+__global__ __launch_bounds__(1024) void k_galois(GaloisArgs a) {
+    typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
+    extern __shared__ __attribute__((aligned(16))) u64 lds[];
+    const u32 n = 1u << a.logn, tid = threadIdx.x, T = blockDim.x;
+    for (size_t p = blockIdx.x; p < a.count; p += gridDim.x) {
+        const u64* src = a.in + p * n;
+        u64* dst = a.out + p * n;
+        if (a.t) {
+            const size_t bk = p / a.L, j = p - bk * a.L;
+            if (bk & 1) {
+                const u2 zero = {0, 0};
+                for (u32 c = tid; c < n / 2; c += T) reinterpret_cast<u2*>(dst)[c] = zero;
+                dst = a.t + ((bk >> 1) * a.L + j) * n;
+            }
+        }
+        if constexpr (LDS) {
+            for (u32 c = tid; c < n / 2; c += T) reinterpret_cast<u2*>(lds)[c] = reinterpret_cast<const u2*>(src)[c];
+            __syncthreads();
+            for (u32 c = tid; c < n / 2; c += T) {
+                const u2 w = {lds[galois_src(2 * c, a.logn, a.g)], lds[galois_src(2 * c + 1, a.logn, a.g)]};
+                reinterpret_cast<u2*>(dst)[c] = w;
+            }
+            __syncthreads();                                      // the next polynomial's load overwrites lds
+        } else {
+            for (u32 c = tid; c < n / 2; c += T) {
+                const u2 w = {src[galois_src(2 * c, a.logn, a.g)], src[galois_src(2 * c + 1, a.logn, a.g)]};
+                reinterpret_cast<u2*>(dst)[c] = w;
+            }
+        }
+    }
+}
+
+static int launch_galois(hexl_ctx* c, hipStream_t st, const GaloisArgs& a) {
+    if (!a.count) return 0;
+    const u32 n = 1u << a.logn;
+    const u32 grid = a.count < 65536 ? (u32)a.count : 65536u;
+    if (a.logn <= 14) {
+        static PerDeviceOnce once;
+        if (int rc = once.run(c->device, [] {
+                HX_CHECK(hipFuncSetAttribute((const void*)k_galois<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8));
+                return 0;
+            }))
+            return rc;
+        hipLaunchKernelGGL(k_galois<true>, dim3(grid), dim3(n >= 2048 ? 1024 : 512), size_t(n) * 8, st, a);
+    } else {
+        hipLaunchKernelGGL(k_galois<false>, dim3(grid), dim3(1024), 0, st, a);
+    }
+    return (int)hipGetLastError();
+}
+
+int hx_launch_galois(hexl_ctx* c, u64* d_out, const u64* d_in, size_t count, u32 logn, u32 g) {
+    GaloisArgs a{d_in, d_out, nullptr, count, logn, g, 1};
+    return launch_galois(c, c->stream, a);
+}
+
+// ---- rescale ----
+template <int LOGN, int LOGE, int LAZY>
+static int run_rescale(hexl_ks_plan* p, const RsArgs& a, u32 nb, u32 ncomp) {
+    using G = Geom<LOGN, LOGE>;
+    static PerDeviceOnce once;
+    if (int rc0 = once.run(p->ctx->device, [] {
+            HX_CHECK(hipFuncSetAttribute((const void*)k_rs_intt<LOGN, LOGE, LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_USED));
+            HX_CHECK(hipFuncSetAttribute((const void*)k_rs_down<LOGN, LOGE, LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_USED));
+            return 0;
+        }))
+        return rc0;
+    hipStream_t st = p->ctx->stream;
+    hipLaunchKernelGGL((k_rs_intt<LOGN, LOGE, LAZY>), dim3(nb * ncomp), dim3(G::T), G::LDS_USED, st, a);
+    hipLaunchKernelGGL((k_rs_down<LOGN, LOGE, LAZY>), dim3(nb * ncomp * a.l), dim3(G::T), G::LDS_USED, st, a);
+    return (int)hipGetLastError();
+}
+
+// the (LOGN, LOGE) and tier instantiations of run_chunk_f64 (keyswitch_f64.hip): LAZY = -1 when the limbs of the level differ in tier
+static int dispatch_rescale(hexl_ks_plan* p, const RsArgs& a, u32 nb, u32 ncomp, int lazy) {
+    if (lazy < 0) {
+        switch (p->logn) {
+            case 10: return run_rescale<10, 4, -1>(p, a, nb, ncomp);
+            case 11: return run_rescale<11, 5, -1>(p, a, nb, ncomp);
+            case 12: return run_rescale<12, 5, -1>(p, a, nb, ncomp);
+            case 13: return run_rescale<13, 5, -1>(p, a, nb, ncomp);
+            case 14: return run_rescale<14, 4, -1>(p, a, nb, ncomp);
+            case 15: return run_rescale<15, 5, -1>(p, a, nb, ncomp);
+            default: return HEXL_E_BADARG;
+        }
+    }
+    if (lazy > 0) {
+        switch (p->logn) {
+            case 10: return run_rescale<10, 4, 3>(p, a, nb, ncomp);
+            case 11: return run_rescale<11, 5, 3>(p, a, nb, ncomp);
+            case 12: return run_rescale<12, 5, 3>(p, a, nb, ncomp);
+            case 13: return run_rescale<13, 5, 3>(p, a, nb, ncomp);
+            case 15: return run_rescale<15, 5, 3>(p, a, nb, ncomp);
+            case 14: return lazy == 12 ? run_rescale<14, 4, 12>(p, a, nb, ncomp)
+                          : lazy == 6 ? run_rescale<14, 4, 6>(p, a, nb, ncomp)
+                                      : run_rescale<14, 4, 3>(p, a, nb, ncomp);
+            default: return HEXL_E_BADARG;
+        }
+    }
+    switch (p->logn) {
+        case 10: return run_rescale<10, 4, 0>(p, a, nb, ncomp);
+        case 11: return run_rescale<11, 5, 0>(p, a, nb, ncomp);
+        case 12: return run_rescale<12, 5, 0>(p, a, nb, ncomp);
+        case 13: return run_rescale<13, 5, 0>(p, a, nb, ncomp);
+        case 14: return run_rescale<14, 4, 0>(p, a, nb, ncomp);
+        case 15: return run_rescale<15, 5, 0>(p, a, nb, ncomp);
+        default: return HEXL_E_BADARG;
+    }
+}
+
+// per-level constants, computed on the host at the first rescale that drops limb l and kept in the plan
+static int rescale_constants(hexl_ks_plan* p, u32 l) {
+    if (!p->d_rescale) {
+        HX_CHECK(hipMalloc((void**)&p->d_rescale, size_t(16) * 16 * sizeof(KsRescaleF64)));
+        p->rescale_levels = 0;
+    }
+    if (p->rescale_levels >> l & 1u) return 0;
+    const u64 ql = p->moduli[l], half = ql >> 1;
+    KsRescaleF64 rm[16];
+    for (u32 i = 0; i < l; ++i) {
+        const u64 q = p->moduli[i];
+        const double pd = (double)q;
+        const u64 inv = hxnt::invmod(ql % q, q);
+        rm[i].fix = (double)(q - half % q);                       // in [1, q]
+        rm[i].qlinv = inv > q / 2 ? (double)inv - pd : (double)inv;
+        rm[i].qlinv_p = rm[i].qlinv / pd;
+        rm[i].half = (double)half;
+    }
+    HX_CHECK(hipMemcpy(p->d_rescale + size_t(l) * 16, rm, l * sizeof(KsRescaleF64), hipMemcpyHostToDevice));
+    p->rescale_levels |= 1u << l;
+    return 0;
+}
+
+int hx_launch_rescale(hexl_ks_plan* p, u64* d_out, const u64* d_in, size_t batch, u32 n_limbs, u32 ncomp) {
+    const u32 l = n_limbs - 1;
+    if (int rc = rescale_constants(p, l)) return rc;
+    if (!batch) return 0;
+    const size_t n = p->n;
+    const size_t chunk = batch < hx_ks_chunk(p) ? batch : hx_ks_chunk(p);
+    const size_t need = chunk * ncomp;                           // polynomials of s per chunk
+    if (p->rs_cap < need) {                                      // grow-only; earlier launches may still read the old one
+        if (p->d_rs_s) { HX_CHECK(hipDeviceSynchronize()); HX_CHECK(hipFree(p->d_rs_s)); }
+        p->d_rs_s = nullptr; p->rs_cap = 0;
+        HX_CHECK(hipMalloc((void**)&p->d_rs_s, need * n * sizeof(double)));
+        p->rs_cap = need;
+    }
+    // the schedule every limb of the level admits; LAZY = -1 (per-limb lookup) when they differ
+    int lazy = p->tier[0];
+    for (u32 i = 1; i <= l; ++i)
+        if (p->tier[i] != p->tier[0]) lazy = -1;
+    RsArgs a;
+    a.mods = p->d_mods_f64; a.tables = p->d_tables_f64;
+    a.rm = p->d_rescale + size_t(l) * 16;
+    a.s = p->d_rs_s;
+    a.half = (double)(p->moduli[l] >> 1);
+    a.l = l;
+    a.tiermap = 0;
+    for (u32 i = 0; i < p->K; ++i) a.tiermap |= (unsigned long long)(p->tier[i] & 15u) << (4 * i);
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t nb = batch - b0 < chunk ? batch - b0 : chunk;
+        a.in = d_in + b0 * ncomp * n_limbs * n;
+        a.out = d_out + b0 * ncomp * l * n;
+        if (int rc = dispatch_rescale(p, a, (u32)nb, ncomp, lazy)) return rc;
+    }
+    return 0;
+}
+
+// ---- rotate ----
+int hx_launch_rotate(hexl_ks_plan* p, u64* d_out, const u64* d_ct, size_t batch, u32 g) {
+    if (!batch) return 0;
+    if (!p->have_keys) return HEXL_E_NOKEYS;
+    const size_t n = p->n, L = p->L;
+    const size_t slice = batch < hx_ks_chunk(p) ? batch : hx_ks_chunk(p);
+    if (p->rot_cap < slice) {                                    // grow-only; earlier launches may still read the old one
+        if (p->d_rot_t) { HX_CHECK(hipDeviceSynchronize()); HX_CHECK(hipFree(p->d_rot_t)); }
+        p->d_rot_t = nullptr; p->rot_cap = 0;
+        HX_CHECK(hipMalloc((void**)&p->d_rot_t, slice * L * n * sizeof(u64)));
+        p->rot_cap = slice;
+    }
+    for (size_t b0 = 0; b0 < batch; b0 += slice) {
+        const size_t nb = batch - b0 < slice ? batch - b0 : slice;
+        u64* out = d_out + b0 * 2 * L * n;
+        GaloisArgs a{d_ct + b0 * 2 * L * n, out, p->d_rot_t, nb * 2 * L, p->logn, g, (u32)L};
+        if (int rc = launch_galois(p->ctx, p->ctx->stream, a)) return rc;
+        // hx_launch_keyswitch joins its lanes back into the caller's stream before it returns (keyswitch.hip), so the next
+        // slice's gather into the same t buffer runs after this keyswitch has read it
+        if (int rc = hx_launch_keyswitch(p, out, p->d_rot_t, nb, 7, nullptr)) return rc;
+    }
+    return 0;
+}
+
+// ---- entry points of include/hexl_mi355x.h. They live here rather than in capi.hip, whose host half the CPU staging model
+// (tests/cpp) compiles against stubs of the launchers it calls. ----
+static bool ring_dimension_ok(u64 n) { return n >= 1024 && n <= 32768 && !(n & (n - 1)); }
+// [a, a + abytes) and [b, b + bbytes) share a byte
+static bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
+    return (const char*)a < (const char*)b + bbytes && (const char*)b < (const char*)a + abytes;
+}
+static bool galois_elt_ok(u64 g, u64 n) { return (g & 1) && g < 2 * n; }
+
+extern "C" int hexl_apply_galois(hexl_ctx* c, uint64_t* d_out, const uint64_t* d_in, size_t count, uint64_t n, uint64_t g) {
+    if (!c || !d_out || !d_in || !ring_dimension_ok(n) || !galois_elt_ok(g, n)) return HEXL_E_BADARG;
+    if (count > (SIZE_MAX / sizeof(u64)) / n) return HEXL_E_BADARG;
+    const size_t bytes = count * n * sizeof(u64);
+    if (ranges_overlap(d_out, bytes, d_in, bytes)) return HEXL_E_BADARG;    // a permutation cannot run in place
+    if (!count) return 0;
+    u32 logn = 0;
+    while ((1ULL << logn) < n) ++logn;
+    HX_CHECK(hipSetDevice(c->device));
+    return hx_launch_galois(c, d_out, d_in, count, logn, (u32)g);
+}
+
+extern "C" int hexl_rescale(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_in, size_t batch, uint64_t n_limbs,
+                            uint64_t n_components) {
+    if (!p || !d_out || !d_in || !p->use_f64 || p->logn < 10 || p->logn > 15) return HEXL_E_BADARG;
+    if (n_limbs < 2 || n_limbs > p->K - 1 || n_components < 1 || n_components > 3) return HEXL_E_BADARG;
+    const size_t per = size_t(n_components) * p->n * sizeof(u64);
+    if (batch > SIZE_MAX / (per * n_limbs)) return HEXL_E_BADARG;
+    if (ranges_overlap(d_out, batch * per * (n_limbs - 1), d_in, batch * per * n_limbs)) return HEXL_E_BADARG;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    return hx_launch_rescale(p, d_out, d_in, batch, (u32)n_limbs, (u32)n_components);
+}
+
+extern "C" int hexl_rotate(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t g) {
+    if (!p || !d_out || !d_ct || !galois_elt_ok(g, p->n)) return HEXL_E_BADARG;
+    const size_t per = 2 * size_t(p->L) * p->n * sizeof(u64);
+    if (batch > SIZE_MAX / per) return HEXL_E_BADARG;
+    if (ranges_overlap(d_out, batch * per, d_ct, batch * per)) return HEXL_E_BADARG;   // component 1 of d_out is zeroed before the keyswitch
+    if (!p->have_keys) return HEXL_E_NOKEYS;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    return hx_launch_rotate(p, d_out, d_ct, batch, (u32)g);
+}

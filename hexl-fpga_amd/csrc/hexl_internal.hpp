@@ -91,6 +91,13 @@ struct KsModF64 {
     double half;         // floor(q_sp/2)
 };
 
+// per-level constants of the rescale that drops limb l (ckks_ops.hip), one per limb i < l; residues centred, *_p = fl(value / p)
+struct KsRescaleF64 {
+    double fix;          // q_i - (floor(q_l/2) mod q_i), in [1, q_i]
+    double qlinv, qlinv_p;   // q_l^-1 mod q_i
+    double half;         // floor(q_l/2)
+};
+
 // lanes (auxiliary streams) the chunks of one keyswitch call alternate between: 2 in production; HEXL_KS_LANES=3|4 is the
 // experiment that bounds what a single launch per chunk could gain (tools/experiments/README.md, round 4)
 constexpr int HX_KS_MAX_LANES = 4;
@@ -141,6 +148,13 @@ struct hexl_ks_plan {
     u32 host_epoch = 0;
     hipStream_t cur = nullptr;        // stream the chunk being launched goes to
     u64* cur_scratch = nullptr;
+    // CKKS level operations (ckks_ops.hip), all allocated at first use
+    KsRescaleF64* d_rescale = nullptr;   // [16][16]: row l = constants of the rescale that drops limb l (filled at its first call)
+    u32 rescale_levels = 0;           // bit l: row l is filled
+    double* d_rs_s = nullptr;         // rescale scratch: s for rs_cap (instance, component) pairs, n doubles each (grow-only)
+    size_t rs_cap = 0;
+    u64* d_rot_t = nullptr;           // rotate: sigma_g(c1) of one slice of rot_cap instances, [rot_cap][L][n] (grow-only)
+    size_t rot_cap = 0;
 };
 
 // launcher prototypes implemented per translation unit
@@ -165,6 +179,10 @@ bool hx_ks_can_overwrite(const hexl_ks_plan*, size_t nb);
 bool hx_ks_lat_applies(const hexl_ks_plan*, size_t nb);
 int hx_launch_keyswitch_lat(hexl_ks_plan*, u64* d_result, const u64* d_t_target, size_t nb);
 int hx_launch_multiply_relinearize(hexl_ks_plan*, u64* d_out, const u64* d_a, const u64* d_b, size_t batch);
+// CKKS level operations (ckks_ops.hip); arguments checked by their entry points (hexl_apply_galois, hexl_rescale, hexl_rotate)
+int hx_launch_galois(hexl_ctx*, u64* d_out, const u64* d_in, size_t count, u32 logn, u32 g);
+int hx_launch_rescale(hexl_ks_plan*, u64* d_out, const u64* d_in, size_t batch, u32 n_limbs, u32 n_components);
+int hx_launch_rotate(hexl_ks_plan*, u64* d_out, const u64* d_ct, size_t batch, u32 g);
 u32 hx_ks_x_loge();
 // index of coefficient held in register r of thread tid after a forward transform ("B layout")
 u32 hx_idxB(u32 logn, u32 r, u32 tid);

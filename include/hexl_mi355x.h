@@ -53,7 +53,7 @@ int hexl_ctx_describe(hexl_ctx* ctx, char* buf, size_t buflen);
 /* K1 -- batched negacyclic forward NTT, in place, bit-exact with fwd_ntt_kernel
  * (device/fwd_ntt.cpp:82-497; launchers fwd_ntt/ntt_input/ntt_output :619-646).
  * d_x[batch][n]; one modulus and one table pair (bit-reversed order, n words each) per batch.
- * n in {1024, 2048, 4096, 8192, 16384} (reference: 16384 only, host/src/ntt.cpp:24). */
+ * n in {1024, 2048, 4096, 8192, 16384, 32768} (reference: 16384 only, host/src/ntt.cpp:24). */
 int hexl_ntt_fwd(hexl_ctx* ctx, uint64_t* d_x, size_t batch, const uint64_t* d_roots,
                  const uint64_t* d_precon, uint64_t q, uint64_t n);
 
@@ -119,6 +119,31 @@ int hexl_ks_range_check(hexl_ks_plan* plan);
  *   d_out must not overlap d_a or d_b (component 0 is stored before component 1's operands are read): HEXL_E_BADARG. */
 int hexl_multiply_relinearize(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_a,
                               const uint64_t* d_b, size_t batch);
+/* CKKS level operations beside hexl_multiply_relinearize: a ciphertext stays on the device through multiply + relinearize ->
+ * rescale -> rotate. All three are asynchronous on the context's stream.
+ *
+ * Galois automorphism X -> X^galois_elt on `count` polynomials of n words each in NTT form, in the transforms' (bit-reversed) output
+ * order: out[j] = in[brv(((2 brv(j) + 1) g mod 2n - 1) / 2)], brv = bit reversal over log2(n) bits. Words are moved, never interpreted:
+ * any 64-bit value survives and no modulus is involved. n = 1024 ... 32768; galois_elt odd and below 2n. d_out must not overlap d_in.
+ * Anything else: HEXL_E_BADARG. */
+int hexl_apply_galois(hexl_ctx* ctx, uint64_t* d_out, const uint64_t* d_in, size_t count, uint64_t n, uint64_t galois_elt);
+/* Rescale (SEAL's rescale_to_next): divide by the last modulus of the level and drop it, rounding to nearest.
+ *   d_in  [batch][n_components][n_limbs][n]      NTT form, words < q_i, moduli = the plan's first n_limbs
+ *   d_out [batch][n_components][n_limbs - 1][n]  WRITTEN with NTT_i(round(X / q_l) mod q_i), l = n_limbs - 1, X the CRT value of
+ *                                                each coefficient
+ * 2 <= n_limbs <= K - 1 (the last plan modulus is the special prime), 1 <= n_components <= 3; FP64 plans only (every modulus < 2^52)
+ * and n = 1024 ... 32768, as hexl_multiply_relinearize; d_out must not overlap d_in. Anything else: HEXL_E_BADARG. Needs no keys.
+ * The first call for a level computes that level's constants on the host and keeps them in the plan (< 8 KiB for all levels).
+ * Device memory kept by the plan, grow-only: min(batch, chunk) x n_components x n doubles of scratch, chunk = 256 instances at
+ * n = 16384 (the same number of coefficients at other n) -- 64 MiB for two components. */
+int hexl_rescale(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_in, size_t batch, uint64_t n_limbs,
+                 uint64_t n_components);
+/* Rotate: d_ct[batch][2][L][n] -> d_out[batch][2][L][n] WRITTEN with (sigma_g(c0), 0) + KeySwitch(sigma_g(c1)), sigma_g the Galois
+ * automorphism above. The plan's keys must be the switching key from s(X^g) to s (the caller's responsibility). Runs on every plan
+ * hexl_keyswitch accepts, integer kernels included. HEXL_E_NOKEYS before hexl_ks_set_keys; HEXL_E_BADARG for a galois_elt that is
+ * even or >= 2n, or d_out overlapping d_ct. Device memory kept by the plan, grow-only, beside the keyswitch's scratch:
+ * min(batch, chunk) x L x n words (sigma_g(c1) of one slice; 224 MiB at n = 16384, L = 7). */
+int hexl_rotate(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t galois_elt);
 /* Arithmetic tier per limb (introspection for logs and tests): tiers[i], i < key_modulus_size, = the forward transforms' range-
  * reduction period modulo q_i on the FP64 path -- 12 / 6 / 3 for q_i <= 2^49 / 2^50 / 2^51 (1 + 2^-7), 0 = every value reduced after
  * every operation (q_i up to 2^52); -1 for every limb of a plan on the integer kernels (a modulus >= 2^52). Every transform runs modulo
