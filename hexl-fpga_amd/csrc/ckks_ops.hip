@@ -52,7 +52,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_rs_intt(RsArgs a) {
     });
     double* dst = a.s + size_t(item) * G::N;
 #pragma unroll
-    for (int r = 0; r < G::E; ++r) (dst + G::idxA(r, 0))[u32(tid)] = hxf::lift(hxf::reduce(hxf::lift(v[r], m) + a.half, m), m);
+    for (int r = 0; r < G::E; ++r) (dst + G::idxA(r, 0))[u32(tid)] = hxf::rs_round(v[r], a.half, m);
 }
 
 // one workgroup per (instance, component, i < l): w = NTT_{q_i}((s + fix_i) mod q_i); out = (c_i - w) * q_l^-1 mod q_i
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_rs_down(RsArgs a) {
     const double* sk = a.s + size_t(bk) * G::N;
     double v[G::E];
 #pragma unroll
-    for (int r = 0; r < G::E; ++r) v[r] = hxf::reduce((sk + G::idxA(r, 0))[u32(tid)] + rc.fix, m);
+    for (int r = 0; r < G::E; ++r) v[r] = hxf::rs_shift((sk + G::idxA(r, 0))[u32(tid)], rc.fix, m);
     const u64* ci = a.in + (size_t(bk) * (l + 1) + i) * G::N;
     const u32 tB = u32(G::idxB(0, tid));
     u64 craw[G::E];
@@ -94,10 +94,8 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_rs_down(RsArgs a) {
     });
     u64* dst = a.out + (size_t(bk) * l + i) * G::N;
 #pragma unroll
-    for (int r = 0; r < G::E; ++r) {
-        const double c = hxf::reduce(hxf::to_f64(craw[r]), m);
-        (dst + G::idxB(r, 0))[tB] = hxf::from_f64(hxf::lift(hxf::reduce(hxf::mul_shoup(c - v[r], rc.qlinv, rc.qlinv_p, m), m), m));
-    }
+    for (int r = 0; r < G::E; ++r)
+        (dst + G::idxB(r, 0))[tB] = hxf::from_f64(hxf::rs_down(hxf::to_f64(craw[r]), v[r], rc.qlinv, rc.qlinv_p, m));
 }
 
 // ---- Galois automorphism in NTT form ----

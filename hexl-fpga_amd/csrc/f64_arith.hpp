@@ -83,6 +83,20 @@ HX_HD uint64_t from_f64(double x) {
     return b & 0x000FFFFFFFFFFFFFull;
 }
 
+// ---- the scalar chains of the rescale (ckks_ops.hip k_rs_intt / k_rs_down), here so that tests/cpp/f64_selftest.cpp replays the
+// kernels' own source against 128-bit integers for every pairing of a dropped modulus q_l with a kept modulus q_i ----------------
+// s = (v + half) mod q_l, canonical: v a range-reduced output of INTT_l (|v| <= q_l/2 + 2), half = floor(q_l / 2); m = q_l.
+// lift(v) + half < 1.5 q_l < 2^53.
+HX_HD double rs_round(double v, double half, const Mod m) { return lift(reduce(lift(v, m) + half, m), m); }
+// (s + fix) mod q_i, centred: 0 <= s < q_l, fix = q_i - (half mod q_i) in [1, q_i]; m = q_i. s + fix < 2^52 + 2^52; the quotient inside
+// reduce has up to 26 bits (q_l just below 2^52 beside a 27-bit q_i).
+HX_HD double rs_shift(double s, double fix, const Mod m) { return reduce(s + fix, m); }
+// (c - w) q_l^-1 mod q_i, canonical: c a canonical word of limb i as a double, w the range-reduced output of NTT_i (|w| <= q_i/2 + 2),
+// (qlinv, qlinv_p) = q_l^-1 mod q_i centred and fl(./q_i); m = q_i. |reduce(c) - w| <= q_i + 4, inside mul_shoup's 1.5 q_i.
+HX_HD double rs_down(double c, double w, double qlinv, double qlinv_p, const Mod m) {
+    return lift(reduce(mul_shoup(reduce(c, m) - w, qlinv, qlinv_p, m), m), m);
+}
+
 // The STRICT butterflies (every value reduced after every operation) leave room above 2^52: the largest intermediate is the
 // inverse butterfly's |h - k p| <= (1.31 + 0.22) p for |d| = |X - Y| <= p + 4 (quotient from the product: three roundings of a
 // value near p/2, ulp 1/2), the forward's |X + t| <= 1.4 p, all below 2^53 up to p ~ 2^52.39. The standalone _NTT / _INTT fast

@@ -4,6 +4,8 @@ Layouts are the library's: a polynomial in NTT form is n words in the transforms
 (NTT tables from MinimalPrimitiveRoot(2n, q), as hexl_ks_plan_create derives them without caller twiddles)."""
 import numpy as np
 
+from ks_util import extreme_words, rounding_edge_coeffs
+
 
 def bitrev(j, logn):
     j = np.asarray(j, dtype=np.int64)
@@ -91,6 +93,38 @@ def rescale_crt(lm, c, n_limbs):
         X = (X + lm.intt(c[i], i).astype(object) * (Qi * pow(Qi, -1, q))) % Q
     r = (X + qs[l] // 2) // qs[l]
     return np.stack([lm.ntt(np.array(r % qs[i], dtype=np.uint64), i) for i in range(l)])
+
+
+def rescale_input(lm, n_limbs, n_components, family, b, seed=1):
+    """instance b of a rescale input [n_components][n_limbs][n] (NTT form) from one of three families:
+    uniform   every word uniform below its modulus
+    extreme   every word of every limb from ks_util.extreme_words (q - 1, beside q / 2, 0, 1), in NTT form as it stands
+    edge      kept limbs as in `extreme`; the dropped limb is NTT_l(rounding_edge_coeffs), so INTT_l(c_l) is exactly those words and
+              s = (INTT_l(c_l) + half) mod q_l lands on 0, 1, q_l - 1 and both sides of the wrap"""
+    n, l = lm.n, n_limbs - 1
+    out = np.empty((n_components, n_limbs, n), dtype=np.uint64)
+    for k in range(n_components):
+        for i in range(n_limbs):
+            w = b * 7 + k * 3 + i
+            if family == "uniform":
+                out[k, i] = lm.orc.splitmix(n, seed * 1009 + b * 101 + k * 13 + i, lm.qs[i])
+            elif family == "edge" and i == l:
+                out[k, i] = lm.ntt(rounding_edge_coeffs(n, lm.qs[l], w + seed), l)
+            else:
+                assert family in ("extreme", "edge"), family
+                out[k, i] = extreme_words(n, lm.qs[i], w + seed)
+    return out
+
+
+def first_mismatch(got, want, shape_names, shape):
+    """'instance 3, limb 1, coefficient 77: got ..., want ...' for the first differing word of two flat arrays of `shape`"""
+    got, want = np.asarray(got).reshape(-1), np.asarray(want).reshape(-1)
+    bad = np.flatnonzero(got != want)
+    if not len(bad):
+        return "equal"
+    idx = np.unravel_index(bad[0], shape)
+    where = ", ".join(f"{nm} {int(v)}" for nm, v in zip(shape_names, idx))
+    return f"{where}: got {int(got[bad[0]])}, want {int(want[bad[0]])} ({len(bad)} of {len(got)} words differ)"
 
 
 def rescale(lm, x, batch, n_limbs, n_components):

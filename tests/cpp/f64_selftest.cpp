@@ -716,6 +716,64 @@ static void test_mixed_chain(uint64_t n, const std::vector<uint64_t>& chain, boo
     }
 }
 
+// ---- the rescale's scalar chains (f64_arith.hpp rs_round / rs_shift / rs_down, called by ckks_ops.hip k_rs_intt / k_rs_down) ---------
+// GPU tests visit a handful of modulus pairs; this replays the three expressions for every ordered pair (q_l dropped, q_i kept) of a
+// set that spans the tiers, against 128-bit integers: INTT outputs at +-(q_l/2 + 2) and 0, s on every wrap point of the rounding,
+// c on extreme_words' values (tests/ks_util.py), w at the ends of the range-reduced interval, and random draws. The intermediates
+// are recomputed here with the same primitives to track their magnitude (s + fix comes closest to 2^53: two moduli just below 2^52).
+static double g_rs_max = 0;
+static long g_rs_cases = 0;
+static inline void trackr(double x) { double a = x < 0 ? -x : x; if (a > g_rs_max) g_rs_max = a; }
+static void test_rescale_pair(uint64_t ql, uint64_t qi, int draws) {
+    const hxf::Mod ml{(double)ql, 1.0 / (double)ql}, mi{(double)qi, 1.0 / (double)qi};
+    const int64_t QL = (int64_t)ql, QI = (int64_t)qi, half = QL >> 1;
+    // the constants as ckks_ops.hip rescale_constants makes them
+    const double fix = (double)(qi - (uint64_t)half % qi);
+    const uint64_t inv = orc_invmod(ql % qi, qi);
+    const double qlinv = inv > qi / 2 ? (double)inv - (double)qi : (double)inv, qlinv_p = qlinv / (double)qi;
+    CHECK(fix >= 1 && fix <= (double)qi, "fix out of [1, q_i]: ql=%lu qi=%lu", ql, qi);
+    const std::vector<int64_t> vs = {0, 1, -1, QL / 2, -(QL / 2), QL / 2 + 1, -(QL / 2) - 1, QL / 2 + 2, -(QL / 2) - 2, half - 1, -(half - 1)};
+    const std::vector<int64_t> ss = {0, 1, 2, half - 2, half - 1, half, half + 1, half + 2, QL - 2, QL - 1};
+    const std::vector<int64_t> cs = {QI - 1, (QI - 1) / 2, (QI + 1) / 2, 0, 1, QI - 2, 2};
+    const std::vector<int64_t> ws = {0, 1, -1, QI / 2, -(QI / 2), QI / 2 + 1, -(QI / 2) - 1, QI / 2 + 2, -(QI / 2) - 2};
+    auto round_one = [&](int64_t v) {
+        const double got = hxf::rs_round((double)v, (double)half, ml);
+        const double lv = hxf::lift((double)v, ml);
+        trackr(lv); trackr(lv + (double)half); trackr(hxf::reduce(lv + (double)half, ml));
+        CHECK(got == (double)centred((i128)v + half, QL), "rs_round ql=%lu v=%ld got %.0f", ql, v, got);
+        ++g_rs_cases;
+    };
+    auto shift_one = [&](int64_t sv) {
+        const double got = hxf::rs_shift((double)sv, fix, mi);
+        trackr((double)sv + fix); trackr(got);
+        CHECK(got == (double)(int64_t)got && (int64_t)got >= -(QI / 2) - 2 && (int64_t)got <= QI / 2 + 2 &&
+              centred((i128)sv - half - (int64_t)got, QI) == 0, "rs_shift ql=%lu qi=%lu s=%ld got %.0f", ql, qi, sv, got);
+        ++g_rs_cases;
+        return got;
+    };
+    auto down_one = [&](int64_t c, int64_t w) {
+        const double got = hxf::rs_down((double)c, (double)w, qlinv, qlinv_p, mi);
+        const double d = hxf::reduce((double)c, mi) - (double)w;
+        const double h = d * qlinv, k = __builtin_rint(d * qlinv_p), pr = hxf::mul_shoup(d, qlinv, qlinv_p, mi);
+        trackr(d); trackr(__builtin_fma(-k, mi.p, h)); trackr(pr); trackr(hxf::reduce(pr, mi));
+        CHECK(got == (double)centred(((i128)c - w) * (int64_t)inv, QI), "rs_down ql=%lu qi=%lu c=%ld w=%ld got %.0f", ql, qi, c, w, got);
+        CHECK(hxf::from_f64(got) == (uint64_t)got, "rs_down word ql=%lu qi=%lu", ql, qi);
+        ++g_rs_cases;
+    };
+    for (int64_t v : vs) round_one(v);
+    for (int64_t sv : ss) {
+        const double w = shift_one(sv);
+        for (int64_t c : cs) down_one(c, (int64_t)w);             // the shifted value itself as w (a one-point transform)
+    }
+    for (int64_t c : cs)
+        for (int64_t w : ws) down_one(c, w);
+    for (int it = 0; it < draws; ++it) {
+        round_one((int64_t)(rnd() % (uint64_t)(QL + 5)) - (QL / 2 + 2));
+        shift_one((int64_t)(rnd() % ql));
+        down_one((int64_t)(rnd() % qi), (int64_t)(rnd() % (uint64_t)(QI + 5)) - (QI / 2 + 2));
+    }
+}
+
 int main() {
     std::vector<uint64_t> primes;
     uint64_t tmp[8];
@@ -875,6 +933,26 @@ int main() {
         std::printf("limbs of different tiers (seal chain 52,30,30,40,27,27,27 + four-tier ladder, every pair): max |x| seen = 2^%.3f (limit 2^53)\n",
                     log2(g_mixed_max));
         CHECK(g_mixed_max < 9007199254740992.0, "mixed-tier bound exceeded");
+    }
+    // the rescale's scalar chains: every ordered pair of {27, 30, 40, 49, 50, 51-bit, both sides of 2^51 (1 + 2^-7), the two largest < 2^52},
+    // largest primes = 1 mod 2^15 below each power of two (and the bench's first prime above 2^51)
+    {
+        std::vector<uint64_t> rs;
+        auto below = [](uint64_t limit) { for (uint64_t v = (limit - 2) / 32768 * 32768 + 1;; v -= 32768) if (v < limit && orc_is_prime(v)) return v; };
+        auto from = [](uint64_t start) { for (uint64_t v = (start + 32766) / 32768 * 32768 + 1;; v += 32768) if (v >= start && orc_is_prime(v)) return v; };
+        for (int b : {27, 30, 40, 49, 50, 51, 52}) rs.push_back(below(1ull << b));
+        rs.push_back(primes[0]);
+        rs.push_back(below(rs[6]));                               // two moduli just below 2^52: s + fix just below 2^53
+        rs.push_back(below((1ull << 51) + (1ull << 44) + 1));
+        rs.push_back(from((1ull << 51) + (1ull << 44) + 1));
+        CHECK((double)rs[9] <= hxf::LAZY_MAX_MODULUS && (double)rs[10] > hxf::LAZY_MAX_MODULUS && rs[6] < (1ull << 52) && rs[0] < (1ull << 27),
+              "rescale moduli do not straddle the lazy / strict boundary");
+        for (uint64_t ql : rs)
+            for (uint64_t qi : rs)
+                if (ql != qi) test_rescale_pair(ql, qi, 40000);
+        std::printf("rescale chains rs_round / rs_shift / rs_down (%zu moduli, every ordered pair, %ld cases): max |x| seen = 2^%.3f (limit 2^53)\n",
+                    rs.size(), g_rs_cases, log2(g_rs_max));
+        CHECK(g_rs_max < 9007199254740992.0, "rescale bound exceeded");
     }
     std::printf("folded multiply-accumulate: max |acc| / p seen = %.3f (bound 1.6)\n", g_fold_max);
     std::printf(failures ? "F64 SELFTEST: %d FAILURE(S)\n" : "F64 SELFTEST: ALL PASSED (%d primes)\n", failures ? failures : (int)primes.size());

@@ -105,6 +105,73 @@ def tier_ladder(orc, K, n):
     return out
 
 
+def big_dropped(orc, n):
+    """K = 4, used with n_limbs = 3: the rescale drops the largest prime below 2^52 beside two 30-bit limbs (the quotient inside
+    reduce(s + fix_i) has 22 bits); the special prime is a 27-bit one"""
+    return primes_below(orc, 2, 1 << 30, n) + primes_below(orc, 1, 1 << 52, n) + primes_below(orc, 1, 1 << 27, n)
+
+
+def small_dropped(orc, n):
+    """the reverse, K = 4 with n_limbs = 3: a 27-bit prime dropped beside the largest primes below 2^52 and 2^51; special prime 27-bit"""
+    small = primes_below(orc, 2, 1 << 27, n)
+    return primes_below(orc, 1, 1 << 52, n) + primes_below(orc, 1, 1 << 51, n) + small
+
+
+def rounding_edge_coeffs(n, q, which):
+    """n COEFFICIENT-domain words from {0, 1, half - 1, half, half + 1, half + 2, q - 2, q - 1}, half = q >> 1: as the INTT of a
+    rescale's dropped limb they put s = (x + half) mod q on every point where round(X / q) changes or wraps. Constant, alternating,
+    in runs of 8, or a walk through all eight values whose stride depends on `which`."""
+    half = q >> 1
+    vals = np.array([0, 1, half - 1, half, half + 1, half + 2, q - 2, q - 1], dtype=np.uint64)
+    j = np.arange(n)
+    kind, v = which % 4, which // 4
+    idx = [np.full(n, v), np.where(j & 1, v + 3, v), (j >> 3) + v, j * (2 * v + 1) + (j >> 5) * 3 + v][kind] % 8
+    return vals[idx]
+
+
+def extreme_ciphertext(case, b, components, limbs=None, salt=0):
+    """instance b of the [k][i][n] layout hexl_rescale and hexl_multiply_relinearize take, every word from extreme_words with the
+    pattern varied per (b, k, i); operands that meet in one call take salts that differ by a non-multiple of 9 (the pattern count)"""
+    limbs = case.L if limbs is None else limbs
+    return np.concatenate([extreme_words(case.n, int(case.moduli[i]), salt + b * 5 + k * 3 + i)
+                           for k in range(components) for i in range(limbs)])
+
+
+# The arithmetic tiers of the FP64 kernels as (environment of the child process, expression for the key moduli; "None" = the bench's
+# 51-bit primes): shared by test_gpu_keyswitch.py (every pipeline) and test_gpu_mulrelin.py (the fused multiply).
+TIERS = {
+    "skip_period3_51bit": ({}, "None"),
+    "noskip_forced_period3_51bit": ({"HEXL_KSX_SKIP": "0"}, "None"),
+    "skip_period3_ratio_1p24": ({}, "[orc.primes(1, 51, n)[0]] + primes_below(orc, K - 1, int(0.81 * 2**51), n)"),
+    "skip_period3_special_prime_smallest": ({}, "orc.primes(K - 1, 51, n) + primes_below(orc, 1, int(0.81 * 2**51), n)"),
+    "skip_period6_just_below_2^50": ({}, "primes_below(orc, K, 1 << 50, n)"),
+    "skip_period12_just_below_2^49": ({}, "primes_below(orc, K, 1 << 49, n)"),
+    "noskip_period6_mixed_50_to_40bit": ({}, "primes_below(orc, 2, 1 << 50, n) + orc.primes(K - 3, 40, n) + orc.primes(1, 45, n)"),
+    "noskip_period3_mixed_51_and_30bit": ({}, "orc.primes(2, 51, n)[:1] + orc.primes(K - 2, 30, n) + orc.primes(2, 51, n)[1:]"),
+    "strict_just_below_2^52": ({}, "primes_below(orc, K, 1 << 52, n)"),
+    # round 6: both sides of the lazy / strict boundary 2^51 (1 + 2^-7) (f64_arith.hpp LAZY_MAX_MODULUS)
+    "period3_tier_top_2^51_plus_2^44": ({}, "primes_below(orc, K, (1 << 51) + (1 << 44), n)"),
+    "strict_just_above_2^51_plus_2^44": ({}, "primes_from(orc, K, (1 << 51) + (1 << 44), n)"),
+    "strict_forced_51bit": ({"HEXL_KS_NOLAZY": "1"}, "None"),
+    # round 5: plans whose limbs differ in tier -- every transform takes the tier of ITS modulus (hexl_ks_plan::tier; the reference's NTT
+    # engines each run on their own modulus, device/keyswitch/ntt_core.hpp:285-291)
+    "mixed_seal_chain_strict_and_period12": ({}, "seal_chain(orc, K, n)"),
+    "mixed_seal_chain_plan_wide_tier": ({"HEXL_KS_PER_LIMB": "0"}, "seal_chain(orc, K, n)"),
+    "mixed_special_prime_strict_rest_period12": ({}, "orc.primes(K - 1, 47, n) + primes_below(orc, 1, 1 << 52, n)"),
+    "mixed_skip_period6_and_period3_around_2^50": ({}, "(primes_below(orc, K, 1 << 50, n) + orc.primes(K, 50, n))[K // 2:K // 2 + K]"),
+    "mixed_all_four_tiers": ({}, "tier_ladder(orc, K, n)"),
+}
+# the tiers the worst-case operand families (extreme_words) run in
+EXTREME_TIERS = ["skip_period3_51bit", "period3_tier_top_2^51_plus_2^44", "strict_just_above_2^51_plus_2^44", "skip_period6_just_below_2^50",
+                 "skip_period12_just_below_2^49", "strict_just_below_2^52", "mixed_seal_chain_strict_and_period12", "mixed_all_four_tiers"]
+
+
+def tier_moduli(orc, tier, n, K):
+    """the key moduli of TIERS[tier] in this process (None: KsCase's default primes)"""
+    return eval(TIERS[tier][1], {"orc": orc, "n": n, "K": K, "primes_below": primes_below, "primes_from": primes_from,
+                                 "seal_chain": seal_chain, "tier_ladder": tier_ladder})
+
+
 class RlweCase:
     """Real RLWE switching keys with special prime P = moduli[K-1]: key d, limb i holds (b, a) with
     b = -a*s_old + e + (i == d ? P : 0) * s_new in the NTT domain. check(res) asserts that

@@ -50,6 +50,16 @@ def trace(ref: Path, out: Path) -> int:
         env.update(RUN_CHOICE="1", FPGA_BITSTREAM_DIR="/nonexistent-bitstreams")
         base = tmp / "base_env.json"
         base.write_text(json.dumps(env))
+        # calibration: a stub started directly, without a script in between, reports what its own interpreters add to the environment
+        # (bash, python3: locale coercion, start-up hooks of the machine; such values may differ from process to process). Those names
+        # are no script's doing and are dropped from every recorded invocation, so the trace does not depend on where it is made.
+        cal = tmp / "calibration.jsonl"
+        subprocess.run([str(tmp / "test_fwd_ntt")], cwd=tmp, capture_output=True, text=True, timeout=120,
+                       env=dict(env, HEXL_TRACE_FILE=str(cal), HEXL_TRACE_BASE_ENV=str(base), HEXL_TRACE_SCRIPT=""))
+        noise = set()
+        if cal.exists():
+            for l in cal.read_text().splitlines():
+                noise |= set(json.loads(l)["env"])
         for s in scripts:
             tf = tmp / "trace.jsonl"
             if tf.exists():
@@ -64,6 +74,8 @@ def trace(ref: Path, out: Path) -> int:
             if not got:
                 print(f"{rel} called none of the known binaries", file=sys.stderr)
                 return 1
+            for e in got:
+                e["env"] = {k: v for k, v in e["env"].items() if k not in noise}
             entries += got
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps({"run_with": {"RUN_CHOICE": "1", "FPGA_BITSTREAM_DIR": "/nonexistent-bitstreams"},

@@ -5,8 +5,8 @@ import ctypes
 import numpy as np
 import pytest
 
-from ckks_model import Limbs, apply_galois, automorphism_coeff, rescale_crt, rescale_poly
-from ks_util import seal_chain
+from ckks_model import Limbs, apply_galois, automorphism_coeff, rescale_crt, rescale_input, rescale_poly
+from ks_util import big_dropped, primes_below, seal_chain, small_dropped, tier_ladder
 
 HEXL_E_BADARG = -1
 
@@ -53,6 +53,29 @@ def test_rescale_formula_at_the_ends_of_the_range(orc):
     for fill in (0, 1, -1):
         c = np.stack([np.full(n, fill % q, dtype=np.uint64) for q in qs])
         assert np.array_equal(rescale_poly(lm, c, 4), rescale_crt(lm, c, 4)), fill
+
+
+EDGE_CHAINS = {"seal": lambda orc, n: seal_chain(orc, 7, n), "ladder": lambda orc, n: tier_ladder(orc, 8, n),
+               "strict": lambda orc, n: primes_below(orc, 5, 1 << 52, n), "period6": lambda orc, n: primes_below(orc, 5, 1 << 50, n),
+               "period12": lambda orc, n: primes_below(orc, 5, 1 << 49, n), "big_dropped": big_dropped, "small_dropped": small_dropped}
+
+
+@pytest.mark.parametrize("kind", list(EDGE_CHAINS))
+def test_rescale_formula_on_rounding_edges_and_extreme_words(orc, kind):
+    """the model the GPU tests compare with equals big-integer CRT rounding on the very inputs they use: the dropped limb's INTT at 0, 1,
+    half - 1 ... half + 2, q_l - 2, q_l - 1 beside extreme kept limbs ("edge"), and every limb extreme in NTT form ("extreme"), for
+    every n_limbs the chain admits (2 ... K - 1), three instances (= patterns) each"""
+    n = 1024
+    qs = EDGE_CHAINS[kind](orc, n)
+    lm = Limbs(orc, n, qs)
+    for n_limbs in range(2, len(qs)):
+        for family in ("edge", "extreme"):
+            for b in range(3):
+                c = rescale_input(lm, n_limbs, 1, family, b, seed=n_limbs)[0]
+                if family == "edge":                              # the dropped limb's coefficients are the edge words themselves
+                    half, ql = qs[n_limbs - 1] >> 1, qs[n_limbs - 1]
+                    assert set(int(v) for v in lm.intt(c[n_limbs - 1], n_limbs - 1)) <= {0, 1, half - 1, half, half + 1, half + 2, ql - 2, ql - 1}
+                assert np.array_equal(rescale_poly(lm, c, n_limbs), rescale_crt(lm, c, n_limbs)), (n_limbs, family, b)
 
 
 def test_new_entry_points_refuse_a_null_handle(hx):

@@ -5,19 +5,30 @@ import numpy as np
 import pytest
 
 from ckks_model import Limbs, rescale, rotate
-from ks_util import KsCase, seal_chain
+from ks_util import KsCase, extreme_ciphertext, seal_chain
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("n,nb", [(16384, 5), (4096, 70)])
 def test_multiply_rescale_rotate(hx, ctx, dev, orc, n, nb):
+    run_level(hx, ctx, dev, orc, n, nb, extreme=False)
+
+
+def test_multiply_rescale_rotate_extreme_operands(hx, ctx, dev, orc):
+    """the same level with every word of both operands and of both key sets at q - 1, beside q / 2, 0 or 1 (ks_util.extreme_words): the
+    rescale then takes what the fused multiply made of them, the rotate what the rescale did"""
+    run_level(hx, ctx, dev, orc, 4096, 5, extreme=True)
+
+
+def run_level(hx, ctx, dev, orc, n, nb, extreme):
     import torch
     K = 7
     L = K - 1
     qs = seal_chain(orc, K, n)
-    relin = KsCase(orc, n, L, K, seed=21, moduli=qs)                       # level L: data limbs q_0 ... q_5, special q_6
-    galois = KsCase(orc, n, L - 1, K - 1, seed=22, moduli=qs[:L - 1] + qs[K - 1:])   # after the rescale: q_0 ... q_4, special q_6
+    # level L: data limbs q_0 ... q_5, special q_6; after the rescale: q_0 ... q_4, special q_6
+    relin = KsCase(orc, n, L, K, seed=21, moduli=qs, extreme_keys=extreme)
+    galois = KsCase(orc, n, L - 1, K - 1, seed=22, moduli=qs[:L - 1] + qs[K - 1:], extreme_keys=extreme)
     p1 = hx.KeySwitchPlan(ctx, n, L, K, K, 2, relin.moduli, relin.modswitch)
     p1.set_keys(relin.keys)
     p2 = hx.KeySwitchPlan(ctx, n, L - 1, K - 1, K - 1, 2, galois.moduli, galois.modswitch)
@@ -26,6 +37,8 @@ def test_multiply_rescale_rotate(hx, ctx, dev, orc, n, nb):
     g = pow(5, 11, 2 * n)
 
     def operand(b, which):
+        if extreme:
+            return extreme_ciphertext(relin, b, 2, salt=4 * which)
         return np.concatenate([orc.splitmix(n, 500 + b * 131 + which * 17 + k * 5 + i, qs[i]) for k in range(2) for i in range(L)])
 
     distinct = 2

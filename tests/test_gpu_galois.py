@@ -3,7 +3,7 @@ test_ckks_ops_model.py) and hexl_rotate against (perm(c0), 0) + orc.keyswitch(pe
 import numpy as np
 import pytest
 
-from ckks_model import apply_galois, automorphism_coeff, rotate
+from ckks_model import apply_galois, automorphism_coeff, first_mismatch, rotate
 from ks_util import KsCase, RlweCase, primes_below, seal_chain, tier_ladder
 
 pytestmark = pytest.mark.gpu
@@ -70,18 +70,94 @@ def test_rotate_vs_oracle(hx, ctx, dev, orc, n, L, K, nb, kind):
     if kind == "int":
         assert plan.tiers()[0][0] == -1
     plan.set_keys(case.keys)
-    distinct = min(nb, 3)
-    cts = [ct_of(orc, case, b) for b in range(distinct)]
-    d_ct = hx.as_i64(np.concatenate([cts[b % distinct] for b in range(nb)])).to(dev)
-    import torch
-    d_out = torch.full((nb * 2 * L * n,), -1, dtype=torch.int64, device=dev)   # written, not accumulated into
     g = pow(5, 3, 2 * n)
+    check_rotate(hx, ctx, dev, orc, case, plan, nb, g, min(nb, 3))
+    plan.close()
+
+
+def rotate_buffers(hx, dev, cts, nb):
+    """device input of nb instances (the distinct ones in `cts`, repeated) and an output filled with -1 (written, not accumulated into)"""
+    import torch
+    d_ct = hx.as_i64(np.concatenate([cts[b % len(cts)] for b in range(nb)])).to(dev)
+    return torch.full((nb * len(cts[0]),), -1, dtype=torch.int64, device=dev), d_ct
+
+
+def assert_rotated(hx, orc, case, d_out, cts, nb, g, label=""):
+    out = hx.to_u64(d_out).reshape(nb, -1)
+    want = [rotate(orc, case, ct, g) for ct in cts]
+    for b in range(nb):
+        if not np.array_equal(out[b], want[b % len(cts)]):
+            where = first_mismatch(out[b], want[b % len(cts)], ("component", "limb", "coefficient"), (2, case.L, case.n))
+            raise AssertionError(f"{label}instance {b} of {nb}, {where}")
+
+
+def check_rotate(hx, ctx, dev, orc, case, plan, nb, g, distinct):
+    cts = [ct_of(orc, case, b) for b in range(distinct)]
+    d_out, d_ct = rotate_buffers(hx, dev, cts, nb)
     plan.rotate(d_out, d_ct, nb, g)
     ctx.sync()
-    out = hx.to_u64(d_out).reshape(nb, -1)
-    want = [rotate(orc, case, cts[b], g) for b in range(distinct)]
-    for b in range(nb):
-        assert np.array_equal(out[b], want[b % distinct]), f"instance {b}"
+    assert_rotated(hx, orc, case, d_out, cts, nb, g)
+
+
+def slice_of(plan):
+    """instances per slice of hexl_rotate = per scratch chunk of the keyswitch, read off hexl_ks_scratch_bytes (bytes grow with the batch
+    up to one chunk, DESIGN section 3: 256 at N = 16384, the same number of coefficients at the other ring dimensions)"""
+    chunk = plan.scratch_bytes(1 << 24) // plan.scratch_bytes(1)
+    assert chunk >= 2 and plan.scratch_bytes(chunk) == plan.scratch_bytes(chunk + 1) > plan.scratch_bytes(chunk - 1)
+    return chunk
+
+
+@pytest.mark.parametrize("which", ["identity", "conjugation", "5^3"])
+@pytest.mark.parametrize("n", [4096, 32768])
+def test_rotate_at_the_ends_of_the_galois_group(hx, ctx, dev, orc, n, which):
+    """g = 1 and g = 2n - 1 through the rotate's own branch of k_galois (component 1 gathered into the plan's t buffer, zeros into the
+    output), on the LDS gather (n <= 16384) and on the global one (n = 32768)"""
+    g = {"identity": 1, "conjugation": 2 * n - 1, "5^3": pow(5, 3, 2 * n)}[which]
+    L, K = 2, 3
+    case = KsCase(orc, n, L, K, seed=71)
+    plan = hx.KeySwitchPlan(ctx, n, L, K, K, 2, case.moduli, case.modswitch)
+    plan.set_keys(case.keys)
+    check_rotate(hx, ctx, dev, orc, case, plan, 3, g, 3)
+    plan.close()
+
+
+@pytest.mark.parametrize("kernels", ["fp64", "integer"])
+def test_rotate_two_full_slices(hx, ctx, dev, orc, kernels):
+    """2 x slice + 1 instances: the second slice's gather overwrites EVERY row of the t buffer the first slice's keyswitch reads. The
+    distinct instances do not divide the slice, so row r of the second slice differs from row r of the first: a gather that ran before
+    the keyswitch had read t would change the first slice's result. An FP64 plan runs a slice on the caller's stream alone; a plan on
+    the integer kernels (moduli above 2^52) splits it over two lanes, and hx_launch_rotate then relies on hx_launch_keyswitch having
+    joined them back into the stream."""
+    n, L, K = 4096, 2, 3
+    case = KsCase(orc, n, L, K, seed=72, bits=55 if kernels == "integer" else 51)
+    plan = hx.KeySwitchPlan(ctx, n, L, K, K, 2, case.moduli, case.modswitch)
+    assert (plan.tiers()[0][0] == -1) == (kernels == "integer")
+    plan.set_keys(case.keys)
+    chunk = slice_of(plan)
+    distinct = 3 if chunk % 3 else 5
+    assert chunk % distinct
+    check_rotate(hx, ctx, dev, orc, case, plan, 2 * chunk + 1, pow(5, 3, 2 * n), distinct)
+    plan.close()
+
+
+def test_rotate_one_plan_growing_batch(hx, ctx, dev, orc):
+    """one instance, then more than a slice, then three, on one plan and with nothing but stream order between the calls: the plan's t
+    buffer is replaced (grow-only) while the first call is queued, and the third call runs in the larger one"""
+    n, L, K = 4096, 1, 2
+    case = KsCase(orc, n, L, K, seed=73)
+    plan = hx.KeySwitchPlan(ctx, n, L, K, K, 2, case.moduli, case.modswitch)
+    plan.set_keys(case.keys)
+    chunk = slice_of(plan)
+    cts = [ct_of(orc, case, b) for b in range(3)]
+    g = pow(5, 5, 2 * n)
+    calls = [(1, cts[2:]), (chunk + 2, cts), (3, cts[::-1])]
+    bufs = [rotate_buffers(hx, dev, c, nb) for nb, c in calls]    # every upload first: a copy from host memory waits for the stream
+    ctx.sync()
+    for (nb, _), (d_out, d_ct) in zip(calls, bufs):
+        plan.rotate(d_out, d_ct, nb, g)
+    ctx.sync()
+    for (nb, c), (d_out, _) in zip(calls, bufs):
+        assert_rotated(hx, orc, case, d_out, c, nb, g, label=f"call with {nb}: ")
     plan.close()
 
 

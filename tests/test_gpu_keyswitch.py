@@ -4,7 +4,7 @@ tests/test_keyswitch.cpp:148-191 (vectors 16384_6_7_7_2 / 8192_.., one worksize 
 import numpy as np
 import pytest
 
-from ks_util import KsCase, primes_below, seal_chain, tier_ladder
+from ks_util import EXTREME_TIERS, TIERS, KsCase, primes_below, seal_chain, tier_ladder
 
 pytestmark = pytest.mark.gpu
 from pathlib import Path  # noqa: E402
@@ -442,28 +442,7 @@ def test_bd_major_pipeline_on_small_rings(n, nb):
 # lazy kernels -- SKIP (moduli within a factor 1.25 of each other: c_d and s' enter the transforms without a range reduction, on the
 # shifted schedule) and non-SKIP (HEXL_KSX_SKIP=0, or moduli of different sizes) -- plus the strict kernels. Rounds 1-3 covered the
 # tiers below 2^51 with two instances only, i.e. on the (b, d)-major kernels.
-TIERS = {
-    "skip_period3_51bit": ({}, "None"),
-    "noskip_forced_period3_51bit": ({"HEXL_KSX_SKIP": "0"}, "None"),
-    "skip_period3_ratio_1p24": ({}, "[orc.primes(1, 51, n)[0]] + primes_below(orc, K - 1, int(0.81 * 2**51), n)"),
-    "skip_period3_special_prime_smallest": ({}, "orc.primes(K - 1, 51, n) + primes_below(orc, 1, int(0.81 * 2**51), n)"),
-    "skip_period6_just_below_2^50": ({}, "primes_below(orc, K, 1 << 50, n)"),
-    "skip_period12_just_below_2^49": ({}, "primes_below(orc, K, 1 << 49, n)"),
-    "noskip_period6_mixed_50_to_40bit": ({}, "primes_below(orc, 2, 1 << 50, n) + orc.primes(K - 3, 40, n) + orc.primes(1, 45, n)"),
-    "noskip_period3_mixed_51_and_30bit": ({}, "orc.primes(2, 51, n)[:1] + orc.primes(K - 2, 30, n) + orc.primes(2, 51, n)[1:]"),
-    "strict_just_below_2^52": ({}, "primes_below(orc, K, 1 << 52, n)"),
-    # round 6: both sides of the lazy / strict boundary 2^51 (1 + 2^-7) (f64_arith.hpp LAZY_MAX_MODULUS)
-    "period3_tier_top_2^51_plus_2^44": ({}, "primes_below(orc, K, (1 << 51) + (1 << 44), n)"),
-    "strict_just_above_2^51_plus_2^44": ({}, "primes_from(orc, K, (1 << 51) + (1 << 44), n)"),
-    "strict_forced_51bit": ({"HEXL_KS_NOLAZY": "1"}, "None"),
-    # round 5: plans whose limbs differ in tier -- every transform takes the tier of ITS modulus (hexl_ks_plan::tier; the reference's NTT
-    # engines each run on their own modulus, device/keyswitch/ntt_core.hpp:285-291)
-    "mixed_seal_chain_strict_and_period12": ({}, "seal_chain(orc, K, n)"),
-    "mixed_seal_chain_plan_wide_tier": ({"HEXL_KS_PER_LIMB": "0"}, "seal_chain(orc, K, n)"),
-    "mixed_special_prime_strict_rest_period12": ({}, "orc.primes(K - 1, 47, n) + primes_below(orc, 1, 1 << 52, n)"),
-    "mixed_skip_period6_and_period3_around_2^50": ({}, "(primes_below(orc, K, 1 << 50, n) + orc.primes(K, 50, n))[K // 2:K // 2 + K]"),
-    "mixed_all_four_tiers": ({}, "tier_ladder(orc, K, n)"),
-}
+# (the table itself is in ks_util.py: test_gpu_mulrelin.py runs the fused multiply over the same tiers)
 # what plan.tiers() must report for the first K = 4 limbs of the round-5 entries at n = 16384 (test_per_limb_tiers_reported)
 MIXED_TIERS_K4 = {
     "mixed_seal_chain_strict_and_period12": ([0, 12, 12, 12], True),
@@ -484,10 +463,6 @@ def test_slot_major_kernels_in_every_tier(tier, n, L, K, nb):
 # Round 6: the X / I reduction schedules leave sums un-reduced wherever the worst-case bound chain allows it. Uniform inputs stay far
 # from those bounds; these do not try to reach them (no input does on all 14 stages) but start every chain at its largest magnitudes:
 # every word of the keys, t_target and result at q - 1, beside q / 2, 0 or 1, constant / alternating / in runs (ks_util.extreme_words)
-EXTREME_TIERS = ["skip_period3_51bit", "period3_tier_top_2^51_plus_2^44", "strict_just_above_2^51_plus_2^44", "skip_period6_just_below_2^50",
-                 "skip_period12_just_below_2^49", "strict_just_below_2^52", "mixed_seal_chain_strict_and_period12", "mixed_all_four_tiers"]
-
-
 @pytest.mark.parametrize("tier", EXTREME_TIERS)
 @pytest.mark.parametrize("n,L,K,nb,env", [(16384, 3, 4, 300, {"HEXL_KS_PIPE": "3"}), (16384, 3, 4, 9, {"HEXL_KS_LAT": "0"}),
                                           (16384, 3, 4, 3, {"HEXL_KS_LAT": "2"}), (32768, 3, 4, 90, {})])
