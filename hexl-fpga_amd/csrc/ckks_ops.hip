@@ -155,12 +155,7 @@ static int launch_galois(hexl_ctx* c, hipStream_t st, const GaloisArgs& a) {
     const u32 n = 1u << a.logn;
     const u32 grid = a.count < 65536 ? (u32)a.count : 65536u;
     if (a.logn <= 14) {
-        static PerDeviceOnce once;
-        if (int rc = once.run(c->device, [] {
-                HX_CHECK(hipFuncSetAttribute((const void*)k_galois<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8));
-                return 0;
-            }))
-            return rc;
+        if (int rc = hx_lds_optin<k_galois<true>>(c->device, 16384 * 8)) return rc;
         hipLaunchKernelGGL(k_galois<true>, dim3(grid), dim3(n >= 2048 ? 1024 : 512), size_t(n) * 8, st, a);
     } else {
         hipLaunchKernelGGL(k_galois<false>, dim3(grid), dim3(1024), 0, st, a);
@@ -177,54 +172,11 @@ int hx_launch_galois(hexl_ctx* c, u64* d_out, const u64* d_in, size_t count, u32
 template <int LOGN, int LOGE, int LAZY>
 static int run_rescale(hexl_ks_plan* p, const RsArgs& a, u32 nb, u32 ncomp) {
     using G = Geom<LOGN, LOGE>;
-    static PerDeviceOnce once;
-    if (int rc0 = once.run(p->ctx->device, [] {
-            HX_CHECK(hipFuncSetAttribute((const void*)k_rs_intt<LOGN, LOGE, LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_USED));
-            HX_CHECK(hipFuncSetAttribute((const void*)k_rs_down<LOGN, LOGE, LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_USED));
-            return 0;
-        }))
-        return rc0;
+    if (int rc = hx_lds_optin<k_rs_intt<LOGN, LOGE, LAZY>, k_rs_down<LOGN, LOGE, LAZY>>(p->ctx->device, G::LDS_USED)) return rc;
     hipStream_t st = p->ctx->stream;
     hipLaunchKernelGGL((k_rs_intt<LOGN, LOGE, LAZY>), dim3(nb * ncomp), dim3(G::T), G::LDS_USED, st, a);
     hipLaunchKernelGGL((k_rs_down<LOGN, LOGE, LAZY>), dim3(nb * ncomp * a.l), dim3(G::T), G::LDS_USED, st, a);
     return (int)hipGetLastError();
-}
-
-// the (LOGN, LOGE) and tier instantiations of run_chunk_f64 (keyswitch_f64.hip): LAZY = -1 when the limbs of the level differ in tier
-static int dispatch_rescale(hexl_ks_plan* p, const RsArgs& a, u32 nb, u32 ncomp, int lazy) {
-    if (lazy < 0) {
-        switch (p->logn) {
-            case 10: return run_rescale<10, 4, -1>(p, a, nb, ncomp);
-            case 11: return run_rescale<11, 5, -1>(p, a, nb, ncomp);
-            case 12: return run_rescale<12, 5, -1>(p, a, nb, ncomp);
-            case 13: return run_rescale<13, 5, -1>(p, a, nb, ncomp);
-            case 14: return run_rescale<14, 4, -1>(p, a, nb, ncomp);
-            case 15: return run_rescale<15, 5, -1>(p, a, nb, ncomp);
-            default: return HEXL_E_BADARG;
-        }
-    }
-    if (lazy > 0) {
-        switch (p->logn) {
-            case 10: return run_rescale<10, 4, 3>(p, a, nb, ncomp);
-            case 11: return run_rescale<11, 5, 3>(p, a, nb, ncomp);
-            case 12: return run_rescale<12, 5, 3>(p, a, nb, ncomp);
-            case 13: return run_rescale<13, 5, 3>(p, a, nb, ncomp);
-            case 15: return run_rescale<15, 5, 3>(p, a, nb, ncomp);
-            case 14: return lazy == 12 ? run_rescale<14, 4, 12>(p, a, nb, ncomp)
-                          : lazy == 6 ? run_rescale<14, 4, 6>(p, a, nb, ncomp)
-                                      : run_rescale<14, 4, 3>(p, a, nb, ncomp);
-            default: return HEXL_E_BADARG;
-        }
-    }
-    switch (p->logn) {
-        case 10: return run_rescale<10, 4, 0>(p, a, nb, ncomp);
-        case 11: return run_rescale<11, 5, 0>(p, a, nb, ncomp);
-        case 12: return run_rescale<12, 5, 0>(p, a, nb, ncomp);
-        case 13: return run_rescale<13, 5, 0>(p, a, nb, ncomp);
-        case 14: return run_rescale<14, 4, 0>(p, a, nb, ncomp);
-        case 15: return run_rescale<15, 5, 0>(p, a, nb, ncomp);
-        default: return HEXL_E_BADARG;
-    }
 }
 
 // per-level constants, computed on the host at the first rescale that drops limb l and kept in the plan
@@ -241,7 +193,7 @@ static int rescale_constants(hexl_ks_plan* p, u32 l) {
         const double pd = (double)q;
         const u64 inv = hxnt::invmod(ql % q, q);
         rm[i].fix = (double)(q - half % q);                       // in [1, q]
-        rm[i].qlinv = inv > q / 2 ? (double)inv - pd : (double)inv;
+        rm[i].qlinv = hx_centre(inv, q);
         rm[i].qlinv_p = rm[i].qlinv / pd;
         rm[i].half = (double)half;
     }
@@ -255,14 +207,9 @@ int hx_launch_rescale(hexl_ks_plan* p, u64* d_out, const u64* d_in, size_t batch
     if (int rc = rescale_constants(p, l)) return rc;
     if (!batch) return 0;
     const size_t n = p->n;
-    const size_t chunk = batch < hx_ks_chunk(p) ? batch : hx_ks_chunk(p);
-    const size_t need = chunk * ncomp;                           // polynomials of s per chunk
-    if (p->rs_cap < need) {                                      // grow-only; earlier launches may still read the old one
-        if (p->d_rs_s) { HX_CHECK(hipDeviceSynchronize()); HX_CHECK(hipFree(p->d_rs_s)); }
-        p->d_rs_s = nullptr; p->rs_cap = 0;
-        HX_CHECK(hipMalloc((void**)&p->d_rs_s, need * n * sizeof(double)));
-        p->rs_cap = need;
-    }
+    const size_t chunk = hx_ks_chunk_of(p, batch);
+    // s: one polynomial per (instance, component) of a chunk
+    if (int rc = hx_grow_device((void**)&p->d_rs_s, &p->rs_cap, chunk * ncomp, n * sizeof(double), nullptr)) return rc;
     // the schedule every limb of the level admits; LAZY = -1 (per-limb lookup) when they differ
     int lazy = p->tier[0];
     for (u32 i = 1; i <= l; ++i)
@@ -273,13 +220,13 @@ int hx_launch_rescale(hexl_ks_plan* p, u64* d_out, const u64* d_in, size_t batch
     a.s = p->d_rs_s;
     a.half = (double)(p->moduli[l] >> 1);
     a.l = l;
-    a.tiermap = 0;
-    for (u32 i = 0; i < p->K; ++i) a.tiermap |= (unsigned long long)(p->tier[i] & 15u) << (4 * i);
+    a.tiermap = hx_tiermap(p);
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const size_t nb = batch - b0 < chunk ? batch - b0 : chunk;
         a.in = d_in + b0 * ncomp * n_limbs * n;
         a.out = d_out + b0 * ncomp * l * n;
-        if (int rc = dispatch_rescale(p, a, (u32)nb, ncomp, lazy)) return rc;
+        // (the (LOGN, LOGE) and tier instantiations of run_chunk_f64, keyswitch_f64.hip)
+        if (int rc = hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return run_rescale<N, E, Z>(p, a, (u32)nb, ncomp); })) return rc;
     }
     return 0;
 }
@@ -289,13 +236,8 @@ int hx_launch_rotate(hexl_ks_plan* p, u64* d_out, const u64* d_ct, size_t batch,
     if (!batch) return 0;
     if (!p->have_keys) return HEXL_E_NOKEYS;
     const size_t n = p->n, L = p->L;
-    const size_t slice = batch < hx_ks_chunk(p) ? batch : hx_ks_chunk(p);
-    if (p->rot_cap < slice) {                                    // grow-only; earlier launches may still read the old one
-        if (p->d_rot_t) { HX_CHECK(hipDeviceSynchronize()); HX_CHECK(hipFree(p->d_rot_t)); }
-        p->d_rot_t = nullptr; p->rot_cap = 0;
-        HX_CHECK(hipMalloc((void**)&p->d_rot_t, slice * L * n * sizeof(u64)));
-        p->rot_cap = slice;
-    }
+    const size_t slice = hx_ks_chunk_of(p, batch);
+    if (int rc = hx_grow_device((void**)&p->d_rot_t, &p->rot_cap, slice, L * n * sizeof(u64), nullptr)) return rc;
     for (size_t b0 = 0; b0 < batch; b0 += slice) {
         const size_t nb = batch - b0 < slice ? batch - b0 : slice;
         u64* out = d_out + b0 * 2 * L * n;
@@ -308,8 +250,8 @@ int hx_launch_rotate(hexl_ks_plan* p, u64* d_out, const u64* d_ct, size_t batch,
     return 0;
 }
 
-// ---- entry points of include/hexl_mi355x.h. They live here rather than in capi.hip, whose host half the CPU staging model
-// (tests/cpp) compiles against stubs of the launchers it calls. ----
+// ---- entry points of include/hexl_mi355x.h. They live here rather than in capi.hip: the CPU staging model (tests/cpp) compiles
+// capi.hip and host_staging.hip against stubs of the launchers those two call, and needs none for these. ----
 static bool ring_dimension_ok(u64 n) { return n >= 1024 && n <= 32768 && !(n & (n - 1)); }
 // [a, a + abytes) and [b, b + bbytes) share a byte
 static bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {

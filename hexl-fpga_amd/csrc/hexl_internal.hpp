@@ -1,10 +1,13 @@
 // hexl_internal.hpp -- host-side state shared by the launcher translation units.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/hexl_mi355x.h"
@@ -24,22 +27,38 @@ typedef unsigned __int128 u128;
         }                                                                                    \
     } while (0)
 
-// hipFuncSetAttribute (the > 64 KiB dynamic-LDS opt-in) applies to the CURRENT device's copy of a kernel, and the
-// launchers may run on one host thread per device (NUM_DEV > 1): one of these per call site runs its initialiser
-// once per device, serialised.
-struct PerDeviceOnce {
-    std::mutex m;
-    uint64_t done = 0;
-    template <class F>
-    int run(int device, F init) {
-        std::lock_guard<std::mutex> g(m);
-        const uint64_t bit = 1ull << (device & 63);
-        if (done & bit) return 0;
-        const int rc = init();
-        if (!rc) done |= bit;
-        return rc;
-    }
-};
+// The > 64 KiB dynamic-LDS opt-in of a set of kernels, the first time their launcher runs on a device: hipFuncSetAttribute applies
+// to the CURRENT device's copy of a kernel, and the launchers may run on one host thread per device (NUM_DEV > 1), so every set of
+// kernels (= every instantiation of this function) keeps its own per-device "done" bits behind a mutex.
+template <auto... Kernels>
+int hx_lds_optin(int device, size_t bytes) {
+    static std::mutex m;
+    static uint64_t done = 0;
+    std::lock_guard<std::mutex> g(m);
+    const uint64_t bit = 1ull << (device & 63);
+    if (done & bit) return 0;
+    for (const void* k : {(const void*)Kernels...})
+        HX_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    done |= bit;
+    return 0;
+}
+
+// ---- environment knobs: one parser; a knob read in more than one place has one accessor here. A `static` in an
+// accessor = read once per process; the others are read by every call (of hexl_ks_plan_create, of a launcher).
+constexpr long HX_KNOB_UNSET = LONG_MIN;
+inline long hx_knob(const char* name, long dflt) {
+    const char* e = getenv(name);
+    return e ? atol(e) : dflt;
+}
+// HEXL_KS_PER_LIMB: 0 = the plan-wide tier for every limb (read per plan); 2 = the (b, d)-major and the latency kernels look the tier
+// up per transform for every batch (tests; read once per process)
+inline int hx_knob_ks_per_limb() { return (int)hx_knob("HEXL_KS_PER_LIMB", 1); }
+// HEXL_KS_LAT: 0 = no lone-keyswitch path, 1 = the three-kernel path of keyswitch_f64.hip for every batch of that pipeline, 2 = the
+// quarter-transform path of keyswitch_lat.hip for every batch that fits a scratch chunk (tests)
+inline int hx_knob_ks_lat() { static const int v = (int)hx_knob("HEXL_KS_LAT", -1); return v; }
+// HEXL_KS_PIPE: 1 = FP64 plans keep the (b, d)-major pipeline and integer plans run the first-generation kernels, 3 = the slot-major
+// pipeline for every batch (tests, comparisons)
+inline int hx_knob_ks_pipe() { static const int v = (int)hx_knob("HEXL_KS_PIPE", 2); return v; }
 
 struct hexl_ctx {
     int device = 0;
@@ -50,9 +69,9 @@ struct hexl_ctx {
     void* d_stage = nullptr;  size_t d_stage_bytes = 0;
     void* d_shared = nullptr; size_t d_shared_bytes = 0;   // small shared arrays of device-resident callers
     void* h_stage = nullptr;  size_t h_stage_bytes = 0;
-    void* h_lone = nullptr;   size_t h_lone_bytes = 0;    // COHERENT pinned slabs of the zero-copy lone keyswitch (capi.hip keyswitch_host_lone)
+    void* h_lone = nullptr;   size_t h_lone_bytes = 0;    // COHERENT pinned slabs of the zero-copy lone keyswitch (host_staging.hip keyswitch_host_lone)
     uint32_t lone_epoch = 0;                                // zero-copy lone keyswitches so far (their completion words carry it)
-    // host-pointer pipeline: copy streams + events (created lazily), see run_pipeline() in capi.hip
+    // host-pointer pipeline: copy streams + events (created lazily), see run_pipeline() in host_staging.hip
     hipStream_t s_up = nullptr, s_down = nullptr;
     hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_down[2] = {nullptr, nullptr};
     void* d_meta = nullptr;   size_t d_meta_bytes = 0;     // dyadic per-(item,modulus) constants
@@ -66,8 +85,15 @@ struct hexl_ctx {
     char name[256] = {0};
 };
 
-int hx_reserve_device(hexl_ctx* ctx, void** p, size_t* cur, size_t need);
+// grow-only device buffer of *cap units of `unit` bytes. Before the old buffer is released everything that may still read it has to
+// finish: the context's stream for a context's buffers (ctx given), the whole device for a plan's (ctx == nullptr: lanes on the
+// plan's auxiliary streams use them)
+int hx_grow_device(void** p, size_t* cap, size_t need, size_t unit, hexl_ctx* ctx);
+inline int hx_reserve_device(hexl_ctx* ctx, void** p, size_t* cur, size_t need) { return hx_grow_device(p, cur, need, 1, ctx); }
 int hx_reserve_pinned(hexl_ctx* ctx, void** p, size_t* cur, size_t need, bool coherent = false);
+void hx_pin_own_thread();    // a host thread of the library (copy pool, unpack lane) asks for the NUMA node of the devices in use (capi.hip)
+// ring dimensions: 1024..16384 as the reference (keyswitch) / 16384 (NTT); 32768 is beyond its envelope
+inline bool hx_supported_ntt_n(u64 n) { return n == 1024 || n == 2048 || n == 4096 || n == 8192 || n == 16384 || n == 32768; }
 
 // per-modulus constants of a keyswitch plan (device copy is an array of K of these)
 struct KsModulus {
@@ -141,7 +167,7 @@ struct hexl_ks_plan {
     bool x_skip = false;              // slot-major lazy kernels: moduli within LAZY_SKIP_MAX_RATIO of each other -> c_d and s' enter the
                                       // transforms without a range reduction (keyswitch_x.hip SKIP variants; HEXL_KSX_SKIP=0 turns it off)
     bool overwrite_result = false;    // host-pointer path, (b, d)-major FP64 kernels: write `result` instead of accumulating into it
-    // zero-copy lone keyswitch of the host-pointer entry point (capi.hip keyswitch_host_lone; set around ONE launch, else null):
+    // zero-copy lone keyswitch of the host-pointer entry point (host_staging.hip keyswitch_host_lone; set around ONE launch, else null):
     // per-quarter-limb completion words and the range flag in pinned host memory (keyswitch_lat.hip KsArgsQ)
     u32* host_done = nullptr;
     u32* host_flag = nullptr;
@@ -188,4 +214,41 @@ u32 hx_ks_x_loge();
 u32 hx_idxB(u32 logn, u32 r, u32 tid);
 u32 hx_loge_for(u32 logn);
 
+
 static inline u64 hx_shoup(u64 y, u64 q) { return (u64)(((u128)(y % q) << 64) / q); }
+// residue v < q as the centred double in (-q/2, q/2] the FP64 kernels work on
+static inline double hx_centre(u64 v, u64 q) { return v > q / 2 ? (double)v - (double)q : (double)v; }
+// nibble i = forward reduction period of limb i (the kernels built with LAZY = -1 look their schedule up here)
+static inline unsigned long long hx_tiermap(const hexl_ks_plan* p) {
+    unsigned long long m = 0;
+    for (u32 i = 0; i < p->K; ++i) m |= (unsigned long long)(p->tier[i] & 15u) << (4 * i);
+    return m;
+}
+// instances of a batch that go into one scratch chunk
+static inline size_t hx_ks_chunk_of(const hexl_ks_plan* p, size_t batch) { return batch < hx_ks_chunk(p) ? batch : hx_ks_chunk(p); }
+
+// The <LOGN, LOGE, LAZY> instantiations of the FP64 (b, d)-major kernels and of the kernels built on their geometry (rescale):
+// f(<LOGN>, <LOGE>, <LAZY>) for ring dimension 2^logn and forward reduction period `lazy` (f64_arith.hpp: 0 = strict, < 0 = looked up
+// per limb). N = 16384 has the periods 3 / 6 / 12, the other rings keep 3 (a shorter period is always valid: fewer kernel variants).
+template <int V> using hx_int = std::integral_constant<int, V>;
+template <class F>
+static int hx_with_f64_geom(u32 logn, int lazy, F f) {
+    auto tiers = [&](auto N, auto E) {
+        if (lazy < 0) return f(N, E, hx_int<-1>{});
+        if (lazy == 0) return f(N, E, hx_int<0>{});
+        if constexpr (decltype(N)::value == 14) {
+            if (lazy == 12) return f(N, E, hx_int<12>{});
+            if (lazy == 6) return f(N, E, hx_int<6>{});
+        }
+        return f(N, E, hx_int<3>{});
+    };
+    switch (logn) {
+        case 10: return tiers(hx_int<10>{}, hx_int<4>{});
+        case 11: return tiers(hx_int<11>{}, hx_int<5>{});
+        case 12: return tiers(hx_int<12>{}, hx_int<5>{});
+        case 13: return tiers(hx_int<13>{}, hx_int<5>{});
+        case 14: return tiers(hx_int<14>{}, hx_int<4>{});
+        case 15: return tiers(hx_int<15>{}, hx_int<5>{});      // beyond the reference: N = 32768
+        default: return (int)HEXL_E_BADARG;
+    }
+}

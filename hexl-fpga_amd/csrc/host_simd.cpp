@@ -68,7 +68,7 @@ void hx_add_mod_u64_at_level(uint64_t* r, const uint64_t* o, size_t n, uint64_t 
     add_mod_portable(r, o, n, q);
 }
 
-// ---- NUMA placement of the library's OWN host threads (the copy pool and the unpack lane of capi.hip) ---------------------------------
+// ---- NUMA placement of the library's OWN host threads (the copy pool and the unpack lane of host_staging.hip) ---------------------------------
 // Round 6 measured the host-pointer KeySwitch at worksize 128 at 19.5-20.0 k keyswitch/s with the process free to roam both sockets and
 // 22.7-23.2 k bound to the socket the GPU hangs off (profiles/r06_host_numa_sweep.txt): the pinned staging slabs live on the GPU's node,
 // and copy threads on the other socket pull every byte across the inter-socket links. The library never touches the affinity of a

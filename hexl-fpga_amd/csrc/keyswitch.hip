@@ -361,17 +361,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ksi_main(KsArgs a) {
 template <int LOGN, int LOGE>
 static int run_chunk_i(hexl_ks_plan* p, const KsArgs& a, int stage_mask, hipEvent_t* ev) {
     using G = Geom<LOGN, LOGE>;
-    static PerDeviceOnce once;
-    if (int rc = once.run(p->ctx->device, [] {
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ks_intt<LOGN, LOGE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)G::LDS_USED));
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ksi_special<LOGN, LOGE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)G::LDS_USED));
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ksi_main<LOGN, LOGE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)G::LDS_USED));
-            return 0;
-        }))
-        return rc;
+    if (int rc = hx_lds_optin<k_ks_intt<LOGN, LOGE>, k_ksi_special<LOGN, LOGE>, k_ksi_main<LOGN, LOGE>>(p->ctx->device, G::LDS_USED)) return rc;
     hipStream_t st = p->cur;
     if (ev) HX_CHECK(hipEventRecord(ev[0], st));
     if (stage_mask & 1)
@@ -390,17 +380,7 @@ static int run_chunk_i(hexl_ks_plan* p, const KsArgs& a, int stage_mask, hipEven
 template <int LOGN, int LOGE>
 static int run_chunk(hexl_ks_plan* p, const KsArgs& a, int stage_mask, hipEvent_t* ev) {
     using G = Geom<LOGN, LOGE>;
-    static PerDeviceOnce once;
-    if (int rc = once.run(p->ctx->device, [] {
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ks_intt<LOGN, LOGE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)G::LDS_USED));
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ks_modup<LOGN, LOGE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)G::LDS_USED));
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ks_moddown<LOGN, LOGE>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_USED));
-            return 0;
-        }))
-        return rc;
+    if (int rc = hx_lds_optin<k_ks_intt<LOGN, LOGE>, k_ks_modup<LOGN, LOGE>, k_ks_moddown<LOGN, LOGE>>(p->ctx->device, G::LDS_USED)) return rc;
     hipStream_t st = p->cur;
     if (ev) HX_CHECK(hipEventRecord(ev[0], st));
     if (stage_mask & 1)
@@ -417,28 +397,24 @@ static int run_chunk(hexl_ks_plan* p, const KsArgs& a, int stage_mask, hipEvent_
 
 // instances per scratch chunk: HEXL_KS_CHUNK, else 256 at N = 16384 and the same number of COEFFICIENTS per chunk at the
 // other ring dimensions (4096 instances at N = 1024: a chunk's kernels must fill the chip whatever the transform size)
-static size_t ks_chunk_default(const hexl_ks_plan* p) {
-    static const long v = [] {
-        const char* e = getenv("HEXL_KS_CHUNK");
-        const long c = e ? atol(e) : 0;
-        return c < 0 ? 0L : c;
-    }();
-    if (v) return (size_t)v;
+size_t hx_ks_chunk(const hexl_ks_plan* p) {
+    static const long v = hx_knob("HEXL_KS_CHUNK", 0);             // (negative = unset)
+    if (v > 0) return (size_t)v;
     return p->logn >= 14 ? size_t(256) >> (p->logn - 14) : size_t(256) << (14 - p->logn);
 }
-
-size_t hx_ks_chunk(const hexl_ks_plan* p) { return ks_chunk_default(p); }
 size_t hx_ks_f64_scratch_words(size_t L);
 static size_t scratch_words(const hexl_ks_plan* p) {           // per instance, in units of n 64-bit words
     return p->use_f64 ? hx_ks_f64_scratch_words(p->L) : size_t(3) * p->L + 2;
 }
 int hx_ks_lanes() {
-    static const int v = [] { const char* e = getenv("HEXL_KS_LANES"); const int l = e ? atoi(e) : 2; return l < 2 ? 2 : l > HX_KS_MAX_LANES ? HX_KS_MAX_LANES : l; }();
+    static const int v = [] { const long l = hx_knob("HEXL_KS_LANES", 2); return l < 2 ? 2 : l > HX_KS_MAX_LANES ? HX_KS_MAX_LANES : (int)l; }();
     return v;
 }
-size_t hexl_ks_scratch_bytes(const hexl_ks_plan* p, size_t batch) {
-    const size_t chunk = batch < ks_chunk_default(p) ? batch : ks_chunk_default(p);
-    return size_t(hx_ks_lanes()) * chunk * scratch_words(p) * p->n * sizeof(u64);      // two lanes
+static size_t lane_bytes(const hexl_ks_plan* p) { return size_t(hx_ks_lanes()) * scratch_words(p) * p->n * sizeof(u64); }   // per instance of a chunk, every lane
+size_t hexl_ks_scratch_bytes(const hexl_ks_plan* p, size_t batch) { return hx_ks_chunk_of(p, batch) * lane_bytes(p); }
+// the plan's scratch for chunks of `chunk` instances (grow-only; lanes of earlier launches may still work in the old one)
+static int reserve_scratch(hexl_ks_plan* p, size_t chunk) {
+    return hx_grow_device((void**)&p->d_scratch, &p->cap, chunk, lane_bytes(p), nullptr);
 }
 
 // HEXL_KS_VALIDATE=1: the keyswitch precondition (every t_target / result word below its modulus), checked on the device
@@ -475,7 +451,7 @@ static int validate_inputs(hexl_ks_plan* p, const u64* d_result, const u64* d_t_
 // the (b, d)-major FP64 kernels can write `result` instead of accumulating into it: every chunk of the batch must take them
 bool hx_ks_can_overwrite(const hexl_ks_plan* p, size_t nb) {
     if (!p->use_f64 || p->logn > 14) return false;               // (N = 32768: no registers for a second epilogue)
-    const size_t chunk = nb < ks_chunk_default(p) ? nb : ks_chunk_default(p);
+    const size_t chunk = hx_ks_chunk_of(p, nb);
     return !hx_ks_x_applies(p, chunk) && !hx_ks_x_applies(p, nb % chunk ? nb % chunk : chunk);
 }
 
@@ -483,28 +459,22 @@ int hx_launch_keyswitch(hexl_ks_plan* p, u64* d_result, const u64* d_t_target, s
                         hipEvent_t* ev) {
     if (!batch) return 0;
     if (!p->have_keys) return HEXL_E_NOKEYS;
-    static const bool validate = [] { const char* e = getenv("HEXL_KS_VALIDATE"); return e && atoi(e) == 1; }();
+    static const bool validate = hx_knob("HEXL_KS_VALIDATE", 0) == 1;
     if (validate)
         if (int rc = validate_inputs(p, d_result, d_t_target, batch)) return rc;
     // chunks alternate between two lanes; a batch that fits one chunk is still split in two when it is large
     // enough to fill the chip twice, so the lanes always have something to overlap. Timing runs (ev) stay on one lane.
-    size_t chunk = batch < ks_chunk_default(p) ? batch : ks_chunk_default(p);
+    size_t chunk = hx_ks_chunk_of(p, batch);
     // (FP64 path: with one barrier per transform and steps 1-2 fused, two lanes measure the same as one stream
     // (160 k vs 162 k keyswitch/s), so it runs its chunks back to back on the caller's stream; HEXL_KS_ONE_LANE=0
     // brings the lanes back)
     // The slot-major pipeline (keyswitch_x.hip) alternates its chunks between the two lanes again: one chunk's three
     // kernels fill the ragged end of the other's last generation of workgroups (174 k against 160-170 k keyswitch/s).
-    const char* lane_env = getenv("HEXL_KS_ONE_LANE");
-    const bool one_lane = lane_env ? atoi(lane_env) == 1 : (p->use_f64 && !hx_ks_x_applies(p, chunk));
+    const long lane_env = hx_knob("HEXL_KS_ONE_LANE", HX_KNOB_UNSET);       // (read by every call)
+    const bool one_lane = lane_env != HX_KNOB_UNSET ? lane_env == 1 : (p->use_f64 && !hx_ks_x_applies(p, chunk));
     const bool two_lanes = !ev && batch >= 64 && !one_lane && !(p->use_f64 && batch <= chunk);
     if (two_lanes && batch <= chunk) chunk = (batch + 1) / 2;
-    const size_t lane_words = chunk * scratch_words(p) * p->n;
-    if (p->cap < chunk) {
-        if (p->d_scratch) { HX_CHECK(hipDeviceSynchronize()); HX_CHECK(hipFree(p->d_scratch)); }
-        p->d_scratch = nullptr; p->cap = 0;
-        HX_CHECK(hipMalloc((void**)&p->d_scratch, size_t(hx_ks_lanes()) * lane_words * sizeof(u64)));
-        p->cap = chunk;
-    }
+    if (int rc = reserve_scratch(p, chunk)) return rc;
     if (!p->aux[0]) {
         for (int l = 0; l < hx_ks_lanes(); ++l) {
             HX_CHECK(hipStreamCreateWithFlags(&p->aux[l], hipStreamNonBlocking));
@@ -552,14 +522,16 @@ int hx_launch_keyswitch(hexl_ks_plan* p, u64* d_result, const u64* d_t_target, s
         a.result = d_result + b0 * 2 * L * n;
         a.L = (u32)L; a.K = p->K; a.nb = (u32)nb;
         // HEXL_KS_PIPE=1: the first-generation kernels (k_ks_modup / k_ks_moddown, `prod` through memory)
-        static const bool gen1 = [] { const char* e = getenv("HEXL_KS_PIPE"); return e && atoi(e) == 1; }();
+        auto run = [&](auto N, auto E) {
+            return hx_knob_ks_pipe() == 1 ? run_chunk<N, E>(p, a, stage_mask, ev) : run_chunk_i<N, E>(p, a, stage_mask, ev);
+        };
         switch (p->logn * 8 + p->int_loge) {
-            case 10 * 8 + 4: rc = gen1 ? run_chunk<10, 4>(p, a, stage_mask, ev) : run_chunk_i<10, 4>(p, a, stage_mask, ev); break;
-            case 11 * 8 + 5: rc = gen1 ? run_chunk<11, 5>(p, a, stage_mask, ev) : run_chunk_i<11, 5>(p, a, stage_mask, ev); break;
-            case 12 * 8 + 5: rc = gen1 ? run_chunk<12, 5>(p, a, stage_mask, ev) : run_chunk_i<12, 5>(p, a, stage_mask, ev); break;
-            case 13 * 8 + 5: rc = gen1 ? run_chunk<13, 5>(p, a, stage_mask, ev) : run_chunk_i<13, 5>(p, a, stage_mask, ev); break;
-            case 14 * 8 + 5: rc = gen1 ? run_chunk<14, 5>(p, a, stage_mask, ev) : run_chunk_i<14, 5>(p, a, stage_mask, ev); break;
-            case 14 * 8 + 4: rc = gen1 ? run_chunk<14, 4>(p, a, stage_mask, ev) : run_chunk_i<14, 4>(p, a, stage_mask, ev); break;
+            case 10 * 8 + 4: rc = run(hx_int<10>{}, hx_int<4>{}); break;
+            case 11 * 8 + 5: rc = run(hx_int<11>{}, hx_int<5>{}); break;
+            case 12 * 8 + 5: rc = run(hx_int<12>{}, hx_int<5>{}); break;
+            case 13 * 8 + 5: rc = run(hx_int<13>{}, hx_int<5>{}); break;
+            case 14 * 8 + 5: rc = run(hx_int<14>{}, hx_int<5>{}); break;
+            case 14 * 8 + 4: rc = run(hx_int<14>{}, hx_int<4>{}); break;
             default: rc = HEXL_E_BADARG;
         }
         if (rc) return rc;
@@ -578,14 +550,8 @@ int hx_launch_multiply_relinearize(hexl_ks_plan* p, u64* d_out, const u64* d_a, 
     if (!batch) return 0;
     if (!p->have_keys) return HEXL_E_NOKEYS;
     if (!p->use_f64 || p->logn < 10 || p->logn > 15) return HEXL_E_BADARG;   // see hx_launch_mulrelin_x
-    const size_t chunk = batch < ks_chunk_default(p) ? batch : ks_chunk_default(p);
-    const size_t lane_words = chunk * scratch_words(p) * p->n;
-    if (p->cap < chunk) {
-        if (p->d_scratch) { HX_CHECK(hipDeviceSynchronize()); HX_CHECK(hipFree(p->d_scratch)); }
-        p->d_scratch = nullptr; p->cap = 0;
-        HX_CHECK(hipMalloc((void**)&p->d_scratch, size_t(hx_ks_lanes()) * lane_words * sizeof(u64)));
-        p->cap = chunk;
-    }
+    const size_t chunk = hx_ks_chunk_of(p, batch);
+    if (int rc = reserve_scratch(p, chunk)) return rc;
     p->cur = p->ctx->stream;
     p->cur_scratch = p->d_scratch;
     const size_t per = 2 * p->L * p->n;

@@ -463,26 +463,14 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ksl_down(KsArgsF a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-template <class K>
-static int set_lds(K kern, size_t bytes) {
-    HX_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return 0;
-}
-
 template <int LOGN, int LOGE, int LAZY>
 static int run_chunk_f64(hexl_ks_plan* p, const KsArgsF& a, int stage_mask, hipEvent_t* ev) {
     using G = Geom<LOGN, LOGE>;
-    static PerDeviceOnce once;
-    if (int rc0 = once.run(p->ctx->device, [] {
-            int rc = 0;
-            if constexpr (LAZY >= 0) rc = set_lds(k_ksf_up<LOGN, LOGE, LAZY>, G::LDS_USED);
-            if (!rc) rc = set_lds(k_ksf_intt<LOGN, LOGE, LAZY>, G::LDS_USED);
-            if (!rc) rc = set_lds(k_ksf_ntt_up<LOGN, LOGE, LAZY>, G::LDS_USED);
-            if (!rc) rc = set_lds(k_ksf_intt_sp<LOGN, LOGE, LAZY>, G::LDS_USED);
-            if (!rc) rc = set_lds(k_ksf_moddown<LOGN, LOGE, LAZY>, G::LDS_USED);
-            return rc;
-        }))
-        return rc0;
+    if constexpr (LAZY >= 0)
+        if (int rc = hx_lds_optin<k_ksf_up<LOGN, LOGE, LAZY>>(p->ctx->device, G::LDS_USED)) return rc;
+    if (int rc = hx_lds_optin<k_ksf_intt<LOGN, LOGE, LAZY>, k_ksf_ntt_up<LOGN, LOGE, LAZY>, k_ksf_intt_sp<LOGN, LOGE, LAZY>,
+                              k_ksf_moddown<LOGN, LOGE, LAZY>>(p->ctx->device, G::LDS_USED))
+        return rc;
     hipStream_t st = p->cur;
     const u32 L = a.L, nb = a.nb;
     // latency path (three kernels, above): a LONE keyswitch. Measured (tools/batch_sweep.py, N = 16384, device-resident): 70.3 us
@@ -493,17 +481,11 @@ static int run_chunk_f64(hexl_ks_plan* p, const KsArgsF& a, int stage_mask, hipE
     // that takes this pipeline (tests).
     // Not for N = 32768 (no registers for the key rows beside 64 data registers); timing runs (ev) keep the five-kernel path,
     // whose stages the events bracket.
-    static const int lat = [] { const char* e = getenv("HEXL_KS_LAT"); return e ? atoi(e) : -1; }();
+    const int lat = hx_knob_ks_lat();
     if constexpr (!G::HALF_ONLY)
     if (!ev && stage_mask == 7 && L <= 15 && (lat == 1 || (lat != 0 && nb == 1))) {
-        static PerDeviceOnce once_l;
-        if (int rc0 = once_l.run(p->ctx->device, [] {
-                int rc = set_lds(k_ksl_intt<LOGN, LOGE, LAZY>, G::LDS_USED);
-                if (!rc) rc = set_lds(k_ksl_up<LOGN, LOGE, LAZY>, G::LDS_USED);
-                if (!rc) rc = set_lds(k_ksl_down<LOGN, LOGE, LAZY>, G::LDS_USED);
-                return rc;
-            }))
-            return rc0;
+        if (int rc = hx_lds_optin<k_ksl_intt<LOGN, LOGE, LAZY>, k_ksl_up<LOGN, LOGE, LAZY>, k_ksl_down<LOGN, LOGE, LAZY>>(p->ctx->device, G::LDS_USED))
+            return rc;
         hipLaunchKernelGGL((k_ksl_intt<LOGN, LOGE, LAZY>), dim3(nb * L), dim3(G::T), G::LDS_USED, st, a);
         hipLaunchKernelGGL((k_ksl_up<LOGN, LOGE, LAZY>), dim3(nb * (L + 1) * L), dim3(G::T), G::LDS_USED, st, a);
         hipLaunchKernelGGL((k_ksl_down<LOGN, LOGE, LAZY>), dim3(nb * 2 * L), dim3(G::T), G::LDS_USED, st, a);
@@ -514,7 +496,7 @@ static int run_chunk_f64(hexl_ks_plan* p, const KsArgsF& a, int stage_mask, hipE
     const u32 cus = (u32)p->ctx->num_cu;
     // (the same fusion of steps 4-7 -- s' in registers, L mod-down transforms per workgroup -- measured 8 % slower
     // than the two kernels below: its epilogue loads cannot be requested early, tools/experiments/fused_down.patch)
-    static const int fuse = [] { const char* e = getenv("HEXL_KS_FUSE"); return e ? atoi(e) : 1; }();
+    static const int fuse = (int)hx_knob("HEXL_KS_FUSE", 1);
     const bool fused_up = LAZY >= 0 && (fuse & 1) && nb * L >= 2 * cus && !G::HALF_ONLY;   // N = 32768: 64 VGPRs of data already
     // timing stages: 1 = steps 1-2 (inverse + mod-up transforms), 2 = steps 3-4, 4 = steps 5-7
     if (ev) HX_CHECK(hipEventRecord(ev[0], st));
@@ -557,48 +539,16 @@ int hx_launch_keyswitch_f64(hexl_ks_plan* p, u64* d_result, const u64* d_t_targe
     a.range_flag = p->d_flag;
     a.overwrite = p->overwrite_result ? 1u : 0u;
     a.skip = p->x_skip ? 1u : 0u;
-    a.tiermap = 0;
-    for (u32 i = 0; i < p->K; ++i) a.tiermap |= (unsigned long long)(p->tier[i] & 15u) << (4 * i);
+    a.tiermap = hx_tiermap(p);
     // Limbs of different tiers: the kernels built with LAZY = -1 look the schedule up per transform (with_tier). They are NOT the default
     // here: this pipeline serves the batches that do not fill the chip, where latency binds, not FP64 issue, and a kernel that carries
     // two to four copies of its transforms spills (k_ksf_moddown 80 registers, k_ksl_up 116) -- bridge-seal's chain at 2 ... 48 instances runs
     // 1-12 % FASTER on the plan-wide tier (round 5, tools/seal_chain_rate.py; 4 instances: 44.3 k against 38.9 k keyswitch/s). The slot-major
     // pipeline (one launch per tier group, +14 %) and the lone-keyswitch kernels keep their per-limb tiers. HEXL_KS_PER_LIMB=2 selects the
     // per-transform lookup here as well (tests).
-    static const bool lookup = [] { const char* e = getenv("HEXL_KS_PER_LIMB"); return e && atoi(e) == 2; }();
-    if (p->mixed && lookup) {
-        switch (p->logn) {
-            case 10: return run_chunk_f64<10, 4, -1>(p, a, stage_mask, ev);
-            case 11: return run_chunk_f64<11, 5, -1>(p, a, stage_mask, ev);
-            case 12: return run_chunk_f64<12, 5, -1>(p, a, stage_mask, ev);
-            case 13: return run_chunk_f64<13, 5, -1>(p, a, stage_mask, ev);
-            case 14: return run_chunk_f64<14, 4, -1>(p, a, stage_mask, ev);
-            case 15: return run_chunk_f64<15, 5, -1>(p, a, stage_mask, ev);
-            default: return HEXL_E_BADARG;
-        }
-    }
+    static const bool lookup = hx_knob_ks_per_limb() == 2;
     // LAZY template argument = forward reduction period (f64_arith.hpp): 3 when every modulus <= 2^51(1+2^-7), 6 / 12
     // for moduli <= 2^50 / 2^49 (N = 16384 only; the smaller transforms keep 3), 0 = strict
-    if (p->f64_lazy) {
-        switch (p->logn) {
-            case 10: return run_chunk_f64<10, 4, 3>(p, a, stage_mask, ev);
-            case 11: return run_chunk_f64<11, 5, 3>(p, a, stage_mask, ev);
-            case 12: return run_chunk_f64<12, 5, 3>(p, a, stage_mask, ev);
-            case 13: return run_chunk_f64<13, 5, 3>(p, a, stage_mask, ev);
-            case 15: return run_chunk_f64<15, 5, 3>(p, a, stage_mask, ev);      // beyond the reference: N = 32768
-            case 14: return p->f64_lazy == 12 ? run_chunk_f64<14, 4, 12>(p, a, stage_mask, ev)
-                          : p->f64_lazy == 6 ? run_chunk_f64<14, 4, 6>(p, a, stage_mask, ev)
-                                             : run_chunk_f64<14, 4, 3>(p, a, stage_mask, ev);
-            default: return HEXL_E_BADARG;
-        }
-    }
-    switch (p->logn) {
-        case 10: return run_chunk_f64<10, 4, 0>(p, a, stage_mask, ev);
-        case 11: return run_chunk_f64<11, 5, 0>(p, a, stage_mask, ev);
-        case 12: return run_chunk_f64<12, 5, 0>(p, a, stage_mask, ev);
-        case 13: return run_chunk_f64<13, 5, 0>(p, a, stage_mask, ev);
-        case 15: return run_chunk_f64<15, 5, 0>(p, a, stage_mask, ev);
-        case 14: return run_chunk_f64<14, 4, 0>(p, a, stage_mask, ev);
-        default: return HEXL_E_BADARG;
-    }
+    return hx_with_f64_geom(p->logn, p->mixed && lookup ? -1 : p->f64_lazy,
+                            [&](auto N, auto E, auto Z) { return run_chunk_f64<N, E, Z>(p, a, stage_mask, ev); });
 }

@@ -47,7 +47,7 @@ struct KsArgsQ {
     u32 L, K;
     u32* range_flag;
     u32 overwrite, skip;     // as in keyswitch_f64.hip
-    // The host-pointer entry point runs a lone keyswitch ZERO-COPY (capi.hip keyswitch_host_lone, round 5): t_target and result are then
+    // The host-pointer entry point runs a lone keyswitch ZERO-COPY (host_staging.hip keyswitch_host_lone, round 5): t_target and result are then
     // device-visible PINNED HOST memory -- k_ksq_intt pulls the 0.8 MB of t_target across PCIe while it transforms (18.7 us against a
     // 29.5 us hipMemcpyAsync in front of the kernel, tools/zero_copy_probe), k_ksq_down pushes its 1.6 MB the same way (31.6 against
     // 43.2 us behind it). Hence: t_target is read exactly ONCE (k_ksq_intt leaves the raw words in `tcopy` for the slot == d terms of
@@ -383,16 +383,8 @@ __global__ __launch_bounds__(GQ::T) KSQ_ILP void k_ksq_down(KsArgsQ a) {
 // ---------------------------------------------------------------------------------------------
 template <int LAZY>
 static int run_lat(hexl_ks_plan* p, const KsArgsQ& a, u32 nb) {
-    static PerDeviceOnce once;
     constexpr size_t lds = GQ::LDS_USED;
-    if (int rc0 = once.run(p->ctx->device, [] {
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ksq_intt<LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ksq_up<LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ksq_intt_sp<LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ksq_down<LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            return 0;
-        }))
-        return rc0;
+    if (int rc = hx_lds_optin<k_ksq_intt<LAZY>, k_ksq_up<LAZY>, k_ksq_intt_sp<LAZY>, k_ksq_down<LAZY>>(p->ctx->device, lds)) return rc;
     hipStream_t st = p->cur;
     const u32 L = a.L;
     hipLaunchKernelGGL((k_ksq_intt<LAZY>), dim3(4 * L, nb), dim3(GQ::T), lds, st, a);
@@ -406,8 +398,8 @@ static int run_lat(hexl_ks_plan* p, const KsArgsQ& a, u32 nb) {
 // HEXL_KS_LAT: 0 = off, 1 = the three-kernel path of keyswitch_f64.hip instead, 2 = this path for EVERY batch that fits a scratch
 // chunk (tests), HEXL_KS_LAT_MAX = largest batch that takes it by default.
 bool hx_ks_lat_applies(const hexl_ks_plan* p, size_t nb) {
-    static const int lat = [] { const char* e = getenv("HEXL_KS_LAT"); return e ? atoi(e) : -1; }();
-    static const long most = [] { const char* e = getenv("HEXL_KS_LAT_MAX"); return e ? atol(e) : -1L; }();
+    const int lat = hx_knob_ks_lat();
+    static const long most = hx_knob("HEXL_KS_LAT_MAX", -1);
     // default: as long as the (slot, d) pairs of the batch are at most KSQ_DEFAULT_MAX_PAIRS -- measured (tools/batch_sweep.py, us per
     // launch, this path / the five kernels): L = 6: 49.4 / 71.4 at one keyswitch, 59.7 / 73.8 at two, 67.2 / 76.5 at three, 80.2 / 78.5
     // at four; L = 7: 54.6 / 73.7, 67.6 / 76.3, 79.9 / 78.4 at three
@@ -437,12 +429,11 @@ int hx_launch_keyswitch_lat(hexl_ks_plan* p, u64* d_result, const u64* d_t_targe
     a.range_flag = p->host_flag ? p->host_flag : p->d_flag;
     a.overwrite = p->overwrite_result ? 1u : 0u;
     a.skip = p->x_skip ? 1u : 0u;
-    a.tiermap = 0;
-    for (u32 i = 0; i < p->K; ++i) a.tiermap |= (unsigned long long)(p->tier[i] & 15u) << (4 * i);
+    a.tiermap = hx_tiermap(p);
     // limbs of different tiers: looked up per transform (with_tier) for a LONE keyswitch (bridge-seal's chain: 48.6 against 49.5 us); two to
     // four instances measured 2-10 % slower that way than on the plan-wide tier (tools/seal_chain_rate.py, round 5) and keep the latter --
     // HEXL_KS_PER_LIMB=2: the lookup for every batch (tests; keyswitch_f64.hip has the same knob)
-    static const bool lookup = [] { const char* e = getenv("HEXL_KS_PER_LIMB"); return e && atoi(e) == 2; }();
+    static const bool lookup = hx_knob_ks_per_limb() == 2;
     if (p->mixed && (nb == 1 || lookup)) return run_lat<-1>(p, a, (u32)nb);
     switch (p->f64_lazy) {
         case 12: return run_lat<12>(p, a, (u32)nb);

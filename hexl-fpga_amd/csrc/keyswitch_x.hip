@@ -909,29 +909,18 @@ __global__ __launch_bounds__(1024, 4) void k_ksh_main(KsArgsX a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-template <class K>
-static int set_lds_x(K kern, size_t bytes) {
-    HX_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return 0;
-}
-
 // one kernel of the pipeline for the limbs `a` selects: stage 1 = k_ksx_intt (step 1), 2 = k_ksx_special (steps 2-4, special slot),
 // 4 = k_ksx_main (steps 2-3 and 5-7 of the decomposition slots)
 template <int LOGN, int LOGE, int LAZY, bool FUSED = false, bool SKIP = false>
 static int launch_stage_x(hexl_ks_plan* p, const KsArgsX& a, int stage) {
     using G = Geom<LOGN, LOGE>;
-    static PerDeviceOnce once;
-    if (int rc0 = once.run(p->ctx->device, [] {
-            int rc = set_lds_x(k_ksx_special<LOGN, LOGE, LAZY, SKIP>, G::LDS_USED);
-            if (!rc) rc = set_lds_x(k_ksx_intt<LOGN, LOGE, LAZY, FUSED>, G::LDS_USED);
-            if (!rc) rc = set_lds_x(k_ksx_main<LOGN, LOGE, LAZY, FUSED, SKIP>, G::LDS_USED);
-            return rc;
-        }))
-        return rc0;
+    if (int rc = hx_lds_optin<k_ksx_special<LOGN, LOGE, LAZY, SKIP>, k_ksx_intt<LOGN, LOGE, LAZY, FUSED>, k_ksx_main<LOGN, LOGE, LAZY, FUSED, SKIP>>(
+            p->ctx->device, G::LDS_USED))
+        return rc;
     hipStream_t st = p->cur;
     // persistent grids: 8 x g workgroups, g = workgroups per XCD = one per CU unless there are fewer items
     // (HEXL_KSX_PERSIST=0: one workgroup per item)
-    static const int persist = [] { const char* e = getenv("HEXL_KSX_PERSIST"); return e ? atoi(e) : 1; }();
+    static const int persist = (int)hx_knob("HEXL_KSX_PERSIST", 1);
     // workgroups one CU holds at once: 16 (or 8) waves of 64 threads
     constexpr u32 wg_per_cu = (KX_WAVES(LOGE) * 4 * 64) / G::T ? (KX_WAVES(LOGE) * 4 * 64) / G::T : 1;
     auto grid_for = [&](u32 items) {
@@ -967,6 +956,20 @@ static int launch_stage_tier(hexl_ks_plan* p, const KsArgsX& a, int stage, int t
     }
 }
 
+// launch(key(i0)) once per group of limbs i < a.L that share key(i), with a.nsel / a.selmap selecting the group
+template <class Key, class Launch>
+static int per_group(KsArgsX& a, Key key, Launch launch) {
+    bool done[16] = {};
+    for (u32 i0 = 0; i0 < a.L; ++i0) {
+        if (done[i0]) continue;
+        a.nsel = 0; a.selmap = 0;
+        for (u32 i = i0; i < a.L; ++i)
+            if (!done[i] && key(i) == key(i0)) { done[i] = true; a.selmap |= (unsigned long long)i << (4 * a.nsel++); }
+        if (int rc = launch(key(i0))) return rc;
+    }
+    return 0;
+}
+
 // One chunk. Plans of ONE tier: three launches, every limb in each. Plans of mixed tiers (hexl_ks_plan::mixed; round 5): k_ksx_intt once
 // for the strict limbs and once for the lazy ones (an inverse transform has those two forms only), k_ksx_special in the special prime's
 // tier, k_ksx_main once per tier present among the decomposition limbs -- e.g. bridge-seal's chain 52,30,30,40,27,27,27
@@ -975,34 +978,21 @@ static int launch_stage_tier(hexl_ks_plan* p, const KsArgsX& a, int stage, int t
 template <int LOGN, int LOGE, bool FUSED = false>
 static int run_chunk_x(hexl_ks_plan* p, KsArgsX a, int stage_mask, hipEvent_t* ev) {
     hipStream_t st = p->cur;
-    const u32 L = a.L;
     const bool per_limb = p->mixed && LOGE == 4;
     auto tier_of = [&](u32 i) { return per_limb ? (int)p->tier[i] : p->f64_lazy; };
-    // launch `stage` once per group of limbs that share key(tier)
-    auto per_group = [&](int stage, auto key) -> int {
-        bool done[16] = {};
-        for (u32 i0 = 0; i0 < L; ++i0) {
-            if (done[i0]) continue;
-            const int t0 = tier_of(i0);
-            a.nsel = 0; a.selmap = 0;
-            for (u32 i = i0; i < L; ++i)
-                if (!done[i] && key(tier_of(i)) == key(t0)) { done[i] = true; a.selmap |= (unsigned long long)i << (4 * a.nsel++); }
-            if (int rc = launch_stage_tier<LOGN, LOGE, FUSED>(p, a, stage, key(t0), p->x_skip)) return rc;
-        }
-        return 0;
-    };
+    auto stage = [&](int s) { return [&a, p, s](int tier) { return launch_stage_tier<LOGN, LOGE, FUSED>(p, a, s, tier, p->x_skip); }; };
     // timing stages: 1 = step 1 (inverse transforms), 2 = special slot (steps 2-4), 4 = decomposition slots (steps 2-3, 5-7)
     if (ev) HX_CHECK(hipEventRecord(ev[0], st));
     if (stage_mask & 1)
-        if (int rc = per_group(1, [](int t) { return t ? 3 : 0; })) return rc;
+        if (int rc = per_group(a, [&](u32 i) { return tier_of(i) ? 3 : 0; }, stage(1))) return rc;   // (an inverse transform is strict or lazy)
     if (ev) HX_CHECK(hipEventRecord(ev[1], st));
     if (stage_mask & 2) {
-        a.nsel = L; a.selmap = 0xFEDCBA9876543210ull;
-        if (int rc = launch_stage_tier<LOGN, LOGE, FUSED>(p, a, 2, tier_of(a.K - 1), p->x_skip)) return rc;
+        a.nsel = a.L; a.selmap = 0xFEDCBA9876543210ull;
+        if (int rc = stage(2)(tier_of(a.K - 1))) return rc;
     }
     if (ev) HX_CHECK(hipEventRecord(ev[2], st));
     if (stage_mask & 4)
-        if (int rc = per_group(4, [](int t) { return (LOGN == 14 && LOGE == 4 && !FUSED) ? t : (t ? 3 : 0); })) return rc;
+        if (int rc = per_group(a, [&](u32 i) { return (LOGN == 14 && LOGE == 4 && !FUSED) ? tier_of(i) : (tier_of(i) ? 3 : 0); }, stage(4))) return rc;
     if (ev) HX_CHECK(hipEventRecord(ev[3], st));
     return (int)hipGetLastError();
 }
@@ -1012,14 +1002,7 @@ static int run_chunk_x(hexl_ks_plan* p, KsArgsX a, int stage_mask, hipEvent_t* e
 template <int LAZY, bool SKIP, bool FUSED = false>
 static int launch_stage_h(hexl_ks_plan* p, const KsArgsX& a, int stage) {
     using G = Geom<14, 4>;
-    static PerDeviceOnce once;
-    if (int rc0 = once.run(p->ctx->device, [] {
-            int rc = set_lds_x(k_ksh_intt<LAZY, FUSED>, G::LDS_USED);
-            if (!rc) rc = set_lds_x(k_ksh_special<LAZY, SKIP>, G::LDS_USED);
-            if (!rc) rc = set_lds_x(k_ksh_main<LAZY, SKIP, FUSED>, G::LDS_USED);
-            return rc;
-        }))
-        return rc0;
+    if (int rc = hx_lds_optin<k_ksh_intt<LAZY, FUSED>, k_ksh_special<LAZY, SKIP>, k_ksh_main<LAZY, SKIP, FUSED>>(p->ctx->device, G::LDS_USED)) return rc;
     hipStream_t st = p->cur;
     auto grid_for = [&](u32 items) {
         const u32 per_xcd = (items + 7) / 8, slots = ((u32)p->ctx->num_cu + 7) / 8;
@@ -1040,31 +1023,21 @@ static int run_chunk_h(hexl_ks_plan* p, KsArgsX a, int stage_mask, hipEvent_t* e
     hipStream_t st = p->cur;
     const u32 L = a.L;
     auto tier_of = [&](u32 i) { return p->mixed ? (p->tier[i] ? 3 : 0) : (p->f64_lazy ? 3 : 0); };
-    auto per_group = [&](int stage) -> int {
-        bool done[16] = {};
-        for (u32 i0 = 0; i0 < L; ++i0) {
-            if (done[i0]) continue;
-            a.nsel = 0; a.selmap = 0;
-            for (u32 i = i0; i < L; ++i)
-                if (!done[i] && tier_of(i) == tier_of(i0)) { done[i] = true; a.selmap |= (unsigned long long)i << (4 * a.nsel++); }
-            if (int rc = launch_stage_h_tier<FUSED>(p, a, stage, tier_of(i0), p->x_skip)) return rc;
-        }
-        return 0;
-    };
+    auto stage = [&](int s) { return [&a, p, s](int tier) { return launch_stage_h_tier<FUSED>(p, a, s, tier, p->x_skip); }; };
     if (ev) HX_CHECK(hipEventRecord(ev[0], st));
     if (stage_mask & 1) {
-        if (int rc = per_group(1)) return rc;
+        if (int rc = per_group(a, tier_of, stage(1))) return rc;
         hipLaunchKernelGGL((k_ksh_finish<0>), dim3((1u << 14) / 256, a.nb * L), dim3(256), 0, st, a, a.nb * L);
     }
     if (ev) HX_CHECK(hipEventRecord(ev[1], st));
     if (stage_mask & 2) {
         a.nsel = L; a.selmap = 0xFEDCBA9876543210ull;
-        if (int rc = launch_stage_h_tier<FUSED>(p, a, 2, tier_of(a.K - 1), p->x_skip)) return rc;
+        if (int rc = stage(2)(tier_of(a.K - 1))) return rc;
         hipLaunchKernelGGL((k_ksh_finish<1>), dim3((1u << 14) / 256, a.nb * 2), dim3(256), 0, st, a, a.nb * 2);
     }
     if (ev) HX_CHECK(hipEventRecord(ev[2], st));
     if (stage_mask & 4)
-        if (int rc = per_group(4)) return rc;
+        if (int rc = per_group(a, tier_of, stage(4))) return rc;
     if (ev) HX_CHECK(hipEventRecord(ev[3], st));
     return (int)hipGetLastError();
 }
@@ -1075,7 +1048,7 @@ size_t hx_ks_x_scratch_words(size_t L) { return L + 2; }   // per instance, in u
 // fused k_ksf_up of the (b, d)-major pipeline. HEXL_KS_PIPE=1 keeps the (b, d)-major pipeline (tests, comparisons).
 u32 hx_ks_x_loge() { return 4; }                                  // 16 coefficients per thread at every ring dimension
 bool hx_ks_x_applies(const hexl_ks_plan* p, size_t nb) {
-    static const int pipe = [] { const char* e = getenv("HEXL_KS_PIPE"); return e ? atoi(e) : 2; }();
+    const int pipe = hx_knob_ks_pipe();
     if (!p->d_keys_x || p->logn < 10 || p->logn > 15) return false;
     if (p->logn == 15 && p->x_loge != 4) return false;              // (N = 32768: the 16 x 1024 half-transform kernels only)
     // one workgroup per (instance, limb) must nearly fill the chip twice (a CU holds 16384 / N of them): measured at N = 16384,
@@ -1105,7 +1078,10 @@ u32 hx_ksx_alias_mask();
 static u32 ksx_alias_mask() { return hx_ksx_alias_mask(); }
 #endif
 
-int hx_launch_keyswitch_x(hexl_ks_plan* p, u64* d_result, const u64* d_t_target, size_t nb, int stage_mask,
+// the arguments of one chunk on p->cur / p->cur_scratch: a keyswitch (t_target -> += result) or, with the ciphertext pairs mul_a / mul_b,
+// the fused multiply + relinearize (result written); then the chunk's kernels for the plan's ring dimension
+template <bool FUSED>
+static int launch_chunk_x(hexl_ks_plan* p, u64* d_result, const u64* d_t_target, const u64* d_a, const u64* d_b, size_t nb, int stage_mask,
                           hipEvent_t* ev) {
     const size_t n = p->n, L = p->L;
     KsArgsX a;
@@ -1114,56 +1090,36 @@ int hx_launch_keyswitch_x(hexl_ks_plan* p, u64* d_result, const u64* d_t_target,
     a.s = a.c + p->cap * L * n;
     a.csub = a.s + p->cap * 2 * n;                                  // (N = 32768 only; inside the (b, d)-major scratch, which is larger)
     a.ssub = a.csub + p->cap * L * n;
+    a.nsel = (u32)L; a.selmap = 0xFEDCBA9876543210ull;
     a.t_target = d_t_target; a.result = d_result;
     a.L = (u32)L; a.K = p->K; a.nb = (u32)nb;
-    a.mul_a = a.mul_b = nullptr;
+    a.mul_a = d_a; a.mul_b = d_b;
     a.stamps = nullptr;
-    a.alias = ksx_alias_mask();
+    a.alias = FUSED ? 0u : ksx_alias_mask();
     a.key_stride = (a.alias & 1u) ? 0u : u32(2 * n);
     a.range_flag = p->d_flag;
+    // (the kernels' LAZY template argument = forward reduction period of the transforms, f64_arith.hpp: launch_stage_tier)
     switch (p->logn) {
-        case 10: return run_chunk_x<10, 4>(p, a, stage_mask, ev);
-        case 11: return run_chunk_x<11, 4>(p, a, stage_mask, ev);
-        case 12: return run_chunk_x<12, 4>(p, a, stage_mask, ev);
-        case 13: return run_chunk_x<13, 4>(p, a, stage_mask, ev);
-        case 14: break;
-        case 15: return run_chunk_h(p, a, stage_mask, ev);           // two 16384-point halves per transform (k_ksh_*)
+        case 10: return run_chunk_x<10, 4, FUSED>(p, a, stage_mask, ev);
+        case 11: return run_chunk_x<11, 4, FUSED>(p, a, stage_mask, ev);
+        case 12: return run_chunk_x<12, 4, FUSED>(p, a, stage_mask, ev);
+        case 13: return run_chunk_x<13, 4, FUSED>(p, a, stage_mask, ev);
+        case 14: return run_chunk_x<14, 4, FUSED>(p, a, stage_mask, ev);
+        case 15: return run_chunk_h<FUSED>(p, a, stage_mask, ev);   // two 16384-point halves per transform (k_ksh_*)
         default: return HEXL_E_BADARG;
     }
-    // (the kernels' LAZY template argument = forward reduction period of the transforms, f64_arith.hpp: launch_stage_tier)
-    return run_chunk_x<14, 4>(p, a, stage_mask, ev);
+}
+
+int hx_launch_keyswitch_x(hexl_ks_plan* p, u64* d_result, const u64* d_t_target, size_t nb, int stage_mask,
+                          hipEvent_t* ev) {
+    return launch_chunk_x<false>(p, d_result, d_t_target, nullptr, nullptr, nb, stage_mask, ev);
 }
 
 // fused ciphertext multiply + relinearize for one scratch chunk (always the slot-major pipeline, 16-coefficient geometry).
 // Where the partial pass leaves a lane at most four adjacent words (N = 1024, 8192, 16384) the operand limbs are read straight at
 // the transforms' B positions; N = 2048 / 4096 read them in A order and go through LDS (load_product_to_B, ksx_down_round).
-// (N = 32768: the half-transform kernels k_ksh_*<..., FUSED>, hx_launch_mulrelin_x below.)
-template <int LOGN>
-static int mulrelin_for(hexl_ks_plan* p, const KsArgsX& a) { return run_chunk_x<LOGN, 4, true>(p, a, 7, nullptr); }
+// (N = 32768: the half-transform kernels k_ksh_*<..., FUSED>.)
 int hx_launch_mulrelin_x(hexl_ks_plan* p, u64* d_out, const u64* d_a, const u64* d_b, size_t nb) {
-    const size_t n = p->n, L = p->L;
     if (!p->use_f64 || !p->d_keys_x || p->x_loge != 4) return HEXL_E_BADARG;
-    KsArgsX a;
-    a.mods = p->d_mods_f64; a.tables = p->d_tables_f64; a.keys = p->d_keys_x;
-    a.c = (double*)p->cur_scratch;
-    a.s = a.c + p->cap * L * n;
-    a.csub = a.s + p->cap * 2 * n;                                  // (N = 32768 only)
-    a.ssub = a.csub + p->cap * L * n;
-    a.nsel = (u32)L; a.selmap = 0xFEDCBA9876543210ull;
-    a.t_target = nullptr; a.result = d_out;
-    a.L = (u32)L; a.K = p->K; a.nb = (u32)nb;
-    a.mul_a = d_a; a.mul_b = d_b;
-    a.stamps = nullptr;
-    a.alias = 0;
-    a.key_stride = u32(2 * n);
-    a.range_flag = p->d_flag;
-    switch (p->logn) {
-        case 10: return mulrelin_for<10>(p, a);
-        case 11: return mulrelin_for<11>(p, a);
-        case 12: return mulrelin_for<12>(p, a);
-        case 13: return mulrelin_for<13>(p, a);
-        case 14: return mulrelin_for<14>(p, a);
-        case 15: return run_chunk_h<true>(p, a, 7, nullptr);         // every transform as two 16384-point halves (k_ksh_*)
-        default: return HEXL_E_BADARG;
-    }
+    return launch_chunk_x<true>(p, d_out, nullptr, d_a, d_b, nb, 7, nullptr);
 }

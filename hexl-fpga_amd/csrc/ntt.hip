@@ -638,12 +638,18 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ntt_redo_inv(u64* __rest
 
 // HEXL_NTT_HALVES=0: N = 32768 back on the monolithic half-size-exchange kernels (A/B)
 static bool halves_enabled() {
-    static const bool v = [] { const char* e = getenv("HEXL_NTT_HALVES"); return !(e && atoi(e) == 0); }();
+    static const bool v = hx_knob("HEXL_NTT_HALVES", 1) != 0;
+    return v;
+}
+
+// HEXL_NTT_PERSIST=0: one workgroup per polynomial instead of persistent workgroups with input prefetch
+static bool persist_enabled() {
+    static const bool v = hx_knob("HEXL_NTT_PERSIST", 1) != 0;
     return v;
 }
 
 static bool fast_path_enabled() {
-    static const bool v = [] { const char* e = getenv("HEXL_NTT_INT"); return !(e && atoi(e) == 1); }();
+    static const bool v = hx_knob("HEXL_NTT_INT", 0) != 1;
     return v;
 }
 
@@ -796,12 +802,7 @@ u32 hx_idxB(u32 logn, u32 r, u32 tid) {
 template <int LOGN, int LOGE>
 static int launch_fwd(hexl_ctx* ctx, u64* x, size_t batch, const u64* roots, const u64* precon, u64 q) {
     using G = Geom<LOGN, LOGE>;
-    static PerDeviceOnce once;
-    if (int rc = once.run(ctx->device, [] {
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ntt_fwd<LOGN, LOGE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_USED));
-            return 0;
-        }))
-        return rc;
+    if (int rc = hx_lds_optin<k_ntt_fwd<LOGN, LOGE>>(ctx->device, G::LDS_USED)) return rc;
     // (a persistent forward integer kernel measured no faster in rounds 2 and 4 -- the integer butterflies are bound by their instruction
     // count, the prefetch registers cost what the hidden load latency gains -- and is gone)
     hipLaunchKernelGGL((k_ntt_fwd<LOGN, LOGE>), dim3((unsigned)batch), dim3(G::T), G::LDS_USED, ctx->stream, x,
@@ -813,21 +814,11 @@ template <int LOGN, int LOGE>
 static int launch_inv(hexl_ctx* ctx, u64* x, size_t batch, const u64* ir, const u64* ip, u64 q, u64 a, u64 ap,
                       u64 b, u64 bp) {
     using G = Geom<LOGN, LOGE>;
-    static PerDeviceOnce once;
-    if (int rc = once.run(ctx->device, [] {
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ntt_inv<LOGN, LOGE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_USED));
-            return 0;
-        }))
-        return rc;
-    static const int persist = [] { const char* e = getenv("HEXL_NTT_PERSIST"); return e ? atoi(e) : 1; }();
+    if (int rc = hx_lds_optin<k_ntt_inv<LOGN, LOGE>>(ctx->device, G::LDS_USED)) return rc;
+    const bool persist = persist_enabled();
     const size_t slots = size_t(ctx->num_cu) * (G::LDS_USED > 80 * 1024 ? 1 : (160 * 1024) / G::LDS_USED);
     if constexpr (LOGN == 14 && LOGE == 4) if (persist && batch > slots) {
-        static PerDeviceOnce once_p;
-        if (int rc = once_p.run(ctx->device, [] {
-                HX_CHECK(hipFuncSetAttribute((const void*)k_ntt_inv_ip<LOGN, LOGE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_USED));
-                return 0;
-            }))
-            return rc;
+        if (int rc = hx_lds_optin<k_ntt_inv_ip<LOGN, LOGE>>(ctx->device, G::LDS_USED)) return rc;
         hipLaunchKernelGGL((k_ntt_inv_ip<LOGN, LOGE>), dim3((unsigned)slots), dim3(G::T), G::LDS_USED, ctx->stream, x, ir, ip,
                            q, a, ap, b, bp, (u32)batch, ctx->ntt_clear_viol, ctx->ntt_clear_viol ? ctx->ntt_hint_word : nullptr);
         return (int)hipGetLastError();
@@ -840,23 +831,13 @@ static int launch_inv(hexl_ctx* ctx, u64* x, size_t batch, const u64* ir, const 
 template <int LOGN, int LOGE, int LAZY, bool SEMI = false>
 static int launch_fwd_x(hexl_ctx* ctx, u64* x, size_t batch, const u64* roots, const u64* precon, u64 q, NttPrep pr) {
     using G = Geom<LOGN, LOGE>;
-    static PerDeviceOnce once;
-    if (int rc = once.run(ctx->device, [] {
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ntt_fwd_x<LOGN, LOGE, LAZY, SEMI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_USED));
-            return 0;
-        }))
-        return rc;
+    if (int rc = hx_lds_optin<k_ntt_fwd_x<LOGN, LOGE, LAZY, SEMI>>(ctx->device, G::LDS_USED)) return rc;
     // persistent workgroups with input prefetch wherever 2 E more registers fit (not N = 32768: 64 data registers at
     // 1024 threads) and the batch fills the chip more than once; HEXL_NTT_PERSIST=0 keeps one workgroup per polynomial
-    static const int persist = [] { const char* e = getenv("HEXL_NTT_PERSIST"); return e ? atoi(e) : 1; }();
+    const bool persist = persist_enabled();
     const size_t slots = size_t(ctx->num_cu) * (G::LDS_USED > 80 * 1024 ? 1 : (160 * 1024) / G::LDS_USED);
     if (persist && !G::HALF_ONLY && batch > slots) {
-        static PerDeviceOnce once_p;
-        if (int rc = once_p.run(ctx->device, [] {
-                HX_CHECK(hipFuncSetAttribute((const void*)k_ntt_fwd_p<LOGN, LOGE, LAZY, SEMI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(G::LDS_USED + RangeVote::BYTES)));
-                return 0;
-            }))
-            return rc;
+        if (int rc = hx_lds_optin<k_ntt_fwd_p<LOGN, LOGE, LAZY, SEMI>>(ctx->device, G::LDS_USED + RangeVote::BYTES)) return rc;
         if (int rc = launch_prepare(ctx, roots, precon, q, pr)) return rc;
         hipLaunchKernelGGL((k_ntt_fwd_p<LOGN, LOGE, LAZY, SEMI>), dim3((unsigned)slots), dim3(G::T), G::LDS_USED + RangeVote::BYTES, ctx->stream, x,
                            roots, precon, q, pr, (u32)batch, NttHint{ctx->ntt_hint_word, ctx->ntt_hint_tag});
@@ -872,28 +853,13 @@ template <int LOGN, int LOGE, int LAZY>
 static int launch_inv_x(hexl_ctx* ctx, u64* x, size_t batch, const u64* ir, const u64* ip, u64 q, u64 a, u64 ap, u64 b,
                         u64 bp, NttPrep pr, hxf::InvScale sc) {
     using G = Geom<LOGN, LOGE>;
-    static PerDeviceOnce once;
-    if (int rc = once.run(ctx->device, [] {
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ntt_inv_x<LOGN, LOGE, LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_USED));
-            return 0;
-        }))
-        return rc;
-    static const int persist = [] { const char* e = getenv("HEXL_NTT_PERSIST"); return e ? atoi(e) : 1; }();
+    if (int rc = hx_lds_optin<k_ntt_inv_x<LOGN, LOGE, LAZY>>(ctx->device, G::LDS_USED)) return rc;
+    const bool persist = persist_enabled();
     const size_t slots = size_t(ctx->num_cu) * (G::LDS_USED > 80 * 1024 ? 1 : (160 * 1024) / G::LDS_USED);
     if (persist && !G::HALF_ONLY && batch > slots) {
-        static PerDeviceOnce once_p;
-        if (int rc = once_p.run(ctx->device, [] {
-                HX_CHECK(hipFuncSetAttribute((const void*)k_ntt_inv_p<LOGN, LOGE, LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(G::LDS_USED + RangeVote::BYTES)));
-                return 0;
-            }))
-            return rc;
+        if (int rc = hx_lds_optin<k_ntt_inv_p<LOGN, LOGE, LAZY>>(ctx->device, G::LDS_USED + RangeVote::BYTES)) return rc;
         if constexpr (ntt_inv_redo<LOGN, LAZY>) {                                // fallback in a launch of its own behind the fast kernel
-            static PerDeviceOnce once_r;
-            if (int rc = once_r.run(ctx->device, [] {
-                    HX_CHECK(hipFuncSetAttribute((const void*)k_ntt_redo_inv<LOGN, LOGE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_USED));
-                    return 0;
-                }))
-                return rc;
+            if (int rc = hx_lds_optin<k_ntt_redo_inv<LOGN, LOGE>>(ctx->device, G::LDS_USED)) return rc;
             if (int rc = reserve_redo(ctx, batch, &pr)) return rc;               // (the preparation zeroes the counter)
         }
         if (int rc = launch_prepare(ctx, ir, ip, q, pr)) return rc;
@@ -914,13 +880,8 @@ template <int LAZY, bool SEMI = false>
 static int launch_fwd_h(hexl_ctx* ctx, u64* x, size_t batch, const u64* roots, const u64* precon, u64 q, NttPrep pr) {
     using G = Geom<14, 4>;
     constexpr size_t LDS = G::LDS_USED + RangeVote::BYTES, LDS_INT = Geom<15, 5>::LDS_USED;
-    static PerDeviceOnce once;
-    if (int rc = once.run(ctx->device, [] {
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ntt_fwd_h<LAZY, SEMI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ntt_redo_fwd<15, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_INT));
-            return 0;
-        }))
-        return rc;
+    if (int rc = hx_lds_optin<k_ntt_fwd_h<LAZY, SEMI>>(ctx->device, LDS)) return rc;
+    if (int rc = hx_lds_optin<k_ntt_redo_fwd<15, 5>>(ctx->device, LDS_INT)) return rc;
     if (int rc = reserve_redo(ctx, batch, &pr)) return rc;
     if (int rc = launch_prepare(ctx, roots, precon, q, pr)) return rc;           // (also zeroes the redo counter)
     const unsigned grid = (unsigned)(batch < (size_t)ctx->num_cu ? batch : (size_t)ctx->num_cu);
@@ -934,13 +895,8 @@ static int launch_inv_h(hexl_ctx* ctx, u64* x, size_t batch, const u64* ir, cons
                         hxf::InvScale sc) {
     using G = Geom<14, 4>;
     constexpr size_t LDS = G::LDS_USED + RangeVote::BYTES, LDS_INT = Geom<15, 5>::LDS_USED;
-    static PerDeviceOnce once;
-    if (int rc = once.run(ctx->device, [] {
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ntt_inv_h<LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-            HX_CHECK(hipFuncSetAttribute((const void*)k_ntt_redo_inv<15, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_INT));
-            return 0;
-        }))
-        return rc;
+    if (int rc = hx_lds_optin<k_ntt_inv_h<LAZY>>(ctx->device, LDS)) return rc;
+    if (int rc = hx_lds_optin<k_ntt_redo_inv<15, 5>>(ctx->device, LDS_INT)) return rc;
     if (int rc = reserve_redo(ctx, batch, &pr)) return rc;
     if (int rc = launch_prepare(ctx, ir, ip, q, pr)) return rc;
     const unsigned grid = (unsigned)(batch < (size_t)ctx->num_cu ? batch : (size_t)ctx->num_cu);
@@ -955,7 +911,7 @@ static int launch_inv_h(hexl_ctx* ctx, u64* x, size_t batch, const u64* ir, cons
 // N = 2048 (+12 %); N = 4096 lost 16 % both ways, the inverse at 8192 11 % (tools/ntt_n_sweep.py).
 // HEXL_NTT_E16 = bit mask over logn - 11 forces the choice for both directions.
 static bool small_e16(int logn, bool fwd) {
-    static const int mask = [] { const char* e = getenv("HEXL_NTT_E16"); return e ? atoi(e) : -1; }();
+    static const int mask = (int)hx_knob("HEXL_NTT_E16", -1);
     const int m = mask >= 0 ? mask : (fwd ? 0b101 : 0b001);
     return (m >> (logn - 11)) & 1;
 }
@@ -1061,9 +1017,8 @@ int hx_launch_ntt_inv(hexl_ctx* ctx, u64* x, size_t batch, const u64* ir, const 
         if (rc) return rc;
         if (hinted) ctx->ntt_clear_viol = pr.viol;
         const double pd = (double)q;
-        auto centre = [&](u64 v) { return v > q / 2 ? (double)v - pd : (double)v; };
         hxf::InvScale sc;
-        sc.n = centre(a); sc.n_p = sc.n / pd; sc.nw = centre(b); sc.nw_p = sc.nw / pd;
+        sc.n = hx_centre(a, q); sc.n_p = sc.n / pd; sc.nw = hx_centre(b, q); sc.nw_p = sc.nw / pd;
         if (!hinted)
             return pd <= hxf::LAZY_MAX_MODULUS ? dispatch_inv_x<3>(logn, ctx, x, batch, ir, ip, q, a, ap, b, bp, pr, sc)
                                                : dispatch_inv_x<0>(logn, ctx, x, batch, ir, ip, q, a, ap, b, bp, pr, sc);

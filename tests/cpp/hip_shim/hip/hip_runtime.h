@@ -1,4 +1,4 @@
-// hip_runtime.h -- TEST INFRASTRUCTURE, CPU only: just enough of the HIP host API for hexl-fpga_amd/csrc/capi.hip (the C-ABI's host half:
+// hip_runtime.h -- TEST INFRASTRUCTURE, CPU only: just enough of the HIP host API for hexl-fpga_amd/csrc/host_staging.hip and capi.hip (the C-ABI's host half:
 // staging pipeline, copy-thread pool, plan set-up) to compile with g++ and RUN without a GPU. "Device" memory is host memory, copies are
 // memcpy on the calling thread, streams and events are ordering no-ops (everything is synchronous), the kernel launchers are the stubs
 // of tests/cpp/stage_model_stubs.cpp. What is left is exactly the HOST side of the host-pointer entry points -- packing, unpacking /

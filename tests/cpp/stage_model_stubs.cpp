@@ -1,5 +1,5 @@
 // stage_model_stubs.cpp -- TEST INFRASTRUCTURE (CPU staging model, see tests/cpp/hip_shim/hip/hip_runtime.h): the kernel launchers behind
-// capi.hip, as stubs. Nothing is computed (results are NOT keyswitch outputs: the model times the host side only). Device time is modelled
+// capi.hip and host_staging.hip, as stubs. Nothing is computed (results are NOT keyswitch outputs: the model times the host side only). Device time is modelled
 // as a sleep of HEXL_MODEL_DEVICE_US_PER_KS microseconds per keyswitch (default 0: an infinitely fast device, i.e. the HOST ceiling) on the
 // launching thread -- the runner thread of that device, which in the product waits for its stream at the same place.
 #include <chrono>

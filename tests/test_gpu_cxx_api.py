@@ -20,7 +20,7 @@ def test_cxx_api_driver():
 
 def test_cxx_api_driver_tiny_staging_slabs():
     """same driver with 1 MiB staging slabs: every batch becomes many sub-batches with a ragged tail, exercising the
-    double-buffered H2D / kernel / D2H pipeline of the host-pointer entry points (capi.hip run_pipeline)"""
+    double-buffered H2D / kernel / D2H pipeline of the host-pointer entry points (host_staging.hip run_pipeline)"""
     import os
     exe = ROOT / "tests" / "cpp" / "test_cxx_api"
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=900,

@@ -171,7 +171,7 @@ def test_device_pointers_dyadic(hx, ctx, dev, orc):
 def test_lone_keyswitch_through_the_host_entry_point(env):
     """hexl_keyswitch_host at the SEAL bridge's worksize 1 (fpga_context.h:13-16). Round 5: the quarter-transform kernels read t_target from
     and write their output to PINNED HOST memory themselves, publish every quarter limb, and the host adds limb by limb while the rest is in
-    flight (capi.hip keyswitch_host_lone); HEXL_HOST_ZERO_COPY=0 keeps the staged route. Same bits as the oracle either way: repeated calls
+    flight (host_staging.hip keyswitch_host_lone); HEXL_HOST_ZERO_COPY=0 keeps the staged route. Same bits as the oracle either way: repeated calls
     (the pinned slabs and completion words are reused), accumulation into the caller's array, two and three objects per call, objects that
     ALIAS one result array (added in order), the 52-bit chain and bridge-seal's mixed one, and L = 7."""
     import os

@@ -1,6 +1,6 @@
 """CPU: the host side of NUM_DEV = 1 ... 8 (the reference's DevicePool of NUM_DEV runners, host/src/fpga.cpp:1646-1673).
 
-The REAL host half of the C-ABI (hexl-fpga_amd/csrc/capi.hip: staging pipeline, process-wide copy-thread pool, per-runner unpack lane) is
+The REAL host half of the C-ABI (hexl-fpga_amd/csrc/host_staging.hip: staging pipeline, process-wide copy-thread pool, per-runner unpack lane) is
 compiled with g++ against a CPU shim of the HIP host API (tests/cpp/hip_shim/: device memory = host memory, copy-engine transfers cost
 nothing, streams / events are no-ops) and stub launchers (tests/cpp/stage_model_stubs.cpp: nothing computed, device time = 0 or a sleep),
 under the REAL hexl_fpga_api.cpp -- so what runs is exactly the host work of the host-pointer entry points: runner threads, window

@@ -37,7 +37,7 @@ def kernels(obj):
             continue
         ins = line.split("//")[0].strip()
         ins = re.sub(r"<[^>]*>", "", ins)                 # symbolic branch targets
-        if ins:
+        if ins and ins != "...":                          # (objdump's mark for the zero padding behind a section's last function: layout, not code)
             body.append(ins)
     if name is not None:
         out[name] = body
