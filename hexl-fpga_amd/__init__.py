@@ -55,6 +55,9 @@ C_ABI = {
     "hexl_apply_galois": [_vp, _vp, _vp, _sz, _u64, _u64],
     "hexl_rescale": [_vp, _vp, _vp, _sz, _u64, _u64],
     "hexl_rotate": [_vp, _vp, _vp, _sz, _u64],
+    "hexl_rns_ntt_fwd": [_vp, _vp, _vp, _sz, _u64],
+    "hexl_rns_ntt_inv": [_vp, _vp, _vp, _sz, _u64],
+    "hexl_multiply_plain": [_vp, _vp, _vp, _vp, _sz, _u64, _u64, _sz, _i],
     "hexl_ks_scratch_bytes": [_vp, _sz],
     "hexl_ntt_fwd_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64],
     "hexl_ntt_inv_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64, _u64, _u64],
@@ -229,6 +232,21 @@ class KeySwitchPlan:
     def rotate(self, out, ct, batch: int, g: int):
         """out[batch][2][L][n] = (sigma_g(c0), 0) + KeySwitch(sigma_g(c1)); the plan's keys switch from s(X^g) to s"""
         _check(lib().hexl_rotate(self.h, _ptr(out), _ptr(ct), batch, g), "hexl_rotate")
+
+    def rns_ntt_fwd(self, out, inp, count: int, n_limbs: int):
+        """out[count][n_limbs][n] = negacyclic NTT of inp, polynomial (c, i) modulo the plan's q_i (coefficients in natural order in,
+        the transforms' bit-reversed order out); out may be inp; moduli < 2^52, 1 <= n_limbs <= K, no keys needed"""
+        _check(lib().hexl_rns_ntt_fwd(self.h, _ptr(out), _ptr(inp), count, n_limbs), "hexl_rns_ntt_fwd")
+
+    def rns_ntt_inv(self, out, inp, count: int, n_limbs: int):
+        """the inverse of rns_ntt_fwd, n^-1 included"""
+        _check(lib().hexl_rns_ntt_inv(self.h, _ptr(out), _ptr(inp), count, n_limbs), "hexl_rns_ntt_inv")
+
+    def multiply_plain(self, out, ct, pt, batch: int, n_components: int, n_limbs: int, pt_batch: int, accumulate: bool = False):
+        """out[batch][n_components][n_limbs][n] = (out +, if accumulate) ct * pt[pt_batch][n_limbs][n] mod q_i, word by word in NTT
+        form; pt_batch = 1 or batch; out may be ct unless accumulating"""
+        _check(lib().hexl_multiply_plain(self.h, _ptr(out), _ptr(ct), _ptr(pt), batch, n_components, n_limbs, pt_batch,
+                                         1 if accumulate else 0), "hexl_multiply_plain")
 
     def keyswitch_host(self, results, t_targets):
         n = len(results)

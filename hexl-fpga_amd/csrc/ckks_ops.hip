@@ -253,17 +253,13 @@ int hx_launch_rotate(hexl_ks_plan* p, u64* d_out, const u64* d_ct, size_t batch,
 // ---- entry points of include/hexl_mi355x.h. They live here rather than in capi.hip: the CPU staging model (tests/cpp) compiles
 // capi.hip and host_staging.hip against stubs of the launchers those two call, and needs none for these. ----
 static bool ring_dimension_ok(u64 n) { return n >= 1024 && n <= 32768 && !(n & (n - 1)); }
-// [a, a + abytes) and [b, b + bbytes) share a byte
-static bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
-    return (const char*)a < (const char*)b + bbytes && (const char*)b < (const char*)a + abytes;
-}
 static bool galois_elt_ok(u64 g, u64 n) { return (g & 1) && g < 2 * n; }
 
 extern "C" int hexl_apply_galois(hexl_ctx* c, uint64_t* d_out, const uint64_t* d_in, size_t count, uint64_t n, uint64_t g) {
     if (!c || !d_out || !d_in || !ring_dimension_ok(n) || !galois_elt_ok(g, n)) return HEXL_E_BADARG;
     if (count > (SIZE_MAX / sizeof(u64)) / n) return HEXL_E_BADARG;
     const size_t bytes = count * n * sizeof(u64);
-    if (ranges_overlap(d_out, bytes, d_in, bytes)) return HEXL_E_BADARG;    // a permutation cannot run in place
+    if (hx_ranges_overlap(d_out, bytes, d_in, bytes)) return HEXL_E_BADARG;    // a permutation cannot run in place
     if (!count) return 0;
     u32 logn = 0;
     while ((1ULL << logn) < n) ++logn;
@@ -277,7 +273,7 @@ extern "C" int hexl_rescale(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_
     if (n_limbs < 2 || n_limbs > p->K - 1 || n_components < 1 || n_components > 3) return HEXL_E_BADARG;
     const size_t per = size_t(n_components) * p->n * sizeof(u64);
     if (batch > SIZE_MAX / (per * n_limbs)) return HEXL_E_BADARG;
-    if (ranges_overlap(d_out, batch * per * (n_limbs - 1), d_in, batch * per * n_limbs)) return HEXL_E_BADARG;
+    if (hx_ranges_overlap(d_out, batch * per * (n_limbs - 1), d_in, batch * per * n_limbs)) return HEXL_E_BADARG;
     HX_CHECK(hipSetDevice(p->ctx->device));
     return hx_launch_rescale(p, d_out, d_in, batch, (u32)n_limbs, (u32)n_components);
 }
@@ -286,7 +282,7 @@ extern "C" int hexl_rotate(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_c
     if (!p || !d_out || !d_ct || !galois_elt_ok(g, p->n)) return HEXL_E_BADARG;
     const size_t per = 2 * size_t(p->L) * p->n * sizeof(u64);
     if (batch > SIZE_MAX / per) return HEXL_E_BADARG;
-    if (ranges_overlap(d_out, batch * per, d_ct, batch * per)) return HEXL_E_BADARG;   // component 1 of d_out is zeroed before the keyswitch
+    if (hx_ranges_overlap(d_out, batch * per, d_ct, batch * per)) return HEXL_E_BADARG;   // component 1 of d_out is zeroed before the keyswitch
     if (!p->have_keys) return HEXL_E_NOKEYS;
     HX_CHECK(hipSetDevice(p->ctx->device));
     return hx_launch_rotate(p, d_out, d_ct, batch, (u32)g);

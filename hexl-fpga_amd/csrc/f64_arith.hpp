@@ -97,6 +97,19 @@ HX_HD double rs_down(double c, double w, double qlinv, double qlinv_p, const Mod
     return lift(reduce(mul_shoup(reduce(c, m) - w, qlinv, qlinv_p, m), m), m);
 }
 
+// ---- the scalar chains of the plaintext multiply (rns_ops.hip k_pt_mul), here so that tests/cpp/pt_mul_selftest.cpp replays the
+// kernel's own source against 128-bit integers ------------------------------------------------------------------------------------
+// c * t mod p, centred: c, t canonical words of one limb as doubles (0 <= . < p < 2^52, exact). reduce brings both to |.| <= p/2 + 2,
+// the operand range mul_mod is bounded for: |product| <= 0.7p. lift itself would take that (it needs floor(x/p) = -1 for x < 0 and 0
+// for x >= 0, i.e. |x| < p), but the accumulate form adds a word of [0, p) on top, so the product is range-reduced here once for
+// both: |result| <= p/2 + 2.
+HX_HD double pt_mul_centred(double c, double t, const Mod m) { return reduce(mul_mod(reduce(c, m), reduce(t, m), m), m); }
+// out = c * t mod p, canonical
+HX_HD double pt_mul(double c, double t, const Mod m) { return lift(pt_mul_centred(c, t, m), m); }
+// out = (prev + c * t) mod p, canonical: prev the canonical word already there. -p/2 - 2 <= product + prev < 1.5p + 2 < 2^53, so the
+// sum is exact and inside reduce's domain.
+HX_HD double pt_mul_acc(double c, double t, double prev, const Mod m) { return lift(reduce(pt_mul_centred(c, t, m) + prev, m), m); }
+
 // The STRICT butterflies (every value reduced after every operation) leave room above 2^52: the largest intermediate is the
 // inverse butterfly's |h - k p| <= (1.31 + 0.22) p for |d| = |X - Y| <= p + 4 (quotient from the product: three roundings of a
 // value near p/2, ulp 1/2), the forward's |X + t| <= 1.4 p, all below 2^53 up to p ~ 2^52.39. The standalone _NTT / _INTT fast

@@ -209,6 +209,11 @@ int hx_launch_multiply_relinearize(hexl_ks_plan*, u64* d_out, const u64* d_a, co
 int hx_launch_galois(hexl_ctx*, u64* d_out, const u64* d_in, size_t count, u32 logn, u32 g);
 int hx_launch_rescale(hexl_ks_plan*, u64* d_out, const u64* d_in, size_t batch, u32 n_limbs, u32 n_components);
 int hx_launch_rotate(hexl_ks_plan*, u64* d_out, const u64* d_ct, size_t batch, u32 g);
+// plan-driven RNS transforms and the plaintext multiply (rns_ops.hip); arguments checked by their entry points (hexl_rns_ntt_fwd,
+// hexl_rns_ntt_inv, hexl_multiply_plain)
+int hx_launch_rns_ntt(hexl_ks_plan*, u64* d_out, const u64* d_in, size_t count, u32 n_limbs, bool inverse);
+int hx_launch_multiply_plain(hexl_ks_plan*, u64* d_out, const u64* d_ct, const u64* d_pt, size_t batch, u32 n_components, u32 n_limbs,
+                             bool per_instance, bool accumulate);
 u32 hx_ks_x_loge();
 // index of coefficient held in register r of thread tid after a forward transform ("B layout")
 u32 hx_idxB(u32 logn, u32 r, u32 tid);
@@ -223,6 +228,10 @@ static inline unsigned long long hx_tiermap(const hexl_ks_plan* p) {
     unsigned long long m = 0;
     for (u32 i = 0; i < p->K; ++i) m |= (unsigned long long)(p->tier[i] & 15u) << (4 * i);
     return m;
+}
+// [a, a + abytes) and [b, b + bbytes) share a byte
+static inline bool hx_ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
+    return (const char*)a < (const char*)b + bbytes && (const char*)b < (const char*)a + abytes;
 }
 // instances of a batch that go into one scratch chunk
 static inline size_t hx_ks_chunk_of(const hexl_ks_plan* p, size_t batch) { return batch < hx_ks_chunk(p) ? batch : hx_ks_chunk(p); }

@@ -144,6 +144,29 @@ int hexl_rescale(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_in, size
  * even or >= 2n, or d_out overlapping d_ct. Device memory kept by the plan, grow-only, beside the keyswitch's scratch:
  * min(batch, chunk) x L x n words (sigma_g(c1) of one slice; 224 MiB at n = 16384, L = 7). */
 int hexl_rotate(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t galois_elt);
+/* Domain changes and the plaintext product for ciphertexts that live on the device: the ends of a flow (encode / encrypt need the
+ * forward transform, decrypt / decode the inverse) and the multiplier of a linear layer (rotate -> multiply_plain -> accumulate).
+ * All three are asynchronous on the context's stream, need no keys and keep no device memory in the plan. FP64 plans only (every
+ * modulus < 2^52) and n = 1024 ... 32768, as hexl_rescale; 1 <= n_limbs <= K: the moduli are the plan's first n_limbs, so a
+ * ciphertext after rescales passes its smaller n_limbs, and n_limbs = K takes key material through the special prime as well.
+ * Precondition: every input word is below its modulus. Every output word is canonical, in [0, q_i).
+ *
+ * RNS transforms: d_in, d_out [count][n_limbs][n], count = instances x components (a ciphertext batch passes batch * 2); polynomial
+ * (c, i) is transformed modulo q_i with the plan's own tables (derived, or the h_twiddles given to hexl_ks_plan_create) in one launch.
+ * Forward: negacyclic NTT, coefficients in natural order in, the transforms' bit-reversed order out -- the form every other entry
+ * point takes. Inverse: the reverse, n^-1 included. Bit-exact with hexl_ntt_fwd / hexl_ntt_inv on tables of the same root.
+ * d_out == d_in (in place) is allowed; any other overlap, a null pointer, n_limbs outside 1 ... K or a size that overflows:
+ * HEXL_E_BADARG. count == 0 returns 0. */
+int hexl_rns_ntt_fwd(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_in, size_t count, uint64_t n_limbs);
+int hexl_rns_ntt_inv(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_in, size_t count, uint64_t n_limbs);
+/* Plaintext multiply, everything in NTT form:
+ *   d_ct, d_out [batch][n_components][n_limbs][n], d_pt [pt_batch][n_limbs][n], pt_batch = 1 (one plaintext for every instance) or batch
+ *   out[b][k][i][j] = ct[b][k][i][j] * pt[b or 0][i][j] mod q_i, WRITTEN when accumulate == 0, else added to the word d_out holds
+ *   (itself below q_i) mod q_i.
+ * 1 <= n_components <= 3. d_out == d_ct is allowed when accumulate == 0; d_out must not overlap d_pt; every other overlap (d_out == d_ct
+ * with accumulate != 0 among them), another pt_batch or a size that overflows: HEXL_E_BADARG. */
+int hexl_multiply_plain(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_ct, const uint64_t* d_pt, size_t batch,
+                        uint64_t n_components, uint64_t n_limbs, size_t pt_batch, int accumulate);
 /* Arithmetic tier per limb (introspection for logs and tests): tiers[i], i < key_modulus_size, = the forward transforms' range-
  * reduction period modulo q_i on the FP64 path -- 12 / 6 / 3 for q_i <= 2^49 / 2^50 / 2^51 (1 + 2^-7), 0 = every value reduced after
  * every operation (q_i up to 2^52); -1 for every limb of a plan on the integer kernels (a modulus >= 2^52). Every transform runs modulo

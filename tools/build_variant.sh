@@ -7,7 +7,7 @@ NAME=$1; shift
 R=$(cd "$(dirname "$0")/.." && pwd); C=$R/hexl-fpga_amd/csrc; O=$R/hexl-fpga_amd/lib_var/$NAME; L=$R/hexl-fpga_amd/lib
 mkdir -p $O
 OBJS=""
-for f in ntt dyadic keyswitch keyswitch_f64 keyswitch_lat keyswitch_x ckks_ops capi host_staging; do
+for f in ntt dyadic keyswitch keyswitch_f64 keyswitch_lat keyswitch_x ckks_ops rns_ops capi host_staging; do
   if [[ " ${VAR_FILES:-keyswitch_x} " == *" $f "* ]]; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -ffp-contract=off "$@" -c $C/$f.hip -o $O/$f.o
     OBJS="$OBJS $O/$f.o"
