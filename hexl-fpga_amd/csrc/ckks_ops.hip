@@ -86,7 +86,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_rs_down(RsArgs a) {
 #pragma unroll
             for (int r = 0; r < G::E; ++r) craw[r] = (ci + G::idxB(r, 0))[tB];
         } else {                                                   // c_i requested behind the cross-wave re-deal
-            W::template forward<true, true>(v, ldsd, tid, tb, tb + G::N, m, [&] {
+            W::template forward<true, true>(v, ldsd, tid, tb, tb + G::N, m, 0u, [&] {
 #pragma unroll
                 for (int r = 0; r < G::E; ++r) craw[r] = (ci + G::idxB(r, 0))[tB];
             });

@@ -74,6 +74,13 @@ constexpr int QLOGN = 14, QLOGM = 12, QLOGE = 4;
 using GQ = Geom<QLOGM, QLOGE>;                                   // 256 threads x 16 coefficients, three full passes
 constexpr int QM = 1 << QLOGM;
 
+// The stage loops' schedules of the quarter transforms (ntt_core_f64.hpp): no forward stage is the transform's last for the reduction
+// schedule; the inverse reads no w/p table, and only inverse_finish (LAST_) runs the stage that carries n^-1.
+template <int LAZY_, bool UNI_>
+struct QuarterFwd : FwdSched { static constexpr int LAZY = LAZY_; static constexpr bool UNI = UNI_; };
+template <int LAZY_, bool UNI_, bool LAST_ = false>
+struct QuarterInv : InvSched { static constexpr int LAZY = LAZY_; static constexpr bool UNI = UNI_, NOWP = true, LAST = LAST_; };
+
 // twelve stages of a 2^14-point transform on quarter `q`: stage numbers and twiddle group indices are the FULL transform's
 // (forward: global stages 3..14, group index = q on top of the local one; inverse: global stages 1..12)
 template <int LAZY>
@@ -89,12 +96,12 @@ struct WgSubNtt {
             constexpr int LO = QLOGM - (PASS + 1) * QLOGE;
             const u32 Gl = (PASS == 0) ? 0u : (LO >= 6 ? u32(__builtin_amdgcn_readfirstlane(u32(tid) >> LO)) : (u32(tid) >> LO));
             const u32 Gg = (q << (S0L - 1)) | Gl;
-            fwd_stages_f64<E, 0, QLOGE, S0L + 2, 0, LAZY, (PASS == 0 || LO >= 6)>(v, Gg, w, w, m);
+            fwd_stages_f64<E, 0, QLOGE, S0L + 2, QuarterFwd<LAZY, (PASS == 0 || LO >= 6)>>(v, Gg, w, w, m);
             redeal_pass<GQ, LO, QLOGE, true, true, (PASS + 1 == P - 1)>(v, lds, tid);
             fwd_pass<PASS + 1>(v, lds, tid, q, w, m);
         } else {
             const u32 Gg = (q << (S0L - 1)) | u32(GQ::grpB(0, tid));
-            fwd_stages_f64<E, 0, QLOGE, S0L + 2, 0, LAZY, false>(v, Gg, w, w, m);
+            fwd_stages_f64<E, 0, QLOGE, S0L + 2, QuarterFwd<LAZY, false>>(v, Gg, w, w, m);
         }
     }
     // inverse: B order of the quarter in, A order out, centred-ish (|x| <= ~1.9p product outputs, see f64_arith.hpp), NOT scaled
@@ -104,14 +111,14 @@ struct WgSubNtt {
         if constexpr (PASS == 0) {
             // coefficient index >> (LO + K) with LO = 0, K = 4: the quarter on top of the lane's group
             const u32 Gg = (q << (QLOGM - QLOGE)) | u32(GQ::grpB(0, tid));
-            inv_stages_f64<E, 0, QLOGE, 0, QLOGN, false, LAZY, false, true>(v, Gg, iw, iw, m, none);
+            inv_stages_f64<E, 0, QLOGE, 0, QLOGN, QuarterInv<LAZY, false>>(v, Gg, iw, iw, m, none);
             inv_pass<1>(v, lds, tid, q, iw, m);
         } else if constexpr (PASS < P) {
             constexpr int LO = PASS * QLOGE;
             redeal_pass<GQ, LO, QLOGE, false, true, (PASS == 1)>(v, lds, tid);
             const u32 Gl = LO + QLOGE >= QLOGM ? 0u : (LO >= 6 ? u32(__builtin_amdgcn_readfirstlane(u32(tid) >> LO)) : (u32(tid) >> LO));
             const u32 Gg = (q << (QLOGM - LO - QLOGE)) | Gl;
-            inv_stages_f64<E, 0, QLOGE, LO, QLOGN, false, LAZY, (LO + QLOGE >= QLOGM || LO >= 6), true>(v, Gg, iw, iw, m, none);
+            inv_stages_f64<E, 0, QLOGE, LO, QLOGN, QuarterInv<LAZY, (LO + QLOGE >= QLOGM || LO >= 6)>>(v, Gg, iw, iw, m, none);
             inv_pass<PASS + 1>(v, lds, tid, q, iw, m);
         }
     }
@@ -130,13 +137,13 @@ __device__ __forceinline__ void b_to_a(double (&v)[GQ::E], double* lds, int tid)
 // transform's last pass does them. Outputs centred (|x| <= p/2 + 2).
 template <int LAZY>
 __device__ __forceinline__ void inverse_finish(double (&a)[4], const double* iw, const Mod m, const hxf::InvScale sc) {
-    inv_stages_f64<4, 0, 2, QLOGM, QLOGN, true, LAZY, true, true>(a, 0u, iw, iw, m, sc);
+    inv_stages_f64<4, 0, 2, QLOGM, QLOGN, QuarterInv<LAZY, true, true>>(a, 0u, iw, iw, m, sc);
 }
 // global forward stages 1 and 2 on the four quarters (inputs centred, |x| <= 0.625p): a[k] becomes quarter k's input to its
 // twelve remaining stages
 template <int LAZY>
 __device__ __forceinline__ void forward_start(double (&a)[4], const double* w, const Mod m) {
-    fwd_stages_f64<4, 0, 2, 1, 0, LAZY, true>(a, 0u, w, w, m);
+    fwd_stages_f64<4, 0, 2, 1, QuarterFwd<LAZY, true>>(a, 0u, w, w, m);
 }
 
 // the input-range flag of a launch whose flag word may be pinned host memory: every reporter stores the same 1 (no read-modify-write

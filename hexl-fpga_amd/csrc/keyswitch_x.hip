@@ -213,6 +213,24 @@ constexpr int KX_PF = KX_PF_DEPTH;
 #ifndef KX_ISCHED
 #define KX_ISCHED 1
 #endif
+// The transforms' options (ntt_core_f64.hpp NttOpt). Mod-up: the forward transforms whose tail goes to mac_fold (SKIP: canonical input
+// as it is); TOP_ = 1 in the N = 32768 kernels (one half of the transform per call) ...
+template <int LAZY, bool SKIP, int TOP_ = 0>
+struct KsxUpOpt : NttOpt {
+    static constexpr int PRE = KX_PRE, FSHIFT = SKIP ? 1 : 0, TOP = TOP_, XSD = KX_XSCHED ? 0 : -1;
+    static constexpr bool SEMIU = KX_SEMIU_ON(LAZY);
+};
+// ... the special limb's kernels, which run them and the inverse without the w/p table in one workgroup ...
+template <int LAZY, bool SKIP, int TOP_ = 0>
+struct KsxSpecialOpt : KsxUpOpt<LAZY, SKIP, TOP_> {
+    static constexpr bool NOWP = true, ISD = KX_ISCHED != 0;
+};
+// ... and mod-down: centred input, tail -> acc - w
+template <int LAZY, int TOP_ = 0>
+struct KsxDownOpt : NttOpt {
+    static constexpr int PRE = KX_PRE, TOP = TOP_, XSD = KX_XSCHED ? 1 : -1;
+    static constexpr bool SEMIU = KX_SEMIU_ON(LAZY);
+};
 // FOLD: the folded multiply-accumulate (f64_arith.hpp mac_fold; lazy tiers: accumulators <= 1.6p between rounds, strict tier <= 0.9p)
 // CSW: words between the two key components of a row (0: G::N; the N = 32768 kernels work on HALF rows of rows that are 2 G::N long)
 template <class G, bool FOLD = false, int CSW = 0>
@@ -316,8 +334,7 @@ __device__ __forceinline__ int in_pos(int r, int tid) { return G::KL <= 2 ? G::i
 template <class G, class W>
 __device__ __forceinline__ void ksx_special_down(double (&v)[G::E], double* __restrict__ dst, double* lds, int tid,
                                                  const double* ts, const KsModF64& msp, ReadersGate<G>& gate) {
-    W::template inverse<false, typename W::NoHook, false, ReadersGate<G>>(v, lds, tid, ts + 2 * G::N, ts + 3 * G::N, msp.m, msp.sc,
-                                                                         typename W::NoHook(), 0u, &gate);
+    W::template inverse<false, ReadersGate<G>>(v, lds, tid, ts + 2 * G::N, ts + 3 * G::N, msp.m, msp.sc, &gate);
 #pragma unroll
     for (int r = 0; r < G::E; ++r) {
         const double c = hxf::lift(v[r], msp.m);                   // canonical [0, q_sp)
@@ -332,7 +349,7 @@ __device__ __forceinline__ void ksx_special_down(double (&v)[G::E], double* __re
 template <int LOGN, int LOGE, int LAZY, bool FUSED = false>
 __global__ __launch_bounds__(1 << (LOGN - LOGE), KX_WAVES(LOGE)) void k_ksx_intt(KsArgsX a) {
     using G = Geom<LOGN, LOGE>;
-    using W = WgNttF64<LOGN, LOGE, LAZY, 0, 0, true, HX_FWD_PRIO, 0, false, -1, KX_ISCHED != 0>;            // inverse without the w/p table
+    using W = WgNttF64<LOGN, LOGE, LAZY, InvNoWpOpt<KX_ISCHED != 0>>;
     extern __shared__ __attribute__((aligned(16))) double ldsx[];
     const XcdWalk wk = xcd_walk(a.nb * a.nsel);
     if (wk.pos >= wk.end) return;
@@ -366,7 +383,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), KX_WAVES(LOGE)) void k_ksx_intt
         if constexpr (FUSED) {                                    // t_target[d] = a_1[d] . b_1[d]
             const size_t at = ((size_t(ib) * 2 + 1) * a.L + d) * G::N;
             load_product_to_B<G>(v, a.mul_a + at, a.mul_b + at, ldsx, tid, md.m);
-            W::template inverse<false, typename W::NoHook, false, ReadersGate<G>>(v, ldsx, tid, tb + 2 * G::N, tb + 3 * G::N, md.m, md.sc, typename W::NoHook(), 0u, &gate);
+            W::template inverse<false, ReadersGate<G>>(v, ldsx, tid, tb + 2 * G::N, tb + 3 * G::N, md.m, md.sc, &gate);
         } else if constexpr (G::KL <= 2) {
             // canonical words as they are: the first inverse stage takes X + Y < 2p and |X - Y| < p (f64_arith.hpp)
             const u64 qd = (u64)md.m.p;
@@ -379,10 +396,10 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE), KX_WAVES(LOGE)) void k_ksx_intt
 #pragma unroll
                 for (int r = 0; r < G::E; ++r) raw[r] = (pn + G::idxB(r, 0))[tB];
             };
-            W::template inverse<false, decltype(request_next), (KX_IPRE != 0), ReadersGate<G>>(v, ldsx, tid, tb + 2 * G::N, tb + 3 * G::N, md.m, md.sc, request_next, 0u, &gate);
+            W::template inverse<false, ReadersGate<G>, (KX_IPRE != 0)>(v, ldsx, tid, tb + 2 * G::N, tb + 3 * G::N, md.m, md.sc, &gate, 0u, request_next);
         } else {
             load_natural_to_B<G>(v, a.t_target + size_t(row) * G::N, ldsx, tid, md.m, bad);
-            W::template inverse<false, typename W::NoHook, false, ReadersGate<G>>(v, ldsx, tid, tb + 2 * G::N, tb + 3 * G::N, md.m, md.sc, typename W::NoHook(), 0u, &gate);
+            W::template inverse<false, ReadersGate<G>>(v, ldsx, tid, tb + 2 * G::N, tb + 3 * G::N, md.m, md.sc, &gate);
         }
         double* cd = a.c + size_t(row) * G::N;
 #pragma unroll
@@ -398,7 +415,7 @@ template <int LOGN, int LOGE, int LAZY, bool SKIP = false>
 __global__ __launch_bounds__(1 << (LOGN - LOGE), KX_WAVES(LOGE)) void k_ksx_special(KsArgsX a) {
     using G = Geom<LOGN, LOGE>;
     static_assert(!SKIP || LAZY != 0, "SKIP is a lazy-kernel variant");
-    using W = WgNttF64<LOGN, LOGE, LAZY, KX_PRE, SKIP ? 1 : 0, true, HX_FWD_PRIO, 0, KX_SEMIU_ON(LAZY), KX_XSCHED ? 0 : -1, KX_ISCHED != 0>;   // forward output -> mac_fold
+    using W = WgNttF64<LOGN, LOGE, LAZY, KsxSpecialOpt<LAZY, SKIP>>;
     extern __shared__ __attribute__((aligned(16))) double ldsx[];
     const u32 L = a.L;
     const u32 isp = a.K - 1;
@@ -487,7 +504,7 @@ __device__ __forceinline__ void ksx_down_round(double (&v)[G::E], const double (
         for (int r = 0; r < G::E; ++r) v[r] = hxf::reduce(v[r], m);
     }
     // (the w/p table -- read by the strict kernels' semi-strict passes only -- lies one FULL transform's worth of words behind w)
-    W::template forward<false, false>(v, lds, tid, tb, tb + (PRED ? 2 : 1) * G::N, m, typename W::NoHook(), typename W::NoHook(), top);   // |w| <= 2.14p
+    W::template forward<false, false>(v, lds, tid, tb, tb + (PRED ? 2 : 1) * G::N, m, top);   // |w| <= 2.14p
 #pragma unroll
     for (int r = 0; r < G::E; ++r) v[r] = hxf::mul_shoup(acc[r] - v[r], md.msf, md.msf_p, m);   // ms.hpp:70-82
     if constexpr (FUSED_K >= 0 && G::KL <= 2) {
@@ -559,8 +576,8 @@ template <int LOGN, int LOGE, int LAZY, bool FUSED = false, bool SKIP = false>
 __global__ __launch_bounds__(1 << (LOGN - LOGE), KX_WAVES(LOGE)) void k_ksx_main(KsArgsX a) {
     using G = Geom<LOGN, LOGE>;
     static_assert(!SKIP || LAZY != 0, "SKIP is a lazy-kernel variant");
-    using W = WgNttF64<LOGN, LOGE, LAZY, KX_PRE, 0, false, HX_FWD_PRIO, 0, KX_SEMIU_ON(LAZY), KX_XSCHED ? 1 : -1>;               // mod-down transforms: centred input, tail -> acc - w
-    using WU = WgNttF64<LOGN, LOGE, LAZY, KX_PRE, SKIP ? 1 : 0, false, HX_FWD_PRIO, 0, KX_SEMIU_ON(LAZY), KX_XSCHED ? 0 : -1>;   // mod-up transforms (SKIP: canonical c_d as it is), tail -> mac_fold
+    using W = WgNttF64<LOGN, LOGE, LAZY, KsxDownOpt<LAZY>>;
+    using WU = WgNttF64<LOGN, LOGE, LAZY, KsxUpOpt<LAZY, SKIP>>;
     // lazy kernels: the d == i term and the accumulators go un-reduced into the folded multiply-accumulate (f64_arith.hpp mac_fold,
     // |acc| <= 1.6p between rounds). The strict kernels (moduli up to 2^52) fold theirs too (transform output |x| <= p/2 + 2,
     // accumulators <= 0.9p between terms) and reduce the accumulators once in front of the mod-down, whose epilogue needs them centred
@@ -718,7 +735,7 @@ __device__ __forceinline__ void ksh_combine(double (&v)[G::E], const double* __r
 template <int LAZY, bool FUSED = false>
 __global__ __launch_bounds__(1024, 4) void k_ksh_intt(KsArgsX a) {
     using G = Geom<14, 4>;
-    using W = WgNttF64<14, 4, LAZY, 0, 0, true, HX_FWD_PRIO, 1>;
+    using W = WgNttF64<14, 4, LAZY, InvNoWpOpt<false, 1>>;
     constexpr u32 NF = 2 * G::N;
     extern __shared__ __attribute__((aligned(16))) double ldsx[];
     const XcdWalk wk = xcd_walk(a.nb * a.nsel * 2);
@@ -746,7 +763,7 @@ __global__ __launch_bounds__(1024, 4) void k_ksh_intt(KsArgsX a) {
 #pragma unroll
             for (int r = 0; r < G::E; ++r) v[r] = hxf::to_f64_lt52_checked((src + G::idxB(r, 0))[tB], qd, bad);    // canonical words as they are
         }
-        W::template inverse<false, typename W::NoHook, false, ReadersGate<G>>(v, ldsx, tid, tb + 2 * NF, tb + 3 * NF, md.m, md.sc, typename W::NoHook(), h, &gate);
+        W::template inverse<false, ReadersGate<G>>(v, ldsx, tid, tb + 2 * NF, tb + 3 * NF, md.m, md.sc, &gate, h);
         double* dst = a.csub + (size_t(row) * 2 + h) * G::N;
 #pragma unroll
         for (int r = 0; r < G::E; ++r) (dst + G::idxA(r, 0))[u32(tid)] = v[r];
@@ -767,7 +784,7 @@ __global__ __launch_bounds__(256) void k_ksh_finish(KsArgsX a, u32 rows) {
     const double* tb = a.tables + size_t(limb) * 4 * NF;
     const double* sub = (WHICH == 0 ? a.csub : a.ssub) + size_t(row) * NF;
     double x[2] = {sub[j], sub[H + j]};
-    inv_stages_f64<2, 0, 1, 14, 15, true, 3, true, true>(x, 0u, tb + 2 * NF, tb + 3 * NF, md.m, md.sc);
+    inv_stages_f64<2, 0, 1, 14, 15, HalvesLastInv>(x, 0u, tb + 2 * NF, tb + 3 * NF, md.m, md.sc);
     double* dst = (WHICH == 0 ? a.c : a.s) + size_t(row) * NF;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -779,7 +796,7 @@ __global__ __launch_bounds__(256) void k_ksh_finish(KsArgsX a, u32 rows) {
 template <int LAZY, bool SKIP>
 __global__ __launch_bounds__(1024, 4) void k_ksh_special(KsArgsX a) {
     using G = Geom<14, 4>;
-    using W = WgNttF64<14, 4, LAZY, KX_PRE, SKIP ? 1 : 0, true, HX_FWD_PRIO, 1, KX_SEMIU_ON(LAZY), KX_XSCHED ? 0 : -1>;
+    using W = WgNttF64<14, 4, LAZY, KsxSpecialOpt<LAZY, SKIP, 1>>;
     constexpr u32 NF = 2 * G::N;
     extern __shared__ __attribute__((aligned(16))) double ldsx[];
     const u32 L = a.L, isp = a.K - 1;
@@ -807,7 +824,7 @@ __global__ __launch_bounds__(1024, 4) void k_ksh_special(KsArgsX a) {
             ksh_combine<G, LAZY, SKIP, (SKIP ? 1 : 0), W::XS>(v, a.c + (size_t(b) * L + it) * NF + G::N, tid, ts, msp.m, h);
             const double* k0 = key_row<G>(a, it, L) + h * G::N;
             const u32 nd = it + 1 < L ? it + 1 : it;
-            W::template forward<false, false>(v, ldsx, tid, ts, ts + NF, msp.m, typename W::NoHook(), typename W::NoHook(), h);
+            W::template forward<false, false>(v, ldsx, tid, ts, ts + NF, msp.m, h);
             mac_keys<G, true, int(NF)>(acc0, acc1, v, k0, a.c + (size_t(b) * L + nd) * NF, tid, msp.m);
         }
 #pragma unroll
@@ -820,7 +837,7 @@ __global__ __launch_bounds__(1024, 4) void k_ksh_special(KsArgsX a) {
             asm volatile("" : "+s"(tsp));
             const double* ts = a.tables + tsp;
             double (&acc)[G::E] = k == 0 ? acc0 : acc1;
-            W::template inverse<false, typename W::NoHook, false, ReadersGate<G>>(acc, ldsx, tid, ts + 2 * NF, ts + 3 * NF, msp.m, msp.sc, typename W::NoHook(), h, &gate);
+            W::template inverse<false, ReadersGate<G>>(acc, ldsx, tid, ts + 2 * NF, ts + 3 * NF, msp.m, msp.sc, &gate, h);
             double* dst = a.ssub + ((size_t(b) * 2 + k) * 2 + h) * G::N;
 #pragma unroll
             for (int r = 0; r < G::E; ++r) (dst + G::idxA(r, 0))[u32(tid)] = acc[r];
@@ -831,8 +848,8 @@ __global__ __launch_bounds__(1024, 4) void k_ksh_special(KsArgsX a) {
 template <int LAZY, bool SKIP, bool FUSED = false>
 __global__ __launch_bounds__(1024, 4) void k_ksh_main(KsArgsX a) {
     using G = Geom<14, 4>;
-    using W = WgNttF64<14, 4, LAZY, KX_PRE, 0, false, HX_FWD_PRIO, 1, KX_SEMIU_ON(LAZY), KX_XSCHED ? 1 : -1>;                 // mod-down transforms: centred input
-    using WU = WgNttF64<14, 4, LAZY, KX_PRE, SKIP ? 1 : 0, false, HX_FWD_PRIO, 1, KX_SEMIU_ON(LAZY), KX_XSCHED ? 0 : -1>;     // mod-up transforms
+    using W = WgNttF64<14, 4, LAZY, KsxDownOpt<LAZY, 1>>;
+    using WU = WgNttF64<14, 4, LAZY, KsxUpOpt<LAZY, SKIP, 1>>;
     constexpr u32 NF = 2 * G::N;
     constexpr bool LAZYFOLD = LAZY != 0;
     extern __shared__ __attribute__((aligned(16))) double ldsx[];
@@ -871,7 +888,7 @@ __global__ __launch_bounds__(1024, 4) void k_ksh_main(KsArgsX a) {
         u32 nit = it + 1;
         if (nit == i) ++nit;
         const double* k0 = key_row<G>(a, it, i) + h * G::N;
-        WU::template forward<false, false>(v, ldsx, tid, tb, tb + NF, m, typename WU::NoHook(), typename WU::NoHook(), h);
+        WU::template forward<false, false>(v, ldsx, tid, tb, tb + NF, m, h);
         mac_keys<G, true, int(NF)>(acc0, acc1, v, k0, round_src(nit), tid, m);           // nit <= L: s'_0 follows the last c_d
         it = nit;
     }

@@ -46,6 +46,14 @@ using namespace hx;
 #endif
 // (the kernels' SEMI parameter: strict tier with the semi-strict butterflies in the WAVE-UNIFORM passes, ntt_core_f64.hpp SEMIU)
 
+// The standalone forward transforms (k_ntt_fwd_x, _p and _h differ in TOP only): the lazy tiers take canonical input as it is, on the X
+// schedule whose tail FINAL's range reduction finishes.
+template <int LOGN, int LAZY, bool SEMI, int TOP_ = 0>
+struct NttFwdOpt : NttOpt {
+    static constexpr int FSHIFT = LAZY != 0 ? 1 : 0, FPRIO = ntt_fwd_prio(LOGN), TOP = TOP_, XSD = NTT_XSCHED ? 0 : -1;
+    static constexpr bool SEMIU = SEMI;
+};
+
 // ---------------------------------------------------------------------------------------------
 // Exact-arithmetic fast path. The Harvey kernels above must be replayed op for op only where that is observable:
 // out-of-range data, improper tables (benchmarks pass random ones), moduli >= 2^52. When q < 2^52, the tables
@@ -167,24 +175,14 @@ __device__ __forceinline__ u64 fast_path_limit(u64 q, bool forward) {
 // canonical result word of a fast-path transform. The strict kernels also serve moduli in [2^52, STRICT_NTT_MAX_Q) (f64_arith.hpp),
 // whose residues need the conversion that does not assume 52 bits (`wide`, wave-uniform)
 // (one wave-uniform branch around the whole store loop, not one per word)
-template <int LAZY, class At>
-__device__ __forceinline__ void fast_path_store(const double (&f)[1 << 4], u64* px, const Mod m, u64 q, At at) {
+template <int LAZY, int E, class At>
+__device__ __forceinline__ void fast_path_store(const double (&f)[E], u64* px, const Mod m, u64 q, At at) {
     if (LAZY == 0 && q >= (1ull << 52)) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) px[at(r)] = hxf::from_f64_53(hxf::lift(f[r], m));
+        for (int r = 0; r < E; ++r) px[at(r)] = hxf::from_f64_53(hxf::lift(f[r], m));
     } else {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) px[at(r)] = hxf::from_f64(hxf::lift(f[r], m));
-    }
-}
-template <int LAZY, class At>
-__device__ __forceinline__ void fast_path_store(const double (&f)[1 << 5], u64* px, const Mod m, u64 q, At at) {
-    if (LAZY == 0 && q >= (1ull << 52)) {
-#pragma unroll
-        for (int r = 0; r < 32; ++r) px[at(r)] = hxf::from_f64_53(hxf::lift(f[r], m));
-    } else {
-#pragma unroll
-        for (int r = 0; r < 32; ++r) px[at(r)] = hxf::from_f64(hxf::lift(f[r], m));
+        for (int r = 0; r < E; ++r) px[at(r)] = hxf::from_f64(hxf::lift(f[r], m));
     }
 }
 template <int LAZY>
@@ -225,7 +223,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ntt_fwd_x(u64* __restric
     // The FP64 transform runs unconditionally; whether its preconditions held for this polynomial is voted on
     // afterwards (a barrier at the very end costs nothing, one before the transform would put all 16 waves back
     // in lockstep). The input is still intact in memory for the integer fallback.
-    WgNttF64<LOGN, LOGE, LAZY, 0, (LAZY != 0 ? 1 : 0), false, ntt_fwd_prio(LOGN), 0, SEMI, NTT_XSCHED ? 0 : -1>::template forward<true>(f, reinterpret_cast<double*>(lds), tid, w, wp, m);
+    WgNttF64<LOGN, LOGE, LAZY, NttFwdOpt<LOGN, LAZY, SEMI>>::template forward<true>(f, reinterpret_cast<double*>(lds), tid, w, wp, m);
     const bool slow = __syncthreads_or(out_of_range);
     if (!slow) {
         fast_path_store<LAZY>(f, px, m, q, [&](int r) { return G::idxB(r, tid); });
@@ -262,7 +260,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ntt_inv_x(u64* __restric
         out_of_range |= raw >= limit;
         f[r] = fast_path_input<LAZY>(raw, m);
     }
-    WgNttF64<LOGN, LOGE, LAZY, 0, 0, true, HX_FWD_PRIO, 0, false, -1, NTT_ISCHED != 0>::template inverse<true>(f, reinterpret_cast<double*>(lds), tid, w, wp, m, sc);   // no w/p table
+    WgNttF64<LOGN, LOGE, LAZY, InvNoWpOpt<NTT_ISCHED != 0>>::template inverse<true>(f, reinterpret_cast<double*>(lds), tid, w, wp, m, sc);   // no w/p table
     const bool slow = __syncthreads_or(out_of_range);                            // see k_ntt_fwd_x
     if (!slow) {
         fast_path_store<LAZY>(f, px, m, q, [&](int r) { return G::idxA(r, tid); });
@@ -366,7 +364,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ntt_fwd_p(u64* __restric
         const u64* pnx = x + size_t(pn) * G::N;
 #pragma unroll
         for (int r = 0; r < G::E; ++r) raw[r] = (pnx + G::idxA(r, 0))[u32(tid)];
-        WgNttF64<LOGN, LOGE, LAZY, 0, (LAZY != 0 ? 1 : 0), false, ntt_fwd_prio(LOGN), 0, SEMI, NTT_XSCHED ? 0 : -1>::template forward<false>(f, reinterpret_cast<double*>(lds), tid, w, wp, m);
+        WgNttF64<LOGN, LOGE, LAZY, NttFwdOpt<LOGN, LAZY, SEMI>>::template forward<false>(f, reinterpret_cast<double*>(lds), tid, w, wp, m);
         const bool slow = vote.result(tid);                                      // see k_ntt_fwd_x, RangeVote
         if (!slow) {
             fast_path_store<LAZY>(f, px, m, q, [&](int r) { return G::idxB(r, tid); });
@@ -435,7 +433,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ntt_inv_p(u64* __restric
         // (N = 32768 in one workgroup, HEXL_NTT_HALVES=0 only: the half-size exchanges bring barriers of their own except behind an inverse
         // transform's last round and in front of its first, wave-private, one -- the same inverse-after-inverse hole, closed with a barrier here)
         if constexpr (G::HALF_ONLY) __syncthreads();
-        WgNttF64<LOGN, LOGE, LAZY, 0, 0, true, HX_FWD_PRIO, 0, false, -1, NTT_ISCHED != 0>::template inverse<false, decltype(request_next), (NTT_IPRE != 0), ReadersGate<G>>(f, reinterpret_cast<double*>(lds), tid, w, wp, m, sc, request_next, 0u, &gate);   // no w/p table
+        WgNttF64<LOGN, LOGE, LAZY, InvNoWpOpt<NTT_ISCHED != 0>>::template inverse<false, ReadersGate<G>, (NTT_IPRE != 0)>(f, reinterpret_cast<double*>(lds), tid, w, wp, m, sc, &gate, 0u, request_next);   // no w/p table
         const bool slow = vote.result(tid);
         if (!slow) {
             fast_path_store<LAZY>(f, px, m, q, [&](int r) { return G::idxA(r, tid); });
@@ -465,8 +463,8 @@ template <int LAZY, bool SEMI = false>
 __global__ __launch_bounds__(1024) void k_ntt_fwd_h(u64* __restrict__ x, const u64* __restrict__ roots, const u64* __restrict__ precon,
                                                     u64 q, NttPrep prep, u32 batch, NttHint hint) {
     using G = Geom<14, 4>;
-    constexpr int FS = LAZY != 0 ? 1 : 0;
-    using W = WgNttF64<14, 4, LAZY, 0, FS, false, ntt_fwd_prio(14), 1, SEMI, NTT_XSCHED ? 0 : -1>;
+    using W = WgNttF64<14, 4, LAZY, NttFwdOpt<14, LAZY, SEMI, 1>>;
+    constexpr int FS = W::FSHIFT;
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
     const u64 limit = fast_path_limit<LAZY>(q, true);
     const Mod m{(double)q, 1.0 / (double)q};
@@ -502,7 +500,7 @@ __global__ __launch_bounds__(1024) void k_ntt_fwd_h(u64* __restrict__ x, const u
             }
         }
         vote.cast(out_of_range);
-        W::template forward<false>(u, reinterpret_cast<double*>(lds), tid, w, wp, m, typename W::NoHook(), typename W::NoHook(), 0u);
+        W::template forward<false>(u, reinterpret_cast<double*>(lds), tid, w, wp, m, 0u);
         if (vote.result(tid)) {                                                  // before anything is stored
             ntt_note_redo(prep, p, tid);
             continue;
@@ -513,7 +511,7 @@ __global__ __launch_bounds__(1024) void k_ntt_fwd_h(u64* __restrict__ x, const u
             for (int r = 0; r < G::E; ++r) to[G::idxB(r, tid)] = LAZY == 0 ? hxf::from_f64_53(hxf::lift(f[r], m)) : hxf::from_f64(hxf::lift(f[r], m));
         };
         store(u, px);
-        W::template forward<false>(v, reinterpret_cast<double*>(lds), tid, w, wp, m, typename W::NoHook(), typename W::NoHook(), 1u);
+        W::template forward<false>(v, reinterpret_cast<double*>(lds), tid, w, wp, m, 1u);
         store(v, px + G::N);
     }
 }
@@ -522,7 +520,7 @@ template <int LAZY>
 __global__ __launch_bounds__(1024) void k_ntt_inv_h(u64* __restrict__ x, const u64* __restrict__ iroots, const u64* __restrict__ iprecon,
                                                     u64 q, NttPrep prep, hxf::InvScale sc, u32 batch, NttHint hint) {
     using G = Geom<14, 4>;
-    using W = WgNttF64<14, 4, LAZY, 0, 0, true, HX_FWD_PRIO, 1>;      // no w/p table
+    using W = WgNttF64<14, 4, LAZY, InvNoWpOpt<false, 1>>;
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
     const u64 limit = fast_path_limit<LAZY>(q, false);
     const Mod m{(double)q, 1.0 / (double)q};
@@ -565,7 +563,7 @@ __global__ __launch_bounds__(1024) void k_ntt_inv_h(u64* __restrict__ x, const u
         }
         vote.cast(out_of_range);
         auto request_other_half = [&] { request(px + G::N); };
-        W::template inverse<false, decltype(request_other_half), false, ReadersGate<G>>(u, reinterpret_cast<double*>(lds), tid, w, wp, m, sc, request_other_half, 0u, &gate);
+        W::template inverse<false, ReadersGate<G>>(u, reinterpret_cast<double*>(lds), tid, w, wp, m, sc, &gate, 0u, request_other_half);
         bool slow = vote.result(tid);
         if (!slow) {
             out_of_range = false;
@@ -575,7 +573,7 @@ __global__ __launch_bounds__(1024) void k_ntt_inv_h(u64* __restrict__ x, const u
                 v[r] = fast_path_input<LAZY>(raw[r], m);
             }
             vote.cast(out_of_range);
-            W::template inverse<false, typename W::NoHook, false, ReadersGate<G>>(v, reinterpret_cast<double*>(lds), tid, w, wp, m, sc, typename W::NoHook(), 1u, &gate);
+            W::template inverse<false, ReadersGate<G>>(v, reinterpret_cast<double*>(lds), tid, w, wp, m, sc, &gate, 1u);
             slow = vote.result(tid);
         }
         if (slow) {
@@ -591,7 +589,7 @@ __global__ __launch_bounds__(1024) void k_ntt_inv_h(u64* __restrict__ x, const u
 #pragma unroll
         for (int r = 0; r < G::E; ++r) {
             double pr2[2] = {u[r], v[r]};
-            inv_stages_f64<2, 0, 1, 14, 15, true, 3, true, true>(pr2, 0u, w, wp, m, sc);
+            inv_stages_f64<2, 0, 1, 14, 15, HalvesLastInv>(pr2, 0u, w, wp, m, sc);
             const double c0 = hxf::lift(pr2[0], m), c1 = hxf::lift(pr2[1], m);
             (px + G::idxA(r, 0))[u32(tid)] = LAZY == 0 ? hxf::from_f64_53(c0) : hxf::from_f64(c0);
             (px + G::N + G::idxA(r, 0))[u32(tid)] = LAZY == 0 ? hxf::from_f64_53(c1) : hxf::from_f64(c1);

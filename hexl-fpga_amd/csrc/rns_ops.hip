@@ -18,6 +18,8 @@ struct RnsNttArgs {
     u32 count, n_limbs;
     unsigned long long tiermap; // LAZY = -1: nibble i = reduction period of limb i (keyswitch_f64.hip)
 };
+// the forward transform of centred residues: the X schedule whose tail FINAL's range reduction finishes
+struct RnsFwdOpt : NttOpt { static constexpr int XSD = 0; };
 
 // One transform per workgroup, LIMB-major: workgroup w works on limb w / count of instance w % count, so the workgroups resident at
 // any time share one limb's table (128 KiB at N = 16384) in every XCD's L2, where an instance-major
@@ -39,7 +41,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_rns_fwd(RnsNttArgs a) {
     // one transform per workgroup: FRESH; FINAL: |v| <= p/2 + 2. Lazy tiers run the X schedule for centred inputs (f64_arith.hpp), as the
     // standalone forward kernel does
     with_tier<LAZY, LOGN == 14>(a.tiermap, i, [&](auto T) {
-        WgNttF64<LOGN, LOGE, decltype(T)::value, 0, 0, false, HX_FWD_PRIO, 0, false, 0>::template forward<true, true>(v, ldsd, tid, tb, tb + G::N, m);
+        WgNttF64<LOGN, LOGE, decltype(T)::value, RnsFwdOpt>::template forward<true, true>(v, ldsd, tid, tb, tb + G::N, m);
     });
     u64* dst = a.out + poly;
     const u32 tB = u32(G::idxB(0, tid));
@@ -64,7 +66,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_rns_inv(RnsNttArgs a) {
     for (int r = 0; r < G::E; ++r) v[r] = hxf::reduce(hxf::to_f64((src + G::idxB(r, 0))[tB]), m);
     // without the w/p table and, in the lazy tiers, on the I schedule: the standalone inverse kernel's transform (ntt.hip)
     with_tier<LAZY, LOGN == 14>(a.tiermap, i, [&](auto T) {
-        WgNttF64<LOGN, LOGE, decltype(T)::value, 0, 0, true, HX_FWD_PRIO, 0, false, -1, true>::template inverse<true>(
+        WgNttF64<LOGN, LOGE, decltype(T)::value, InvNoWpOpt<true>>::template inverse<true>(
             v, ldsd, tid, tb + 2 * G::N, tb + 3 * G::N, m, md.sc);
     });
     u64* dst = a.out + poly;

@@ -11,6 +11,42 @@ static __device__ int g_mode_dummy;
 #include "ntt_core_f64.hpp"
 using namespace hx;
 
+// a full pass of a 2^LOGN_-point transform on the periodic schedule of tier LAZY_
+template <int LOGN_, int LAZY_>
+struct ProbePass : FwdSched { static constexpr int LOGN = LOGN_, LAZY = LAZY_; };
+
+template <class G, class FromIdx, class ToIdx>
+__device__ __forceinline__ void redeal_f64(double (&v)[G::E], double* lds, int tid, FromIdx from, ToIdx to) {
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) lds[G::pad(from(r, tid))] = v[r];
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) v[r] = lds[G::pad(to(r, tid))];
+    __syncthreads();
+}
+
+// every pass of a forward transform except the last (partial) one, ending with the re-deal into B layout; WgNttF64::fwd_last<0> finishes.
+// Lets a persistent kernel slot the next polynomial's loads between the two.
+template <int LOGN, int LOGE, int LAZY, int PASS>
+__device__ __forceinline__ void fwd_pass_until_last(double (&v)[1 << LOGE], double* lds, int tid, const double* w, const double* wp, const Mod m) {
+    using G = Geom<LOGN, LOGE>;
+    if constexpr (PASS < G::P - 1) {
+        constexpr int LO = LOGN - (PASS + 1) * LOGE;
+        // LO >= 6: every lane of a wave shares the group index -> scalar twiddle loads
+        const u32 Gp = (PASS == 0) ? 0u : (LO >= 6 ? u32(__builtin_amdgcn_readfirstlane(u32(tid) >> LO)) : (u32(tid) >> LO));
+        fwd_stages_f64<G::E, 0, LOGE, PASS * LOGE + 1, ProbePass<LOGN, LAZY>>(v, Gp, w, wp, m);
+        if constexpr (PASS + 1 < G::P - 1) {
+            constexpr int LO2 = LO - LOGE;
+            redeal_f64<G>(v, lds, tid, [](int r, int t) { return G::template idxF<LO>(r, t); },
+                          [](int r, int t) { return G::template idxF<LO2>(r, t); });
+        } else {
+            redeal_f64<G>(v, lds, tid, [](int r, int t) { return G::template idxF<LO>(r, t); },
+                          [](int r, int t) { return G::idxB(r, t); });
+        }
+        fwd_pass_until_last<LOGN, LOGE, LAZY, PASS + 1>(v, lds, tid, w, wp, m);
+    }
+}
+
 // MODE bits: 1 = no global load, 2 = twiddles from a 1-entry table (always L1/scalar hit), 4 = no LDS re-deal,
 //            8 = no global store (one guarded store keeps the values live)
 template <int LOGN, int LOGE, int MODE>
@@ -156,7 +192,7 @@ struct HalfX {
         if constexpr (PASS < G::P - 1) {
             constexpr int LO = LOGN - (PASS + 1) * LOGE;
             const u32 Gp = (PASS == 0) ? 0u : (u32(tid) >> LO);
-            fwd_stages_f64<E, 0, LOGE, PASS * LOGE + 1, LOGN, LAZY>(v, Gp, w, wp, m);
+            fwd_stages_f64<E, 0, LOGE, PASS * LOGE + 1, ProbePass<LOGN, LAZY>>(v, Gp, w, wp, m);
             if constexpr (PASS + 1 < G::P - 1) {
                 constexpr int LO2 = LO - LOGE;
                 redeal(v, lds, tid, [](int r, int t) { return G::template idxF<LO>(r, t); }, [](int r, int t) { return G::template idxF<LO2>(r, t); });
@@ -230,7 +266,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_persist(double* x, const
         const double* tw = w + opaque_zero();
         const double* twp = wp + opaque_zero();
         // all passes but the last
-        W::template fwd_pass_until_last<0>(v, ldsd, tid, tw, twp, m);
+        fwd_pass_until_last<LOGN, LOGE, LAZY, 0>(v, ldsd, tid, tw, twp, m);
         if (item + 1 < last) {
             const double* pn = x + size_t(item + 1) * G::N;
 #pragma unroll

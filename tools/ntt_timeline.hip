@@ -42,15 +42,15 @@ __global__ __launch_bounds__(1024) void k_timeline(double* x, const double* w, c
 #pragma unroll
     for (int r = 0; r < G::E; ++r) v[r] = hxf::reduce(px[G::idxA(r, tid)], m);
     STAMP(1, "s_waitcnt vmcnt(0)");
-    fwd_stages_f64<16, 0, 4, 1, 14, LAZY>(v, 0u, w, wp, m);
+    fwd_stages_f64<16, 0, 4, 1, WgFullPass<W, false>>(v, 0u, w, wp, m);
     STAMP(2, "");
     redeal_x<G, false, false>(v, ldsd, tid, [](int r, int t) { return G::idxF<10>(r, t); }, [](int r, int t) { return G::idxF<6>(r, t); });
     STAMP(3, "s_waitcnt lgkmcnt(0)");
-    fwd_stages_f64<16, 0, 4, 5, 14, LAZY>(v, u32(__builtin_amdgcn_readfirstlane(u32(tid) >> 6)), w, wp, m);
+    fwd_stages_f64<16, 0, 4, 5, WgFullPass<W, false>>(v, u32(__builtin_amdgcn_readfirstlane(u32(tid) >> 6)), w, wp, m);
     STAMP(4, "");
     redeal_x<G, true, false>(v, ldsd, tid, [](int r, int t) { return G::idxF<6>(r, t); }, [](int r, int t) { return G::idxF<2>(r, t); });
     STAMP(5, "s_waitcnt lgkmcnt(0)");
-    fwd_stages_f64<16, 0, 4, 9, 14, LAZY>(v, u32(tid) >> 2, w, wp, m);
+    fwd_stages_f64<16, 0, 4, 9, WgFullPass<W, false>>(v, u32(tid) >> 2, w, wp, m);
     STAMP(6, "");
     redeal_x<G, true, false>(v, ldsd, tid, [](int r, int t) { return G::idxF<2>(r, t); }, [](int r, int t) { return G::idxB(r, t); });
     STAMP(7, "s_waitcnt lgkmcnt(0)");
@@ -92,15 +92,15 @@ __global__ __launch_bounds__(1024) void k_timeline_p(unsigned long long* x, cons
         const unsigned long long* pnx = x + size_t(pn) * G::N;
 #pragma unroll
         for (int r = 0; r < G::E; ++r) raw[r] = (pnx + G::idxA(r, 0))[u32(tid)];
-        fwd_stages_f64<16, 0, 4, 1, 14, 3, true>(v, 0u, w, wp, m);
+        fwd_stages_f64<16, 0, 4, 1, WgFullPass<W, true>>(v, 0u, w, wp, m);
         STAMP(2, "");
         redeal_x<G, false, true>(v, ldsd, tid, [](int r, int t) { return G::idxF<10>(r, t); }, [](int r, int t) { return G::idxF<6>(r, t); });
         STAMP(3, "s_waitcnt lgkmcnt(0)");
-        fwd_stages_f64<16, 0, 4, 5, 14, 3, true>(v, u32(__builtin_amdgcn_readfirstlane(u32(tid) >> 6)), w, wp, m);
+        fwd_stages_f64<16, 0, 4, 5, WgFullPass<W, true>>(v, u32(__builtin_amdgcn_readfirstlane(u32(tid) >> 6)), w, wp, m);
         STAMP(4, "");
         redeal_x<G, true, false>(v, ldsd, tid, [](int r, int t) { return G::idxF<6>(r, t); }, [](int r, int t) { return G::idxF<2>(r, t); });
         STAMP(5, "s_waitcnt lgkmcnt(0)");
-        fwd_stages_f64<16, 0, 4, 9, 14, 3>(v, u32(tid) >> 2, w, wp, m);
+        fwd_stages_f64<16, 0, 4, 9, WgFullPass<W, false>>(v, u32(tid) >> 2, w, wp, m);
         STAMP(6, "");
         redeal_x<G, true, false>(v, ldsd, tid, [](int r, int t) { return G::idxF<2>(r, t); }, [](int r, int t) { return G::idxB(r, t); });
         STAMP(7, "s_waitcnt lgkmcnt(0)");

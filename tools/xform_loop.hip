@@ -22,7 +22,9 @@ using namespace hx;
 #define XL_LOGE 4
 #endif
 using G = Geom<14, XL_LOGE>;
-using W = WgNttF64<14, XL_LOGE, 3, XL_PRE, 1>;
+// the mod-up transform of k_ksx_main's round loop: un-centred input, early twiddle requests
+struct LoopOpt : NttOpt { static constexpr int PRE = XL_PRE, FSHIFT = 1; };
+using W = WgNttF64<14, XL_LOGE, 3, LoopOpt>;
 
 __global__ __launch_bounds__(G::T, XL_LOGE == 4 ? 4 : 2) void k_loop(const double* tables, double* out, Mod m, int rounds, unsigned long long* cyc) {
     extern __shared__ __attribute__((aligned(16))) double ldsx[];
