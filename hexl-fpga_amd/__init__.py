@@ -148,6 +148,10 @@ class Context:
     def set_stream(self, raw_stream: int):
         _check(lib().hexl_ctx_set_stream(self.h, _vp(raw_stream)), "hexl_ctx_set_stream")
 
+    def use_own_stream(self):
+        """back to the context's own non-blocking stream; like set_stream, ordered behind what the previous stream holds"""
+        _check(lib().hexl_ctx_use_own_stream(self.h), "hexl_ctx_use_own_stream")
+
     def sync(self):
         _check(lib().hexl_ctx_sync(self.h), "hexl_ctx_sync")
 

@@ -91,20 +91,31 @@ extern "C" int hexl_ctx_destroy(hexl_ctx* c) {
         if (c->ev_comp[i]) (void)hipEventDestroy(c->ev_comp[i]);
         if (c->ev_down[i]) (void)hipEventDestroy(c->ev_down[i]);
     }
+    if (c->ev_switch) (void)hipEventDestroy(c->ev_switch);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return 0;
 }
 
+// A context and its plans keep ONE set of scratch buffers (derived NTT tables, dyadic constants, keyswitch / rescale / rotate scratch,
+// the range flag), safe on one stream because launch k + 1 is ordered behind launch k. A switch keeps that order: the new stream waits
+// for an event recorded behind everything queued on the old one. The host does not wait.
+static int switch_stream(hexl_ctx* c, hipStream_t to) {
+    if (to == c->stream) return 0;
+    HX_CHECK(hipSetDevice(c->device));
+    if (!c->ev_switch) HX_CHECK(hipEventCreateWithFlags(&c->ev_switch, hipEventDisableTiming));
+    HX_CHECK(hipEventRecord(c->ev_switch, c->stream));
+    HX_CHECK(hipStreamWaitEvent(to, c->ev_switch, 0));
+    c->stream = to;
+    return 0;
+}
 extern "C" int hexl_ctx_set_stream(hexl_ctx* c, void* s) {
     if (!c) return HEXL_E_BADARG;
-    c->stream = (hipStream_t)s;
-    return 0;
+    return switch_stream(c, (hipStream_t)s);
 }
 extern "C" int hexl_ctx_use_own_stream(hexl_ctx* c) {
     if (!c) return HEXL_E_BADARG;
-    c->stream = c->own_stream;
-    return 0;
+    return switch_stream(c, c->own_stream);
 }
 extern "C" int hexl_ctx_sync(hexl_ctx* c) {
     if (!c) return HEXL_E_BADARG;

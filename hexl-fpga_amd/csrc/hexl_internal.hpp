@@ -64,6 +64,7 @@ struct hexl_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;      // stream launches go to (own or caller's)
+    hipEvent_t ev_switch = nullptr;    // orders a new stream behind the previous one (capi.hip switch_stream; created at the first switch)
     int num_cu = 0;
     // grow-only device scratch + pinned staging used by the *_host entry points
     void* d_stage = nullptr;  size_t d_stage_bytes = 0;

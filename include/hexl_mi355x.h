@@ -42,9 +42,14 @@ int hexl_device_count(void);
  * binds `device`, creates the stream. */
 int hexl_ctx_create(int device, hexl_ctx** out);
 int hexl_ctx_destroy(hexl_ctx* ctx);
-/* run on a caller-owned hipStream_t (e.g. torch's current stream; NULL = the legacy default stream) */
+/* run on a caller-owned hipStream_t (e.g. torch's current stream; NULL = the legacy default stream).
+ * Stream switches are ordered: after hexl_ctx_set_stream or hexl_ctx_use_own_stream, work submitted through the context and its plans on
+ * the new stream runs behind everything the context has submitted on the previous stream (the context and its plans keep one set of
+ * scratch buffers, which the next launch rewrites). The call itself does not block the host, and does nothing when the stream does
+ * not change. The previous stream must still exist at the switch: switch away from a stream before destroying it. The caller's own
+ * buffers are the caller's to order, as between any two streams. NULL ctx: HEXL_E_BADARG. */
 int hexl_ctx_set_stream(hexl_ctx* ctx, void* hip_stream);
-/* go back to the context's own non-blocking stream (the state after hexl_ctx_create) */
+/* go back to the context's own non-blocking stream (the state after hexl_ctx_create); ordered like hexl_ctx_set_stream */
 int hexl_ctx_use_own_stream(hexl_ctx* ctx);
 int hexl_ctx_sync(hexl_ctx* ctx);
 /* library/device report for logs: writes a NUL-terminated string */
