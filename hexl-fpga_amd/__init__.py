@@ -55,6 +55,7 @@ C_ABI = {
     "hexl_apply_galois": [_vp, _vp, _vp, _sz, _u64, _u64],
     "hexl_rescale": [_vp, _vp, _vp, _sz, _u64, _u64],
     "hexl_rotate": [_vp, _vp, _vp, _sz, _u64],
+    "hexl_rotate_hoisted": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz, ctypes.POINTER(_vp), _vp, _sz],
     "hexl_rns_ntt_fwd": [_vp, _vp, _vp, _sz, _u64],
     "hexl_rns_ntt_inv": [_vp, _vp, _vp, _sz, _u64],
     "hexl_multiply_plain": [_vp, _vp, _vp, _vp, _sz, _u64, _u64, _sz, _i],
@@ -276,7 +277,20 @@ class KeySwitchPlan:
             self.h = None
 
 
+def rotate_hoisted(plans, galois_elts, outs, ct, batch: int):
+    """outs[r][batch][2][L][n] = (sigma_g(c0), 0) + ModDown(sum_d sigma_g(u_d) . key_r[d]) for g = galois_elts[r] and the keys of
+    plans[r], with the mod-up u of ct's component 1 computed once for all of them (hexl_rotate_hoisted). Decrypts like
+    plans[r].rotate(outs[r], ct, batch, g) but is word-identical to it only for g = 1. The plans share one context, n, L, K and moduli
+    (FP64 plans); the scratch is plans[0]'s."""
+    if not (len(plans) == len(galois_elts) == len(outs)):
+        raise ValueError("rotate_hoisted: one plan, one Galois element and one output per rotation")
+    n_rot = len(plans)
+    hs = (_vp * n_rot)(*[p.h.value for p in plans])
+    gs = (_u64 * n_rot)(*[int(g) for g in galois_elts])
+    _check(lib().hexl_rotate_hoisted(hs, gs, n_rot, ptr_array(outs), _ptr(ct), batch), "hexl_rotate_hoisted")
+
+
 from .host_api import HexlFpga  # noqa: E402  (mirror of host/inc/hexl-fpga.h)
 
-__all__ = ["Context", "KeySwitchPlan", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "C_ABI",
+__all__ = ["Context", "KeySwitchPlan", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "C_ABI",
            "LIB_PATH", "ROOT"]

@@ -8,6 +8,7 @@
 //               out[j] = in[brv(((2 brv(j) + 1) g mod 2n - 1) / 2)]                                              k_galois
 //             no arithmetic, no sign flips, no dependence on the root or the modulus.
 //   rotate    (sigma_g(c0), 0) + KeySwitch(sigma_g(c1)): one k_galois launch, then the keyswitch, per slice of instances.
+//   hoisted   many rotations of one ciphertext: the entry point is here, the launcher beside the kernels it runs (keyswitch_f64.hip).
 #include "hexl_internal.hpp"
 #include "ntt_core_f64.hpp"
 #include "number_theory.hpp"
@@ -98,12 +99,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_rs_down(RsArgs a) {
         (dst + G::idxB(r, 0))[tB] = hxf::from_f64(hxf::rs_down(hxf::to_f64(craw[r]), v[r], rc.qlinv, rc.qlinv_p, m));
 }
 
-// ---- Galois automorphism in NTT form ----
-__device__ __forceinline__ u32 galois_src(u32 j, u32 logn, u32 g) {
-    const u32 rj = __builtin_bitreverse32(j) >> (32 - logn);
-    const u32 e = ((2 * rj + 1) * g) & ((2u << logn) - 1);      // (2 brv(j) + 1) g mod 2n; both factors < 2^16
-    return __builtin_bitreverse32((e - 1) >> 1) >> (32 - logn);
-}
+// ---- Galois automorphism in NTT form (galois_src: ntt_core.hpp) ----
 
 struct GaloisArgs {
     const u64* in;              // [count][n]
@@ -117,7 +113,9 @@ struct GaloisArgs {
 // instead, and out[b][1][j] is zeroed -- the keyswitch then adds into (sigma(c0), 0).
 // LDS (n <= 16384, 128 KiB): a coalesced load of the whole polynomial, the gather from LDS, a coalesced store.
 // n = 32768 does not fit: the gather reads global memory (the sources of neighbouring outputs mostly lie within a few words).
-template <bool LDS>
+// C0_ONLY (hexl_rotate_hoisted, p as for rotate): component 1 of `out` is zeroed and sigma(c1) goes nowhere -- the hoisted
+// multiply-accumulate applies sigma to the mod-up output instead; `t` is not read.
+template <bool LDS, bool C0_ONLY = false>
 __global__ __launch_bounds__(1024) void k_galois(GaloisArgs a) {
     typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
@@ -125,7 +123,13 @@ __global__ __launch_bounds__(1024) void k_galois(GaloisArgs a) {
     for (size_t p = blockIdx.x; p < a.count; p += gridDim.x) {
         const u64* src = a.in + p * n;
         u64* dst = a.out + p * n;
-        if (a.t) {
+        if constexpr (C0_ONLY) {
+            if ((p / a.L) & 1) {
+                const u2 zero = {0, 0};
+                for (u32 c = tid; c < n / 2; c += T) reinterpret_cast<u2*>(dst)[c] = zero;
+                continue;                                         // (p is the same for the whole workgroup)
+            }
+        } else if (a.t) {
             const size_t bk = p / a.L, j = p - bk * a.L;
             if (bk & 1) {
                 const u2 zero = {0, 0};
@@ -150,15 +154,16 @@ __global__ __launch_bounds__(1024) void k_galois(GaloisArgs a) {
     }
 }
 
+template <bool C0_ONLY = false>
 static int launch_galois(hexl_ctx* c, hipStream_t st, const GaloisArgs& a) {
     if (!a.count) return 0;
     const u32 n = 1u << a.logn;
     const u32 grid = a.count < 65536 ? (u32)a.count : 65536u;
     if (a.logn <= 14) {
-        if (int rc = hx_lds_optin<k_galois<true>>(c->device, 16384 * 8)) return rc;
-        hipLaunchKernelGGL(k_galois<true>, dim3(grid), dim3(n >= 2048 ? 1024 : 512), size_t(n) * 8, st, a);
+        if (int rc = hx_lds_optin<k_galois<true, C0_ONLY>>(c->device, 16384 * 8)) return rc;
+        hipLaunchKernelGGL((k_galois<true, C0_ONLY>), dim3(grid), dim3(n >= 2048 ? 1024 : 512), size_t(n) * 8, st, a);
     } else {
-        hipLaunchKernelGGL(k_galois<false>, dim3(grid), dim3(1024), 0, st, a);
+        hipLaunchKernelGGL((k_galois<false, C0_ONLY>), dim3(grid), dim3(1024), 0, st, a);
     }
     return (int)hipGetLastError();
 }
@@ -166,6 +171,12 @@ static int launch_galois(hexl_ctx* c, hipStream_t st, const GaloisArgs& a) {
 int hx_launch_galois(hexl_ctx* c, u64* d_out, const u64* d_in, size_t count, u32 logn, u32 g) {
     GaloisArgs a{d_in, d_out, nullptr, count, logn, g, 1};
     return launch_galois(c, c->stream, a);
+}
+
+// d_ct[nb][2][L][n] -> d_out[nb][2][L][n] = (sigma_g(c0), 0): what hexl_rotate_hoisted's mod-down then adds into
+int hx_launch_galois_c0(hexl_ctx* c, u64* d_out, const u64* d_ct, size_t nb, u32 L, u32 logn, u32 g) {
+    GaloisArgs a{d_ct, d_out, nullptr, nb * 2 * L, logn, g, L};
+    return launch_galois<true>(c, c->stream, a);
 }
 
 // ---- rescale ----
@@ -286,4 +297,31 @@ extern "C" int hexl_rotate(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_c
     if (!p->have_keys) return HEXL_E_NOKEYS;
     HX_CHECK(hipSetDevice(p->ctx->device));
     return hx_launch_rotate(p, d_out, d_ct, batch, (u32)g);
+}
+
+extern "C" int hexl_rotate_hoisted(hexl_ks_plan* const* plans, const uint64_t* galois_elts, size_t n_rot, uint64_t* const* d_outs,
+                                   const uint64_t* d_ct, size_t batch) {
+    if (!plans || !galois_elts || !d_outs || !d_ct) return HEXL_E_BADARG;
+    if (!n_rot) return 0;
+    for (size_t r = 0; r < n_rot; ++r)
+        if (!plans[r] || !d_outs[r]) return HEXL_E_BADARG;
+    const hexl_ks_plan* p0 = plans[0];
+    if (!p0->use_f64 || p0->logn < 10 || p0->logn > 15) return HEXL_E_BADARG;     // the (b, d)-major FP64 kernels only
+    const size_t per = 2 * size_t(p0->L) * p0->n * sizeof(u64);
+    if (batch > SIZE_MAX / per) return HEXL_E_BADARG;
+    const size_t bytes = batch * per;
+    for (size_t r = 0; r < n_rot; ++r) {
+        const hexl_ks_plan* p = plans[r];
+        if (p->ctx != p0->ctx || p->n != p0->n || p->L != p0->L || p->K != p0->K || !p->use_f64 || p->moduli != p0->moduli)
+            return HEXL_E_BADARG;
+        if (!galois_elt_ok(galois_elts[r], p0->n)) return HEXL_E_BADARG;
+        if (hx_ranges_overlap(d_outs[r], bytes, d_ct, bytes)) return HEXL_E_BADARG;
+        for (size_t q = 0; q < r; ++q)
+            if (hx_ranges_overlap(d_outs[r], bytes, d_outs[q], bytes)) return HEXL_E_BADARG;
+    }
+    for (size_t r = 0; r < n_rot; ++r)
+        if (!plans[r]->have_keys) return HEXL_E_NOKEYS;
+    if (!batch) return 0;
+    HX_CHECK(hipSetDevice(p0->ctx->device));
+    return hx_launch_rotate_hoisted(plans, galois_elts, n_rot, d_outs, d_ct, batch);
 }

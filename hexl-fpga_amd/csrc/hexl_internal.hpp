@@ -210,6 +210,11 @@ int hx_launch_multiply_relinearize(hexl_ks_plan*, u64* d_out, const u64* d_a, co
 int hx_launch_galois(hexl_ctx*, u64* d_out, const u64* d_in, size_t count, u32 logn, u32 g);
 int hx_launch_rescale(hexl_ks_plan*, u64* d_out, const u64* d_in, size_t batch, u32 n_limbs, u32 n_components);
 int hx_launch_rotate(hexl_ks_plan*, u64* d_out, const u64* d_ct, size_t batch, u32 g);
+// hexl_rotate_hoisted (keyswitch_f64.hip): the keyswitch's steps 1-2 once per chunk on plans[0]'s scratch, steps 3-7 per rotation;
+// hx_launch_galois_c0 (ckks_ops.hip) writes (sigma_g(c0), 0) for nb instances on the context's stream
+int hx_launch_rotate_hoisted(hexl_ks_plan* const* plans, const u64* galois_elts, size_t n_rot, u64* const* d_outs, const u64* d_ct,
+                             size_t batch);
+int hx_launch_galois_c0(hexl_ctx*, u64* d_out, const u64* d_ct, size_t nb, u32 L, u32 logn, u32 g);
 // plan-driven RNS transforms and the plaintext multiply (rns_ops.hip); arguments checked by their entry points (hexl_rns_ntt_fwd,
 // hexl_rns_ntt_inv, hexl_multiply_plain)
 int hx_launch_rns_ntt(hexl_ks_plan*, u64* d_out, const u64* d_in, size_t count, u32 n_limbs, bool inverse);

@@ -51,7 +51,9 @@ __device__ __forceinline__ u32 xcd_item_f(u32 bid, u32 total) {   // see keyswit
 // ---- small batches: one transform per workgroup, so that even a single keyswitch spreads over L*L + ... CUs ----
 // step 1: c_d = INTT_{q_d}(t_target[d]) as canonical doubles
 // mixed-tier kernels (LAZY = -1): four schedules per forward transform at N = 16384 (two -- lazy period 3 / strict -- measured no faster)
-template <int LOGN, int LOGE, int LAZY>
+// CT (hexl_rotate_hoisted only, here and in k_ksf_up): t_target is component 1 of a ciphertext batch [b][2][L][n] read in place -- row d of
+// instance b lies at row 2 b L + d, not b L + d
+template <int LOGN, int LOGE, int LAZY, bool CT = false>
 __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ksf_intt(KsArgsF a) {
     using G = Geom<LOGN, LOGE>;
     extern __shared__ __attribute__((aligned(16))) double ldsd[];
@@ -60,7 +62,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ksf_intt(KsArgsF a) {
     const u32 d = __builtin_amdgcn_readfirstlane(item % a.L);
     const KsModF64 md = a.mods[d];
     const double* tb = a.tables + size_t(d) * 4 * G::N;
-    const u64* src = a.t_target + size_t(item) * G::N;
+    const u64* src = a.t_target + size_t(CT ? 2 * item - d : item) * G::N;
     double v[G::E];
     hxf::RangeMask bad = 0;
 #pragma unroll
@@ -125,7 +127,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ksf_ntt_up(KsArgsF a) {
 // ~5 us per transform on that wait (tools/load_probe.hip, tools/ntt_timeline.hip). The waves of the workgroup only
 // meet at each transform's cross-wave re-deal, so early waves start the next slot while late ones still store.
 // u is kept in the forward transform's register order ("B order", fully coalesced).
-template <int LOGN, int LOGE, int LAZY>
+template <int LOGN, int LOGE, int LAZY, bool CT = false>
 __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ksf_up(KsArgsF a) {
     static_assert(LAZY >= 0, "one schedule for all L + 1 transforms of the workgroup: plans of mixed tiers run k_ksf_intt + k_ksf_ntt_up");
     using G = Geom<LOGN, LOGE>;
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ksf_up(KsArgsF a) {
         const int tid = threadIdx.x;
         const KsModF64 md = a.mods[d];
         const double* tb = a.tables + size_t(d) * 4 * G::N;
-        const u64* src = a.t_target + size_t(item) * G::N;
+        const u64* src = a.t_target + size_t(CT ? 2 * item - d : item) * G::N;
         // uniform row pointer + unsigned 32-bit thread offset: SGPR-base addressing, no 64-bit VALU address math
         const u32 tB = u32(G::idxB(0, tid));
         hxf::RangeMask bad = 0;
@@ -215,6 +217,57 @@ __global__ __launch_bounds__(256) void k_ksf_mac(KsArgsF a, u32 n) {
             }
         __builtin_nontemporal_store(acc0, reinterpret_cast<d2*>(a.prod + ((size_t(b) * 2 + 0) * (L + 1) + slot) * n + j));
         __builtin_nontemporal_store(acc1, reinterpret_cast<d2*>(a.prod + ((size_t(b) * 2 + 1) * (L + 1) + slot) * n + j));
+    }
+}
+
+// step 3 of a hoisted rotation (hexl_rotate_hoisted): prod[b][k][slot] = sum_d sigma_g(u[b][slot][d]) . key[d][k][slot] -- the Galois
+// automorphism applied to the mod-up output, which every rotation of the same ciphertext shares. In NTT-output index space sigma_g is
+// out[j] = in[galois_src(j)]; u, the keys and prod are stored in B order, so a thread takes ONE output index j (gid = slot*n + j), reads
+// the keys and writes prod at position posB(j), and gathers u from posB(galois_src(j)): src = idxB^-1 . pi_g . idxB without a table.
+// The gather reads global memory directly, 8 bytes per lane. pi_g maps every aligned block of 2^k indices onto an aligned block of
+// 2^k indices (the low k bits of j are the high k bits of brv(j), and (2 brv(j) + 1) g only carries upwards), and B order keeps an
+// aligned block of 64 indices as 2^KL rows of 64 >> KL adjacent words: a wave's 64 sources fill exactly as many cache lines as its 64
+// outputs, merely in another order, and a workgroup's (256 indices; 512 at N = 32768, where KL = 5) are whole 128-byte lines. No LDS, no
+// barrier; the price against k_ksf_mac is 8-byte instead of 16-byte accesses. The keys stay in registers while the thread walks the batch.
+// u is not range-reduced (|u| <= 2.14p, KsArgsF) and a permutation moves words without changing them, so the bound holds for every
+// word gathered and the mul_mod / reduce chain below is k_ksf_mac's, term for term.
+struct HoistGeom { u32 logn, loge, kl, wb, g; };                 // Geom<LOGN, LOGE>: N, E, KL, WB as exponents; the Galois element
+
+__device__ __forceinline__ u32 posB(u32 j, const HoistGeom& h) {  // inverse of Geom::idxB: position r*T + tid that holds NTT-output index j
+    const u32 r = (j & ((1u << h.kl) - 1)) | (((j >> (h.kl + h.wb)) & ((1u << (h.loge - h.kl)) - 1)) << h.kl);
+    const u32 tid = ((j >> h.kl) & ((1u << h.wb) - 1)) | ((j >> (h.loge + h.wb)) << h.wb);
+    return (r << (h.logn - h.loge)) | tid;
+}
+
+template <int MAXL>
+__global__ __launch_bounds__(512) void k_ksf_mac_galois(KsArgsF a, HoistGeom h) {
+    const u32 L = a.L, n = 1u << h.logn;
+    const u32 gid = blockIdx.x * blockDim.x + threadIdx.x;        // (slot, j)
+    const u32 slot = gid >> h.logn;
+    if (slot > L) return;
+    const u32 j = gid & (n - 1);
+    const u32 pos = posB(j, h), src = posB(galois_src(j, h.logn, h.g), h);
+    const u32 i = slot < L ? slot : a.K - 1;
+    const Mod m = a.mods[i].m;
+    double key[MAXL][2];
+#pragma unroll
+    for (int d = 0; d < MAXL; ++d)
+        if (d < (int)L) {
+            key[d][0] = a.keys[((size_t(d) * (L + 1) + slot) * 2 + 0) * n + pos];
+            key[d][1] = a.keys[((size_t(d) * (L + 1) + slot) * 2 + 1) * n + pos];
+        }
+    for (u32 b = blockIdx.y; b < a.nb; b += gridDim.y) {
+        const double* ub = a.u + ((size_t(b) * (L + 1) + slot) * L) * n + src;
+        double acc0 = 0.0, acc1 = 0.0;
+#pragma unroll
+        for (int d = 0; d < MAXL; ++d)
+            if (d < (int)L) {
+                const double u = ub[size_t(d) * n];               // plain load: the rest of the line is another lane's, or the next wave's
+                acc0 = hxf::reduce(acc0 + hxf::mul_mod(u, key[d][0], m), m);
+                acc1 = hxf::reduce(acc1 + hxf::mul_mod(u, key[d][1], m), m);
+            }
+        __builtin_nontemporal_store(acc0, a.prod + ((size_t(b) * 2 + 0) * (L + 1) + slot) * n + pos);
+        __builtin_nontemporal_store(acc1, a.prod + ((size_t(b) * 2 + 1) * (L + 1) + slot) * n + pos);
     }
 }
 
@@ -530,30 +583,112 @@ static int run_chunk_f64(hexl_ks_plan* p, const KsArgsF& a, int stage_mask, hipE
 
 size_t hx_ks_f64_scratch_words(size_t L) { return L + (L + 1) * L + 2 * (L + 1) + 2; }   // per instance, in units of n
 
-int hx_launch_keyswitch_f64(hexl_ks_plan* p, u64* d_result, const u64* d_t_target, size_t nb, int stage_mask,
-                            hipEvent_t* ev) {
+// constants, tables and keys of `p`; scratch (the chunk `mem->cur_scratch` points at) and range flag of `mem` -- the same plan, except for
+// hexl_rotate_hoisted, where every rotation's plan works in plans[0]'s scratch
+static KsArgsF ksf_args(const hexl_ks_plan* p, const hexl_ks_plan* mem, u64* d_result, const u64* d_t_target, size_t nb) {
     const size_t n = p->n, L = p->L;
     KsArgsF a;
     a.mods = p->d_mods_f64; a.tables = p->d_tables_f64; a.keys = p->d_keys_f64;
-    a.c = (double*)p->cur_scratch;
-    a.u = a.c + p->cap * L * n;
-    a.prod = a.u + p->cap * (L + 1) * L * n;
-    a.s = a.prod + p->cap * 2 * (L + 1) * n;
+    a.c = (double*)mem->cur_scratch;
+    a.u = a.c + mem->cap * L * n;
+    a.prod = a.u + mem->cap * (L + 1) * L * n;
+    a.s = a.prod + mem->cap * 2 * (L + 1) * n;
     a.t_target = d_t_target; a.result = d_result;
     a.L = (u32)L; a.K = p->K; a.nb = (u32)nb;
-    a.range_flag = p->d_flag;
+    a.range_flag = mem->d_flag;
     a.overwrite = p->overwrite_result ? 1u : 0u;
     a.skip = p->x_skip ? 1u : 0u;
     a.tiermap = hx_tiermap(p);
+    return a;
+}
+// the tier of the kernels a plan's chunks run on: see hx_launch_keyswitch_f64
+static int ksf_lazy(const hexl_ks_plan* p) {
+    static const bool lookup = hx_knob_ks_per_limb() == 2;
+    return p->mixed && lookup ? -1 : p->f64_lazy;
+}
+
+int hx_launch_keyswitch_f64(hexl_ks_plan* p, u64* d_result, const u64* d_t_target, size_t nb, int stage_mask,
+                            hipEvent_t* ev) {
+    const KsArgsF a = ksf_args(p, p, d_result, d_t_target, nb);
     // Limbs of different tiers: the kernels built with LAZY = -1 look the schedule up per transform (with_tier). They are NOT the default
     // here: this pipeline serves the batches that do not fill the chip, where latency binds, not FP64 issue, and a kernel that carries
     // two to four copies of its transforms spills (k_ksf_moddown 80 registers, k_ksl_up 116) -- bridge-seal's chain at 2 ... 48 instances runs
     // 1-12 % FASTER on the plan-wide tier (round 5, tools/seal_chain_rate.py; 4 instances: 44.3 k against 38.9 k keyswitch/s). The slot-major
     // pipeline (one launch per tier group, +14 %) and the lone-keyswitch kernels keep their per-limb tiers. HEXL_KS_PER_LIMB=2 selects the
     // per-transform lookup here as well (tests).
-    static const bool lookup = hx_knob_ks_per_limb() == 2;
     // LAZY template argument = forward reduction period (f64_arith.hpp): 3 when every modulus <= 2^51(1+2^-7), 6 / 12
     // for moduli <= 2^50 / 2^49 (N = 16384 only; the smaller transforms keep 3), 0 = strict
-    return hx_with_f64_geom(p->logn, p->mixed && lookup ? -1 : p->f64_lazy,
-                            [&](auto N, auto E, auto Z) { return run_chunk_f64<N, E, Z>(p, a, stage_mask, ev); });
+    return hx_with_f64_geom(p->logn, ksf_lazy(p), [&](auto N, auto E, auto Z) { return run_chunk_f64<N, E, Z>(p, a, stage_mask, ev); });
+}
+
+// ---- hoisted rotations (hexl_rotate_hoisted): R rotations of one ciphertext share the keyswitch's steps 1-2 ----
+// steps 1-2 of one chunk on component 1 of the ciphertext batch, read in place (the CT kernels); the route is run_chunk_f64's
+template <int LOGN, int LOGE, int LAZY>
+static int run_hoist_up(hexl_ctx* c, const KsArgsF& a) {
+    using G = Geom<LOGN, LOGE>;
+    const u32 L = a.L, nb = a.nb;
+    const bool fused_up = LAZY >= 0 && (hx_knob("HEXL_KS_FUSE", 1) & 1) && nb * L >= 2 * (u32)c->num_cu && !G::HALF_ONLY;
+    if constexpr (LAZY >= 0)
+        if (fused_up) {
+            if (int rc = hx_lds_optin<k_ksf_up<LOGN, LOGE, LAZY, true>>(c->device, G::LDS_USED)) return rc;
+            hipLaunchKernelGGL((k_ksf_up<LOGN, LOGE, LAZY, true>), dim3(nb * L), dim3(G::T), G::LDS_USED, c->stream, a);
+            return (int)hipGetLastError();
+        }
+    if (int rc = hx_lds_optin<k_ksf_intt<LOGN, LOGE, LAZY, true>, k_ksf_ntt_up<LOGN, LOGE, LAZY>>(c->device, G::LDS_USED)) return rc;
+    hipLaunchKernelGGL((k_ksf_intt<LOGN, LOGE, LAZY, true>), dim3(nb * L), dim3(G::T), G::LDS_USED, c->stream, a);
+    hipLaunchKernelGGL((k_ksf_ntt_up<LOGN, LOGE, LAZY>), dim3(nb * L * L), dim3(G::T), G::LDS_USED, c->stream, a);
+    return (int)hipGetLastError();
+}
+
+// steps 3-7 of one rotation of one chunk: sigma_g inside the multiply-accumulate, then the keyswitch's own steps 4-7
+template <int LOGN, int LOGE, int LAZY>
+static int run_hoist_down(hexl_ctx* c, const KsArgsF& a, u32 g) {
+    using G = Geom<LOGN, LOGE>;
+    if (int rc = hx_lds_optin<k_ksf_intt_sp<LOGN, LOGE, LAZY>, k_ksf_moddown<LOGN, LOGE, LAZY>>(c->device, G::LDS_USED)) return rc;
+    const u32 L = a.L, nb = a.nb;
+    const u32 by = nb < 8 ? nb : 8;                                // as run_chunk_f64
+    if (g == 1) {                                                  // the identity: the keyswitch's own step 3
+        const u32 threads = (L + 1) * (G::N / 2);
+        if (L <= 8) hipLaunchKernelGGL((k_ksf_mac<8>), dim3(threads / 256, by), dim3(256), 0, c->stream, a, (u32)G::N);
+        else        hipLaunchKernelGGL((k_ksf_mac<16>), dim3(threads / 256, by), dim3(256), 0, c->stream, a, (u32)G::N);
+    } else {
+        const HoistGeom h{LOGN, LOGE, G::KL, G::WB, g};
+        const u32 wg = G::KL + 4 > 8 ? 1u << (G::KL + 4) : 256u;   // 2^KL rows of >= 16 adjacent words: whole 128-byte lines per workgroup
+        static_assert(G::KL + 4 <= 9, "k_ksf_mac_galois is bounded at 512 threads");
+        if (L <= 8) hipLaunchKernelGGL((k_ksf_mac_galois<8>), dim3((L + 1) * G::N / wg, by), dim3(wg), 0, c->stream, a, h);
+        else        hipLaunchKernelGGL((k_ksf_mac_galois<16>), dim3((L + 1) * G::N / wg, by), dim3(wg), 0, c->stream, a, h);
+    }
+    hipLaunchKernelGGL((k_ksf_intt_sp<LOGN, LOGE, LAZY>), dim3(nb * 2), dim3(G::T), G::LDS_USED, c->stream, a);
+    hipLaunchKernelGGL((k_ksf_moddown<LOGN, LOGE, LAZY>), dim3(nb * L * 2), dim3(G::T), G::LDS_USED, c->stream, a);
+    return (int)hipGetLastError();
+}
+
+// Arguments checked by hexl_rotate_hoisted (ckks_ops.hip). Everything goes to the context's stream, chunk after chunk, rotation after
+// rotation: one lane, so nothing has to be joined and the next chunk's mod-up overwrites u behind the last rotation that read it.
+int hx_launch_rotate_hoisted(hexl_ks_plan* const* plans, const u64* galois_elts, size_t n_rot, u64* const* d_outs, const u64* d_ct,
+                             size_t batch) {
+    hexl_ks_plan* p0 = plans[0];
+    hexl_ctx* c = p0->ctx;
+    const size_t n = p0->n, L = p0->L, per = 2 * L * n;
+    const size_t chunk = hx_ks_chunk_of(p0, batch);
+    // plans[0]'s keyswitch scratch, grown as hx_launch_keyswitch grows it (hexl_ks_scratch_bytes(p, 1): one instance of a chunk, every lane)
+    if (int rc = hx_grow_device((void**)&p0->d_scratch, &p0->cap, chunk, hexl_ks_scratch_bytes(p0, 1), nullptr)) return rc;
+    p0->cur = c->stream;
+    p0->cur_scratch = p0->d_scratch;
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t nb = batch - b0 < chunk ? batch - b0 : chunk;
+        const u64* ct = d_ct + b0 * per;
+        const KsArgsF up = ksf_args(p0, p0, nullptr, ct + L * n, nb);
+        if (int rc = hx_with_f64_geom(p0->logn, ksf_lazy(p0), [&](auto N, auto E, auto Z) { return run_hoist_up<N, E, Z>(c, up); })) return rc;
+        for (size_t r = 0; r < n_rot; ++r) {
+            const u32 g = (u32)galois_elts[r];
+            u64* out = d_outs[r] + b0 * per;
+            if (int rc = hx_launch_galois_c0(c, out, ct, nb, (u32)L, p0->logn, g)) return rc;
+            KsArgsF a = ksf_args(plans[r], p0, out, nullptr, nb);
+            a.overwrite = 0;                                       // accumulated into (sigma_g(c0), 0)
+            if (int rc = hx_with_f64_geom(p0->logn, ksf_lazy(plans[r]), [&](auto N, auto E, auto Z) { return run_hoist_down<N, E, Z>(c, a, g); }))
+                return rc;
+        }
+    }
+    return 0;
 }

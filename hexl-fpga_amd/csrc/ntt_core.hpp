@@ -141,6 +141,14 @@ struct Geom {
     static constexpr bool wave_private = (LOGT <= 6) || (LO <= 6);
 };
 
+// Galois automorphism X -> X^g on a polynomial in NTT form (the transforms' bit-reversed output order): word j of the output is word
+// galois_src(j) of the input (hexl_apply_galois; ckks_ops.hip k_galois, keyswitch_f64.hip k_ksf_mac_galois)
+__device__ __forceinline__ uint32_t galois_src(uint32_t j, uint32_t logn, uint32_t g) {
+    const uint32_t rj = __builtin_bitreverse32(j) >> (32 - logn);
+    const uint32_t e = ((2 * rj + 1) * g) & ((2u << logn) - 1);      // (2 brv(j) + 1) g mod 2n; both factors < 2^16
+    return __builtin_bitreverse32((e - 1) >> 1) >> (32 - logn);
+}
+
 // ---------------------------------------------------------------------------------------------
 // register butterfly networks. `v` is the thread's E words, OFF the first register of the group.
 // ---------------------------------------------------------------------------------------------

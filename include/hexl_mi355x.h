@@ -149,6 +149,33 @@ int hexl_rescale(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_in, size
  * even or >= 2n, or d_out overlapping d_ct. Device memory kept by the plan, grow-only, beside the keyswitch's scratch:
  * min(batch, chunk) x L x n words (sigma_g(c1) of one slice; 224 MiB at n = 16384, L = 7). */
 int hexl_rotate(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t galois_elt);
+/* Hoisted rotations: n_rot rotations of ONE ciphertext batch (the inner loop of the diagonal method, rotate -> multiply_plain ->
+ * accumulate). The keyswitch's steps 1-2 (inverse transforms and mod-up, L + L*L of its L*L + 3L + 2 transforms) depend on c1 alone,
+ * not on the key, and commute with the Galois automorphism up to a digit lift of the same size: they run once per chunk and every
+ * rotation reuses their output.
+ *   plans[r]        holds the switching key from s(X^g_r) to s;  galois_elts[r] = g_r
+ *   d_outs          HOST array of n_rot DEVICE pointers, each [batch][2][L][n]
+ *   d_ct            [batch][2][L][n], NTT form, every word below its modulus
+ * For every r, d_outs[r] is WRITTEN with (sigma_g(c0), 0) + ModDown(sum_d sigma_g(u_d) . key_r[d]), where
+ * u_d[slot] = NTT_slot(INTT_d(c1[d]) mod q_slot) is the keyswitch's mod-up of c1, sigma_g the word permutation of hexl_apply_galois
+ * and ModDown the keyswitch's steps 4-7. Asynchronous on the context's stream (one lane: the stream contract of hexl_ctx_set_stream
+ * holds as for any single launch).
+ * NOT word-identical to hexl_rotate for g != 1: hexl_rotate lifts the digits of sigma_g(c1), where a negated coefficient is q_d - c
+ * before it is reduced modulo q_i; this call lifts the digits of c1 and then permutes, where it is -(c mod q_i). The two differ by
+ * multiples of q_d inside a digit; both are digit lifts below q_d that are congruent to sigma_g(c1) modulo q_d, so both outputs
+ * decrypt to the same plaintext with key-switch noise of the same bound. For g = 1 the output is word for word that of hexl_rotate.
+ * Plans: all of one context, with the same n, L, K and moduli; FP64 plans only (every modulus < 2^52), n = 1024 ... 32768; every
+ * plan with keys (else HEXL_E_NOKEYS). The plans must have been created with the same twiddles (all derived, or the same h_twiddles):
+ * that is the caller's responsibility, it is not checked. The same g, or the same plan, may appear more than once.
+ * HEXL_E_BADARG: a null pointer (in the arguments or in either array), a plan that does not match plans[0] or runs on the integer
+ * kernels, a g that is even or >= 2n, a d_outs[r] that overlaps d_ct or another d_outs[r'], a size that overflows. n_rot == 0 or
+ * batch == 0 returns 0 after these checks and writes nothing.
+ * Device memory: steps 1-2 run in plans[0]'s keyswitch scratch, grown as hexl_keyswitch grows it -- hexl_ks_scratch_bytes(plans[0],
+ * batch) bytes, of which this call uses the first lane (min(batch, chunk) x (L*L + 4L + 4) x n doubles: 2.5 GiB of the 5.1 GiB at
+ * n = 16384, L = 7, batch >= 256); the other plans' scratch is not touched and nothing else is allocated. The input-range flag
+ * (hexl_ks_range_check) is raised on plans[0] only. */
+int hexl_rotate_hoisted(hexl_ks_plan* const* plans, const uint64_t* galois_elts, size_t n_rot, uint64_t* const* d_outs,
+                        const uint64_t* d_ct, size_t batch);
 /* Domain changes and the plaintext product for ciphertexts that live on the device: the ends of a flow (encode / encrypt need the
  * forward transform, decrypt / decode the inverse) and the multiplier of a linear layer (rotate -> multiply_plain -> accumulate).
  * All three are asynchronous on the context's stream, need no keys and keep no device memory in the plan. FP64 plans only (every
