@@ -56,6 +56,7 @@ C_ABI = {
     "hexl_rescale": [_vp, _vp, _vp, _sz, _u64, _u64],
     "hexl_rotate": [_vp, _vp, _vp, _sz, _u64],
     "hexl_rotate_hoisted": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz, ctypes.POINTER(_vp), _vp, _sz],
+    "hexl_linear_transform": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_vp), _sz, _vp, _vp, _vp, _sz],
     "hexl_rns_ntt_fwd": [_vp, _vp, _vp, _sz, _u64],
     "hexl_rns_ntt_inv": [_vp, _vp, _vp, _sz, _u64],
     "hexl_multiply_plain": [_vp, _vp, _vp, _vp, _sz, _u64, _u64, _sz, _i],
@@ -290,7 +291,23 @@ def rotate_hoisted(plans, galois_elts, outs, ct, batch: int):
     _check(lib().hexl_rotate_hoisted(hs, gs, n_rot, ptr_array(outs), _ptr(ct), batch), "hexl_rotate_hoisted")
 
 
+def linear_transform(plans, galois_elts, pts, out, ct, batch: int, pt_identity=None):
+    """out[batch][2][L][n] = sum_r pts[r] . Rotate_g_r(ct) + pt_identity . ct for g_r = galois_elts[r] and the keys of plans[r], with
+    the mod-up of ct's component 1 AND the mod-down shared by all rotations (hexl_linear_transform): the weighted sum is taken in the
+    extended basis, so each pts[r] is [L + 1][n] -- the plaintext modulo q_0 ... q_(L-1) and modulo the special prime, in NTT form
+    (plans[r].rns_ntt_fwd(..., 1, K) when K = L + 1); pt_identity is [L][n] or None. Decrypts like rotate_hoisted -> multiply_plain ->
+    accumulate but is not word-identical to it (one rounding by the special prime instead of one per rotation). The plans share one
+    context, n, L, K and moduli (FP64 plans); the scratch is plans[0]'s."""
+    if not (len(plans) == len(galois_elts) == len(pts)):
+        raise ValueError("linear_transform: one plan, one Galois element and one plaintext per rotation")
+    n_rot = len(plans)
+    hs = (_vp * n_rot)(*[p.h.value for p in plans])
+    gs = (_u64 * n_rot)(*[int(g) for g in galois_elts])
+    _check(lib().hexl_linear_transform(hs, gs, ptr_array(pts), n_rot, None if pt_identity is None else _ptr(pt_identity), _ptr(out),
+                                       _ptr(ct), batch), "hexl_linear_transform")
+
+
 from .host_api import HexlFpga  # noqa: E402  (mirror of host/inc/hexl-fpga.h)
 
-__all__ = ["Context", "KeySwitchPlan", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "C_ABI",
+__all__ = ["Context", "KeySwitchPlan", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform", "C_ABI",
            "LIB_PATH", "ROOT"]

@@ -9,6 +9,8 @@
 //             no arithmetic, no sign flips, no dependence on the root or the modulus.
 //   rotate    (sigma_g(c0), 0) + KeySwitch(sigma_g(c1)): one k_galois launch, then the keyswitch, per slice of instances.
 //   hoisted   many rotations of one ciphertext: the entry point is here, the launcher beside the kernels it runs (keyswitch_f64.hip).
+//   linear    the hoisted rotations weighted by plaintexts and summed before ONE mod-down (hexl_linear_transform): entry point and the
+//             key-free part (k_galois_c0_pt) here, launcher and multiply-accumulate in keyswitch_f64.hip.
 #include "hexl_internal.hpp"
 #include "ntt_core_f64.hpp"
 #include "number_theory.hpp"
@@ -179,6 +181,77 @@ int hx_launch_galois_c0(hexl_ctx* c, u64* d_out, const u64* d_ct, size_t nb, u32
     return launch_galois<true>(c, c->stream, a);
 }
 
+// ---- the part of a linear transform (hexl_linear_transform) that needs no key: what its single mod-down then adds into ----
+//     out[b][0][i][j] = sum_r pt_r[i][j] . c0[b][i][galois_src_r(j)] + pt_id[i][j] . c0[b][i][j]
+//     out[b][1][i][j] =                                                pt_id[i][j] . c1[b][i][j]      (0 without an identity term)
+// every word canonical. One launch per chunk writes both components; the rotations come from the per-call device table.
+struct GaloisPtArgs {
+    const KsModF64* mods;       // [K]
+    const u64* ct;              // [nb][2][L][n]
+    u64* out;                   // [nb][2][L][n]
+    const HxLtRot* rots;        // [n_rot]: plaintext [L + 1][n] (rows 0 ... L - 1 are read here) and Galois element
+    const u64* pt_id;           // [L][n]; nullptr: no identity term
+    u32* range_flag;            // raised for a ciphertext word read here that is not below its modulus
+    u32 n_rot, nb, L, logn;
+};
+constexpr u32 GPT_THREADS = 256, GPT_LOG_CHUNK = 9;     // two adjacent words per lane: 512 words of one polynomial per workgroup
+
+// One workgroup per (limb, 512-word piece, instance), the instance fastest: the workgroups resident at any time meet the same plaintext
+// words, which are read from HBM once and from L2 afterwards. A lane owns two adjacent output words (16-byte plaintext loads and stores)
+// and gathers its two c0 words per rotation through L2 -- the whole row is 8 n bytes, and sigma_g maps aligned blocks onto aligned
+// blocks (keyswitch_f64.hip k_ksf_mac_galois), so a workgroup's sources are whole cache lines. The sum runs on hxf::lt_mac_acc, the
+// multiply-accumulate's own chain. Every c0 word is some lane's source in every rotation, so the range check sees all of them.
+template <bool IDENTITY>
+__global__ __launch_bounds__(GPT_THREADS) void k_galois_c0_pt(GaloisPtArgs a) {
+    typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
+    const u32 n = 1u << a.logn;
+    const u32 b = blockIdx.x % a.nb, ic = blockIdx.x / a.nb;      // (i * pieces + piece) * nb + b
+    const u32 i = ic >> (a.logn - GPT_LOG_CHUNK), piece = ic & ((1u << (a.logn - GPT_LOG_CHUNK)) - 1);
+    const u32 j = (piece << GPT_LOG_CHUNK) + 2 * threadIdx.x;
+    const Mod m = a.mods[i].m;
+    const size_t row = size_t(i) * n;
+    const u64* c0 = a.ct + size_t(b) * 2 * a.L * n + row;
+    const u64* c1 = c0 + size_t(a.L) * n;
+    u64* o0 = a.out + size_t(b) * 2 * a.L * n + row;
+    u64* o1 = o0 + size_t(a.L) * n;
+    hxf::RangeMask bad = 0;
+    double acc[2] = {0.0, 0.0};
+    for (u32 r = 0; r < a.n_rot; ++r) {
+        const HxLtRot rot = a.rots[r];                            // uniform: scalar loads
+        const u2 t = *reinterpret_cast<const u2*>(rot.pt + row + j);
+        const u64 w[2] = {c0[galois_src(j, a.logn, (u32)rot.g)], c0[galois_src(j + 1, a.logn, (u32)rot.g)]};
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+            acc[e] = hxf::lt_mac_acc(hxf::reduce(hxf::to_f64_checked(w[e], m, bad), m), hxf::lt_pt(hxf::to_f64(t[e]), m), acc[e], m);
+    }
+    u2 out0, out1 = {0, 0};
+    if constexpr (IDENTITY) {
+        const u2 t = *reinterpret_cast<const u2*>(a.pt_id + row + j);
+        const u2 w0 = *reinterpret_cast<const u2*>(c0 + j), w1 = *reinterpret_cast<const u2*>(c1 + j);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const double td = hxf::lt_pt(hxf::to_f64(t[e]), m);
+            acc[e] = hxf::lt_mac_acc(hxf::reduce(hxf::to_f64_checked(w0[e], m, bad), m), td, acc[e], m);
+            out1[e] = hxf::from_f64(hxf::lift(hxf::lt_mac(hxf::reduce(hxf::to_f64_checked(w1[e], m, bad), m), td, m), m));
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 2; ++e) out0[e] = hxf::from_f64(hxf::lift(acc[e], m));
+    *reinterpret_cast<u2*>(o0 + j) = out0;
+    *reinterpret_cast<u2*>(o1 + j) = out1;
+    hxf::report_range(bad, a.range_flag);
+}
+
+int hx_launch_galois_c0_pt(hexl_ks_plan* p, u64* d_out, const u64* d_ct, const HxLtRot* d_rots, size_t n_rot, const u64* d_pt_identity,
+                           size_t nb) {
+    if (!nb) return 0;
+    const GaloisPtArgs a{p->d_mods_f64, d_ct, d_out, d_rots, d_pt_identity, p->d_flag, (u32)n_rot, (u32)nb, p->L, p->logn};
+    const dim3 grid((u32)(nb * p->L * (p->n >> GPT_LOG_CHUNK))), block(GPT_THREADS);
+    if (d_pt_identity) hipLaunchKernelGGL((k_galois_c0_pt<true>), grid, block, 0, p->ctx->stream, a);
+    else hipLaunchKernelGGL((k_galois_c0_pt<false>), grid, block, 0, p->ctx->stream, a);
+    return (int)hipGetLastError();
+}
+
 // ---- rescale ----
 template <int LOGN, int LOGE, int LAZY>
 static int run_rescale(hexl_ks_plan* p, const RsArgs& a, u32 nb, u32 ncomp) {
@@ -324,4 +397,31 @@ extern "C" int hexl_rotate_hoisted(hexl_ks_plan* const* plans, const uint64_t* g
     if (!batch) return 0;
     HX_CHECK(hipSetDevice(p0->ctx->device));
     return hx_launch_rotate_hoisted(plans, galois_elts, n_rot, d_outs, d_ct, batch);
+}
+
+extern "C" int hexl_linear_transform(hexl_ks_plan* const* plans, const uint64_t* galois_elts, const uint64_t* const* d_pts, size_t n_rot,
+                                     const uint64_t* d_pt_identity, uint64_t* d_out, const uint64_t* d_ct, size_t batch) {
+    if (!plans || !galois_elts || !d_pts || !d_out || !d_ct || !n_rot) return HEXL_E_BADARG;
+    if (n_rot > SIZE_MAX / sizeof(HxLtRot)) return HEXL_E_BADARG;
+    for (size_t r = 0; r < n_rot; ++r)
+        if (!plans[r] || !d_pts[r]) return HEXL_E_BADARG;
+    const hexl_ks_plan* p0 = plans[0];
+    if (!p0->use_f64 || p0->logn < 10 || p0->logn > 15) return HEXL_E_BADARG;     // as hexl_rotate_hoisted
+    const size_t row = size_t(p0->L) * p0->n * sizeof(u64), per = 2 * row;
+    if (batch > SIZE_MAX / per) return HEXL_E_BADARG;
+    const size_t bytes = batch * per, pt_bytes = row + p0->n * sizeof(u64);       // [L + 1][n]
+    if (hx_ranges_overlap(d_out, bytes, d_ct, bytes)) return HEXL_E_BADARG;
+    if (d_pt_identity && hx_ranges_overlap(d_out, bytes, d_pt_identity, row)) return HEXL_E_BADARG;
+    for (size_t r = 0; r < n_rot; ++r) {
+        const hexl_ks_plan* p = plans[r];
+        if (p->ctx != p0->ctx || p->n != p0->n || p->L != p0->L || p->K != p0->K || !p->use_f64 || p->moduli != p0->moduli)
+            return HEXL_E_BADARG;
+        if (!galois_elt_ok(galois_elts[r], p0->n)) return HEXL_E_BADARG;
+        if (hx_ranges_overlap(d_out, bytes, d_pts[r], pt_bytes)) return HEXL_E_BADARG;
+    }
+    for (size_t r = 0; r < n_rot; ++r)
+        if (!plans[r]->have_keys) return HEXL_E_NOKEYS;
+    if (!batch) return 0;
+    HX_CHECK(hipSetDevice(p0->ctx->device));
+    return hx_launch_linear_transform(plans, galois_elts, d_pts, n_rot, d_pt_identity, d_out, d_ct, batch);
 }

@@ -110,6 +110,19 @@ HX_HD double pt_mul(double c, double t, const Mod m) { return lift(pt_mul_centre
 // sum is exact and inside reduce's domain.
 HX_HD double pt_mul_acc(double c, double t, double prev, const Mod m) { return lift(reduce(pt_mul_centred(c, t, m) + prev, m), m); }
 
+// ---- the scalar chains of the linear transform (keyswitch_f64.hip k_ksf_mac_galois_pt, ckks_ops.hip k_galois_c0_pt), here so that
+// tests/cpp/lt_mac_selftest.cpp replays the kernels' own source against 128-bit integers --------------------------------------------
+// a plaintext word as the multiply-accumulate takes it: canonical (0 <= t < p < 2^52, exact as a double) -> centred, |.| <= p/2 + 2;
+// converted once per thread, the same for every instance it meets
+HX_HD double lt_pt(double t, const Mod m) { return reduce(t, m); }
+// acc' = (prev + pt * inner) mod p, centred. pt = lt_pt(.), inner and prev outputs of reduce: all three |.| <= p/2 + 2, the operand
+// range mul_mod is bounded for, so |product| <= 0.7p and |prev + product| <= 1.2p + 2 < 2^53: the sum is exact and inside reduce's
+// domain, |acc'| <= p/2 + 2 -- pt_mul_acc's chain with a centred addend in place of a canonical one. A reduce output is what
+// k_ksf_intt_sp and k_ksf_moddown accept from k_ksf_mac, and what the next rotation takes as prev.
+HX_HD double lt_mac_acc(double inner, double pt, double prev, const Mod m) { return reduce(prev + mul_mod(pt, inner, m), m); }
+// the first term of a sum: no prev (the accumulator is written, not read)
+HX_HD double lt_mac(double inner, double pt, const Mod m) { return reduce(mul_mod(pt, inner, m), m); }
+
 // The STRICT butterflies (every value reduced after every operation) leave room above 2^52: the largest intermediate is the
 // inverse butterfly's |h - k p| <= (1.31 + 0.22) p for |d| = |X - Y| <= p + 4 (quotient from the product: three roundings of a
 // value near p/2, ulp 1/2), the forward's |X + t| <= 1.4 p, all below 2^53 up to p ~ 2^52.39. The standalone _NTT / _INTT fast

@@ -215,6 +215,15 @@ int hx_launch_rotate(hexl_ks_plan*, u64* d_out, const u64* d_ct, size_t batch, u
 int hx_launch_rotate_hoisted(hexl_ks_plan* const* plans, const u64* galois_elts, size_t n_rot, u64* const* d_outs, const u64* d_ct,
                              size_t batch);
 int hx_launch_galois_c0(hexl_ctx*, u64* d_out, const u64* d_ct, size_t nb, u32 L, u32 logn, u32 g);
+// hexl_linear_transform (keyswitch_f64.hip): the hoisted rotations weighted by plaintexts and summed in the extended basis, one mod-down
+// per chunk. HxLtRot: one rotation of the per-call device table (in the context's d_shared) that hx_launch_galois_c0_pt (ckks_ops.hip)
+// walks: d_out[nb][2][L][n] = (sum_r pt_r . sigma_{g_r}(c0) + pt_id . c0, pt_id . c1), canonical words, on the context's stream; the
+// range flag of `p` is raised for a ciphertext word it reads that is not below its modulus
+struct HxLtRot { const u64* pt; u64 g; };                       // pt: [L + 1][n], the kernel reads rows 0 ... L - 1
+int hx_launch_linear_transform(hexl_ks_plan* const* plans, const u64* galois_elts, const u64* const* d_pts, size_t n_rot,
+                               const u64* d_pt_identity, u64* d_out, const u64* d_ct, size_t batch);
+int hx_launch_galois_c0_pt(hexl_ks_plan* p, u64* d_out, const u64* d_ct, const HxLtRot* d_rots, size_t n_rot, const u64* d_pt_identity,
+                           size_t nb);
 // plan-driven RNS transforms and the plaintext multiply (rns_ops.hip); arguments checked by their entry points (hexl_rns_ntt_fwd,
 // hexl_rns_ntt_inv, hexl_multiply_plain)
 int hx_launch_rns_ntt(hexl_ks_plan*, u64* d_out, const u64* d_in, size_t count, u32 n_limbs, bool inverse);

@@ -271,6 +271,50 @@ __global__ __launch_bounds__(512) void k_ksf_mac_galois(KsArgsF a, HoistGeom h) 
     }
 }
 
+// step 3 of a linear transform (hexl_linear_transform): one rotation's term of
+//     prod[b][k][slot] = sum_r pt_r[slot] . ( sum_d sigma_{g_r}(u[b][slot][d]) . key_r[d][k][slot] )
+// k_ksf_mac_galois's addressing and inner sum, term for term; the reduced inner sum is then multiplied by the rotation's plaintext word
+// and added to what the earlier rotations left in prod (hxf::lt_mac_acc; FIRST: the chunk's first rotation writes prod without reading
+// it). pt is [L + 1][n] u64 in plain NTT-output order, row L modulo the special prime: the thread's word is pt[slot][j], coalesced in j,
+// converted once and the same for every instance the thread walks. prod never leaves the extended basis between rotations, so the
+// special-prime inverse and the mod-down run once for all of them. g = 1 takes the same kernel (galois_src(j) = j).
+template <int MAXL, bool FIRST>
+__global__ __launch_bounds__(512) void k_ksf_mac_galois_pt(KsArgsF a, HoistGeom h, const u64* pt) {
+    const u32 L = a.L, n = 1u << h.logn;
+    const u32 gid = blockIdx.x * blockDim.x + threadIdx.x;        // (slot, j)
+    const u32 slot = gid >> h.logn;
+    if (slot > L) return;
+    const u32 j = gid & (n - 1);
+    const u32 pos = posB(j, h), src = posB(galois_src(j, h.logn, h.g), h);
+    const u32 i = slot < L ? slot : a.K - 1;
+    const Mod m = a.mods[i].m;
+    const double t = hxf::lt_pt(hxf::to_f64(pt[gid]), m);         // gid = slot * n + j
+    double key[MAXL][2];
+#pragma unroll
+    for (int d = 0; d < MAXL; ++d)
+        if (d < (int)L) {
+            key[d][0] = a.keys[((size_t(d) * (L + 1) + slot) * 2 + 0) * n + pos];
+            key[d][1] = a.keys[((size_t(d) * (L + 1) + slot) * 2 + 1) * n + pos];
+        }
+    for (u32 b = blockIdx.y; b < a.nb; b += gridDim.y) {
+        const double* ub = a.u + ((size_t(b) * (L + 1) + slot) * L) * n + src;
+        double* p0 = a.prod + ((size_t(b) * 2 + 0) * (L + 1) + slot) * n + pos;
+        double* p1 = a.prod + ((size_t(b) * 2 + 1) * (L + 1) + slot) * n + pos;
+        double prev0 = 0.0, prev1 = 0.0;
+        if constexpr (!FIRST) { prev0 = *p0; prev1 = *p1; }        // requested in front of the gather
+        double acc0 = 0.0, acc1 = 0.0;
+#pragma unroll
+        for (int d = 0; d < MAXL; ++d)
+            if (d < (int)L) {
+                const double u = ub[size_t(d) * n];               // plain load, as k_ksf_mac_galois
+                acc0 = hxf::reduce(acc0 + hxf::mul_mod(u, key[d][0], m), m);
+                acc1 = hxf::reduce(acc1 + hxf::mul_mod(u, key[d][1], m), m);
+            }
+        if constexpr (FIRST) { *p0 = hxf::lt_mac(acc0, t, m); *p1 = hxf::lt_mac(acc1, t, m); }
+        else { *p0 = hxf::lt_mac_acc(acc0, t, prev0, m); *p1 = hxf::lt_mac_acc(acc1, t, prev1, m); }   // plain stores: the next rotation reads them
+    }
+}
+
 // step 4: s'_k = INTT_{q_sp}(prod[k][special]) + floor(q_sp/2)  (mod q_sp), canonical
 template <int LOGN, int LOGE, int LAZY>
 __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ksf_intt_sp(KsArgsF a) {
@@ -689,6 +733,76 @@ int hx_launch_rotate_hoisted(hexl_ks_plan* const* plans, const u64* galois_elts,
             if (int rc = hx_with_f64_geom(p0->logn, ksf_lazy(plans[r]), [&](auto N, auto E, auto Z) { return run_hoist_down<N, E, Z>(c, a, g); }))
                 return rc;
         }
+    }
+    return 0;
+}
+
+// ---- linear transform (hexl_linear_transform): the hoisted rotations with their plaintext weights, summed BEFORE the mod-down ----
+// step 3 of one rotation of one chunk: its term goes into prod (`first`: prod is written)
+template <int LOGN, int LOGE>
+static int run_lt_mac(hexl_ctx* c, const KsArgsF& a, u32 g, const u64* d_pt, bool first) {
+    using G = Geom<LOGN, LOGE>;
+    const u32 L = a.L, nb = a.nb;
+    const u32 by = nb < 8 ? nb : 8;                                // as run_chunk_f64
+    const HoistGeom h{LOGN, LOGE, G::KL, G::WB, g};
+    const u32 wg = G::KL + 4 > 8 ? 1u << (G::KL + 4) : 256u;       // as run_hoist_down: whole 128-byte lines per workgroup
+    const dim3 grid((L + 1) * G::N / wg, by), block(wg);
+    if (L <= 8) {
+        if (first) hipLaunchKernelGGL((k_ksf_mac_galois_pt<8, true>), grid, block, 0, c->stream, a, h, d_pt);
+        else       hipLaunchKernelGGL((k_ksf_mac_galois_pt<8, false>), grid, block, 0, c->stream, a, h, d_pt);
+    } else {
+        if (first) hipLaunchKernelGGL((k_ksf_mac_galois_pt<16, true>), grid, block, 0, c->stream, a, h, d_pt);
+        else       hipLaunchKernelGGL((k_ksf_mac_galois_pt<16, false>), grid, block, 0, c->stream, a, h, d_pt);
+    }
+    return (int)hipGetLastError();
+}
+
+// steps 4-7 of one chunk, once for all rotations: the keyswitch's own kernels on the accumulated prod
+template <int LOGN, int LOGE, int LAZY>
+static int run_lt_down(hexl_ctx* c, const KsArgsF& a) {
+    using G = Geom<LOGN, LOGE>;
+    if (int rc = hx_lds_optin<k_ksf_intt_sp<LOGN, LOGE, LAZY>, k_ksf_moddown<LOGN, LOGE, LAZY>>(c->device, G::LDS_USED)) return rc;
+    hipLaunchKernelGGL((k_ksf_intt_sp<LOGN, LOGE, LAZY>), dim3(a.nb * 2), dim3(G::T), G::LDS_USED, c->stream, a);
+    hipLaunchKernelGGL((k_ksf_moddown<LOGN, LOGE, LAZY>), dim3(a.nb * a.L * 2), dim3(G::T), G::LDS_USED, c->stream, a);
+    return (int)hipGetLastError();
+}
+
+// Arguments checked by hexl_linear_transform (ckks_ops.hip). One lane on the context's stream, as hx_launch_rotate_hoisted; per chunk:
+// the shared mod-up, the plaintext-weighted c0 / identity terms into d_out (hx_launch_galois_c0_pt), one multiply-accumulate launch per
+// rotation into plans[0]'s prod, then the special-prime inverse and the mod-down ONCE, added into d_out.
+int hx_launch_linear_transform(hexl_ks_plan* const* plans, const u64* galois_elts, const u64* const* d_pts, size_t n_rot,
+                               const u64* d_pt_identity, u64* d_out, const u64* d_ct, size_t batch) {
+    hexl_ks_plan* p0 = plans[0];
+    hexl_ctx* c = p0->ctx;
+    const size_t n = p0->n, L = p0->L, per = 2 * L * n;
+    const size_t chunk = hx_ks_chunk_of(p0, batch);
+    if (int rc = hx_grow_device((void**)&p0->d_scratch, &p0->cap, chunk, hexl_ks_scratch_bytes(p0, 1), nullptr)) return rc;
+    // the per-call table of the c0 kernel. The source is pageable host memory: the copy has left it when hipMemcpyAsync returns, and
+    // the stream orders it behind the previous call's kernels that read the table
+    std::vector<HxLtRot> table(n_rot);
+    for (size_t r = 0; r < n_rot; ++r) table[r] = HxLtRot{d_pts[r], galois_elts[r]};
+    if (int rc = hx_reserve_device(c, &c->d_shared, &c->d_shared_bytes, n_rot * sizeof(HxLtRot))) return rc;
+    HX_CHECK(hipMemcpyAsync(c->d_shared, table.data(), n_rot * sizeof(HxLtRot), hipMemcpyHostToDevice, c->stream));
+    p0->cur = c->stream;
+    p0->cur_scratch = p0->d_scratch;
+    const int lazy = ksf_lazy(p0);
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t nb = batch - b0 < chunk ? batch - b0 : chunk;
+        const u64* ct = d_ct + b0 * per;
+        u64* out = d_out + b0 * per;
+        const KsArgsF up = ksf_args(p0, p0, nullptr, ct + L * n, nb);
+        if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto Z) { return run_hoist_up<N, E, Z>(c, up); })) return rc;
+        if (int rc = hx_launch_galois_c0_pt(p0, out, ct, (const HxLtRot*)c->d_shared, n_rot, d_pt_identity, nb)) return rc;
+        for (size_t r = 0; r < n_rot; ++r) {
+            const KsArgsF a = ksf_args(plans[r], p0, nullptr, nullptr, nb);          // plan r's keys, plans[0]'s scratch
+            if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto) {
+                    return run_lt_mac<decltype(N)::value, decltype(E)::value>(c, a, (u32)galois_elts[r], d_pts[r], r == 0);
+                }))
+                return rc;
+        }
+        KsArgsF down = ksf_args(p0, p0, out, nullptr, nb);
+        down.overwrite = 0;                                        // accumulated into what the c0 kernel wrote
+        if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto Z) { return run_lt_down<N, E, Z>(c, down); })) return rc;
     }
     return 0;
 }

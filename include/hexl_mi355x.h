@@ -176,6 +176,44 @@ int hexl_rotate(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_ct, size_
  * (hexl_ks_range_check) is raised on plans[0] only. */
 int hexl_rotate_hoisted(hexl_ks_plan* const* plans, const uint64_t* galois_elts, size_t n_rot, uint64_t* const* d_outs,
                         const uint64_t* d_ct, size_t batch);
+/* Linear transform ("double hoisting"): the whole loop rotate -> multiply_plain -> accumulate of the diagonal method in one call,
+ *   d_out = sum_r pt_r . Rotate_{g_r}(ct) + pt_id . ct,
+ * with the mod-up shared as in hexl_rotate_hoisted AND the mod-down shared: the plaintexts are also known modulo the special prime, so
+ * they are multiplied in before the mod-down, the sum over the rotations is taken in the extended basis q_0 ... q_{L-1}, q_sp, and the
+ * special-prime inverse and the mod-down run once -- L*L + 3L + 2 transforms per instance whatever n_rot is, against
+ * (L*L + L) + n_rot (2L + 2) for hexl_rotate_hoisted. The n_rot rotated ciphertexts never exist in memory.
+ *   plans[r], galois_elts[r]   as for hexl_rotate_hoisted, under the same matching rules (below)
+ *   d_pts           HOST array of n_rot DEVICE pointers, each [L + 1][n]: row i < L is the plaintext modulo q_i, row L the plaintext
+ *                   modulo the special prime (plan modulus K - 1); NTT form in the transforms' output order, every word below its
+ *                   modulus; one plaintext serves every instance of the batch. When K = L + 1 this is exactly what
+ *                   hexl_rns_ntt_fwd(plan, ..., count = 1, n_limbs = K) writes.
+ *   d_pt_identity   NULL, or a device [L][n] plaintext for the un-rotated term pt_id . (c0, c1) -- the g = 1 diagonal, which needs no key
+ *   d_ct, d_out     [batch][2][L][n]; d_out is WRITTEN
+ * Per instance, every line modulo its limb's modulus and every output word canonical:
+ *   u[d][slot]    = the keyswitch's mod-up of c1 (as above), slot = 0 ... L-1 and the special prime
+ *   acc[k][slot]  = sum_r pt_r[slot] . ( sum_d sigma_{g_r}(u[d][slot]) . key_r[d][k][slot] )
+ *   s'_k          = (INTT_sp(acc[k][sp]) + floor(q_sp / 2)) mod q_sp
+ *   out[0][i]     = sum_r pt_r[i] . sigma_{g_r}(c0[i]) + pt_id[i] . c0[i] + (acc[0][i] - NTT_i((s'_0 + fix_i) mod q_i)) . msf_i
+ *   out[1][i]     =                                      pt_id[i] . c1[i] + (acc[1][i] - NTT_i((s'_1 + fix_i) mod q_i)) . msf_i
+ * sigma_g, fix_i and msf_i are those of hexl_rotate_hoisted; the pt_id terms are absent when d_pt_identity is NULL. With n_rot = 1, no
+ * identity term and a plaintext whose every word is 1 the output is word for word hexl_rotate_hoisted's.
+ * NOT word-identical to hexl_rotate_hoisted -> hexl_multiply_plain -> accumulate in general: that composition divides by q_sp and
+ * rounds once per rotation and multiplies the rounded words, this call rounds the weighted sum once. The two differ by the plaintext-
+ * weighted rounding terms, each below one unit per rotation before the weight; both decrypt to the same plaintext, this call with no
+ * more noise (one rounding error instead of the sum of n_rot weighted ones).
+ * Plans: all of one context, with the same n, L, K and moduli; FP64 plans only (every modulus < 2^52), n = 1024 ... 32768; every plan
+ * with keys (else HEXL_E_NOKEYS); equal twiddles across the plans are the caller's responsibility. The same g, or the same plan, may
+ * appear more than once.
+ * HEXL_E_BADARG: a null pointer in the arguments or in plans / d_pts (d_pt_identity excepted), n_rot == 0, a plan that does not match
+ * plans[0] or runs on the integer kernels, a g that is even or >= 2n, d_out overlapping d_ct, any d_pts[r] or d_pt_identity, a size
+ * that overflows. batch == 0 returns 0 after these checks and writes nothing.
+ * Asynchronous on the context's stream (one lane; the stream contract of hexl_ctx_set_stream holds as for any single launch); the
+ * three host arrays may be reused as soon as the call returns. The input-range flag (hexl_ks_range_check) is raised on plans[0] for a
+ * ciphertext word that is not below its modulus; plaintext words below their modulus are a precondition and are not flagged.
+ * Device memory: plans[0]'s keyswitch scratch, grown and used as by hexl_rotate_hoisted (its multiply-accumulate output is the
+ * accumulator), and n_rot x 16 bytes of the context's grow-only table space; nothing else is allocated. */
+int hexl_linear_transform(hexl_ks_plan* const* plans, const uint64_t* galois_elts, const uint64_t* const* d_pts, size_t n_rot,
+                          const uint64_t* d_pt_identity, uint64_t* d_out, const uint64_t* d_ct, size_t batch);
 /* Domain changes and the plaintext product for ciphertexts that live on the device: the ends of a flow (encode / encrypt need the
  * forward transform, decrypt / decode the inverse) and the multiplier of a linear layer (rotate -> multiply_plain -> accumulate).
  * All three are asynchronous on the context's stream, need no keys and keep no device memory in the plan. FP64 plans only (every
