@@ -57,6 +57,9 @@ C_ABI = {
     "hexl_rotate": [_vp, _vp, _vp, _sz, _u64],
     "hexl_rotate_hoisted": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz, ctypes.POINTER(_vp), _vp, _sz],
     "hexl_linear_transform": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_vp), _sz, _vp, _vp, _vp, _sz],
+    "hexl_linear_transform_bsgs": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz, ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz,
+                                   ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _sz],
+    "hexl_lt_bsgs_scratch_bytes": [_vp, _sz, _sz],
     "hexl_rns_ntt_fwd": [_vp, _vp, _vp, _sz, _u64],
     "hexl_rns_ntt_inv": [_vp, _vp, _vp, _sz, _u64],
     "hexl_multiply_plain": [_vp, _vp, _vp, _vp, _sz, _u64, _u64, _sz, _i],
@@ -101,7 +104,7 @@ def lib() -> ctypes.CDLL:
         for name, args in C_ABI.items():
             fn = getattr(_lib, name)
             fn.argtypes = args
-            fn.restype = _sz if name == "hexl_ks_scratch_bytes" else _i
+            fn.restype = _sz if name in ("hexl_ks_scratch_bytes", "hexl_lt_bsgs_scratch_bytes") else _i
     return _lib
 
 
@@ -307,7 +310,38 @@ def linear_transform(plans, galois_elts, pts, out, ct, batch: int, pt_identity=N
                                        _ptr(ct), batch), "hexl_linear_transform")
 
 
+def _opt_ptrs(items):
+    """ctypes array of pointers with None entries as NULL"""
+    return (_vp * len(items))(*[None if a is None else _ptr(a) for a in items])
+
+
+def linear_transform_bsgs(baby_plans, baby_elts, giant_plans, giant_elts, pts, out, ct, batch: int, pt_identity=None):
+    """out[batch][2][L][n] = sum_j Rotate_G_j( sum_i pts[j][i] . Rotate_g_i(ct) + pt_identity[j] . ct ) with g_i = baby_elts[i] and the
+    keys of baby_plans[i], G_j = giant_elts[j] and the keys of giant_plans[j] (hexl_linear_transform_bsgs): n_baby + n_giant key passes
+    instead of n_baby * n_giant. pts is a list of n_giant rows of n_baby entries, each None (an absent diagonal) or [L + 1][n] as for
+    linear_transform, already rotated by G_j^-1; pt_identity is None or a list of n_giant entries, each None or [L][n]. A baby plan whose
+    column is empty and a giant plan with G_j = 1 may be None. Word for word linear_transform per row -> rotate_hoisted -> sum; the
+    scratch, the buffers and the range flag are the first plan's."""
+    n_baby, n_giant = len(baby_plans), len(giant_plans)
+    if len(baby_elts) != n_baby or len(giant_elts) != n_giant or len(pts) != n_giant or any(len(row) != n_baby for row in pts):
+        raise ValueError("linear_transform_bsgs: one element per plan and n_giant rows of n_baby plaintexts")
+    if pt_identity is not None and len(pt_identity) != n_giant:
+        raise ValueError("linear_transform_bsgs: one identity plaintext (or None) per giant step")
+    handles = lambda plans: (_vp * len(plans))(*[None if p is None else p.h.value for p in plans])
+    flat = [p for row in pts for p in row]
+    _check(lib().hexl_linear_transform_bsgs(handles(baby_plans), (_u64 * n_baby)(*[int(g) for g in baby_elts]), n_baby,
+                                            handles(giant_plans), (_u64 * n_giant)(*[int(g) for g in giant_elts]), n_giant,
+                                            _opt_ptrs(flat), None if pt_identity is None else _opt_ptrs(pt_identity), _ptr(out), _ptr(ct),
+                                            batch), "hexl_linear_transform_bsgs")
+
+
+def lt_bsgs_scratch_bytes(plan, n_baby: int, batch: int) -> int:
+    """device bytes a linear_transform_bsgs call with `plan` first holds on it: baby store, inner result and keyswitch scratch"""
+    return lib().hexl_lt_bsgs_scratch_bytes(plan.h, n_baby, batch)
+
+
 from .host_api import HexlFpga  # noqa: E402  (mirror of host/inc/hexl-fpga.h)
 
-__all__ = ["Context", "KeySwitchPlan", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform", "C_ABI",
+__all__ = ["Context", "KeySwitchPlan", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform",
+           "linear_transform_bsgs", "lt_bsgs_scratch_bytes", "C_ABI",
            "LIB_PATH", "ROOT"]

@@ -337,6 +337,8 @@ extern "C" int hexl_ks_plan_destroy(hexl_ks_plan* p) {
     if (p->d_rescale) (void)hipFree(p->d_rescale);
     if (p->d_rs_s) (void)hipFree(p->d_rs_s);
     if (p->d_rot_t) (void)hipFree(p->d_rot_t);
+    if (p->d_bsgs_b) (void)hipFree(p->d_bsgs_b);
+    if (p->d_bsgs_t) (void)hipFree(p->d_bsgs_t);
     delete p;
     return 0;
 }

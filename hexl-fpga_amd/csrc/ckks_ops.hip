@@ -252,6 +252,46 @@ int hx_launch_galois_c0_pt(hexl_ks_plan* p, u64* d_out, const u64* d_ct, const H
     return (int)hipGetLastError();
 }
 
+// ---- the giant steps of hexl_linear_transform_bsgs from the second on: the key-free part is ADDED to what the earlier steps left ----
+//     out[b][k][i][j] = (out[b][k][i][j] + t[b][k][i][galois_src(j)]) mod q_i     for k < n_comp; component 1 is left alone when n_comp = 1
+// n_comp = 1, g != 1: sigma_g(t[0]) of a rotated giant step (its mod-down then accumulates on top, as after k_galois<., C0_ONLY>);
+// n_comp = 2, g = 1: a giant step without a rotation, t itself. Both operands are canonical words (outputs of the mod-down or of
+// k_galois_c0_pt), so one conditional subtraction of the integer modulus keeps the sum canonical; the plan's moduli are below 2^52 and
+// exact as doubles. Workgroups and lanes as k_galois_c0_pt: (component, limb, 512-word piece, instance), the instance fastest, two
+// adjacent words per lane, the gather through L2.
+struct GaloisAddArgs {
+    const KsModF64* mods;       // [K]
+    const u64* t;               // [nb][2][L][n]
+    u64* out;                   // [nb][2][L][n]
+    u32 nb, L, logn, g;
+};
+
+__global__ __launch_bounds__(GPT_THREADS) void k_galois_add(GaloisAddArgs a) {
+    typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
+    const u32 n = 1u << a.logn;
+    const u32 b = blockIdx.x % a.nb, kic = blockIdx.x / a.nb;     // ((k * L + i) * pieces + piece) * nb + b
+    const u32 ki = kic >> (a.logn - GPT_LOG_CHUNK), piece = kic & ((1u << (a.logn - GPT_LOG_CHUNK)) - 1);
+    const u32 j = (piece << GPT_LOG_CHUNK) + 2 * threadIdx.x;
+    const u64 q = (u64)a.mods[ki % a.L].m.p;
+    const size_t row = (size_t(b) * 2 * a.L + ki) * n;
+    const u64* src = a.t + row;
+    u2 o = *reinterpret_cast<const u2*>(a.out + row + j);
+    const u64 w[2] = {src[galois_src(j, a.logn, a.g)], src[galois_src(j + 1, a.logn, a.g)]};
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const u64 s = o[e] + w[e];
+        o[e] = s >= q ? s - q : s;
+    }
+    *reinterpret_cast<u2*>(a.out + row + j) = o;
+}
+
+int hx_launch_galois_add(hexl_ks_plan* p, u64* d_out, const u64* d_t, size_t nb, u32 g, u32 n_comp) {
+    if (!nb) return 0;
+    const GaloisAddArgs a{p->d_mods_f64, d_t, d_out, (u32)nb, p->L, p->logn, g};
+    hipLaunchKernelGGL(k_galois_add, dim3((u32)(nb * n_comp * p->L * (p->n >> GPT_LOG_CHUNK))), dim3(GPT_THREADS), 0, p->ctx->stream, a);
+    return (int)hipGetLastError();
+}
+
 // ---- rescale ----
 template <int LOGN, int LOGE, int LAZY>
 static int run_rescale(hexl_ks_plan* p, const RsArgs& a, u32 nb, u32 ncomp) {
@@ -424,4 +464,50 @@ extern "C" int hexl_linear_transform(hexl_ks_plan* const* plans, const uint64_t*
     if (!batch) return 0;
     HX_CHECK(hipSetDevice(p0->ctx->device));
     return hx_launch_linear_transform(plans, galois_elts, d_pts, n_rot, d_pt_identity, d_out, d_ct, batch);
+}
+
+extern "C" int hexl_linear_transform_bsgs(hexl_ks_plan* const* baby_plans, const uint64_t* baby_elts, size_t n_baby,
+                                          hexl_ks_plan* const* giant_plans, const uint64_t* giant_elts, size_t n_giant,
+                                          const uint64_t* const* d_pts, const uint64_t* const* d_pt_identity, uint64_t* d_out,
+                                          const uint64_t* d_ct, size_t batch) {
+    if (!baby_plans || !baby_elts || !giant_plans || !giant_elts || !d_pts || !d_out || !d_ct || !n_giant) return HEXL_E_BADARG;
+    if (n_giant > SIZE_MAX / sizeof(HxLtRot) / 2 || (n_baby && n_giant > SIZE_MAX / sizeof(HxLtRot) / 2 / n_baby)) return HEXL_E_BADARG;
+    // the plan that lends scratch, buffers, tier and range flag: baby_plans[0] whenever there is one
+    hexl_ks_plan* p0 = nullptr;
+    for (size_t i = 0; i < n_baby && !p0; ++i) p0 = baby_plans[i];
+    for (size_t j = 0; j < n_giant && !p0; ++j) p0 = giant_plans[j];
+    if (!p0) return HEXL_E_BADARG;
+    if (!p0->use_f64 || p0->logn < 10 || p0->logn > 15) return HEXL_E_BADARG;     // as hexl_rotate_hoisted
+    const size_t row = size_t(p0->L) * p0->n * sizeof(u64), per = 2 * row;
+    if (batch > SIZE_MAX / per) return HEXL_E_BADARG;
+    if (n_baby > HX_LT_BSGS_STORE_BYTES / (2 * (row + p0->n * sizeof(u64)))) return HEXL_E_BADARG;   // not one instance would fit the baby store
+    const size_t bytes = batch * per, pt_bytes = row + p0->n * sizeof(u64);       // [L + 1][n]
+    if (hx_ranges_overlap(d_out, bytes, d_ct, bytes)) return HEXL_E_BADARG;
+    auto matches = [&](const hexl_ks_plan* p) {
+        return p->ctx == p0->ctx && p->n == p0->n && p->L == p0->L && p->K == p0->K && p->use_f64 && p->moduli == p0->moduli;
+    };
+    for (size_t i = 0; i < n_baby; ++i)
+        if ((baby_plans[i] && !matches(baby_plans[i])) || !galois_elt_ok(baby_elts[i], p0->n)) return HEXL_E_BADARG;
+    for (size_t j = 0; j < n_giant; ++j) {
+        if ((giant_plans[j] && !matches(giant_plans[j])) || !galois_elt_ok(giant_elts[j], p0->n)) return HEXL_E_BADARG;
+        if (!giant_plans[j] && giant_elts[j] != 1) return HEXL_E_BADARG;
+        const u64* pt_id = d_pt_identity ? d_pt_identity[j] : nullptr;
+        if (pt_id && hx_ranges_overlap(d_out, bytes, pt_id, row)) return HEXL_E_BADARG;
+        bool any = pt_id != nullptr;
+        for (size_t i = 0; i < n_baby; ++i)
+            if (const u64* pt = d_pts[j * n_baby + i]) {
+                if (!baby_plans[i] || hx_ranges_overlap(d_out, bytes, pt, pt_bytes)) return HEXL_E_BADARG;
+                any = true;
+            }
+        if (!any) return HEXL_E_BADARG;                             // a giant row with no term at all
+    }
+    for (size_t j = 0; j < n_giant; ++j) {
+        if (giant_elts[j] != 1 && !giant_plans[j]->have_keys) return HEXL_E_NOKEYS;
+        for (size_t i = 0; i < n_baby; ++i)
+            if (d_pts[j * n_baby + i] && !baby_plans[i]->have_keys) return HEXL_E_NOKEYS;
+    }
+    if (!batch) return 0;
+    HX_CHECK(hipSetDevice(p0->ctx->device));
+    return hx_launch_linear_transform_bsgs(p0, baby_plans, baby_elts, n_baby, giant_plans, giant_elts, n_giant, d_pts, d_pt_identity, d_out,
+                                           d_ct, batch);
 }

@@ -315,6 +315,42 @@ __global__ __launch_bounds__(512) void k_ksf_mac_galois_pt(KsArgsF a, HoistGeom 
     }
 }
 
+// step 3 of one giant step of a baby-step/giant-step linear transform (hexl_linear_transform_bsgs):
+//     prod[b][k][slot] = sum_i pt_{j,i}[slot] . B_i[b][k][slot]
+// B_i is what k_ksf_mac_galois (k_ksf_mac for g = 1) stored for baby step i: sum_d sigma_{g_i}(u[b][slot][d]) . key_i[d][k][slot], the
+// inner sum of k_ksf_mac_galois_pt, computed once per chunk instead of once per giant step. No keys, no gather: a thread owns NTT-output
+// index j of one slot as k_ksf_mac_galois_pt does (gid = slot * n + j), reads its plaintext word pt[slot][j] (plain order, coalesced in
+// j) and the two stored words at posB(j) per term of the per-call table, keeps both accumulators in registers across the terms and
+// writes prod once -- no read-modify-write of prod per rotation. The plaintext words come from L2 from the second instance on.
+// The scalar chain is k_ksf_mac_galois_pt's unchanged -- lt_pt, lt_mac for the first term, lt_mac_acc after it -- and its inner operand
+// is, as there, an output of reduce (the last operation of the stored multiply-accumulate): the bound chain of f64_arith.hpp and its
+// host replay (tests/cpp/lt_mac_selftest.cpp) cover this kernel as they stand.
+struct HxBsgsTerm { const u64* pt; const double* B; };           // pt: [L + 1][n]; B: baby step's slice [nb][2][L + 1][n], B order
+
+__global__ __launch_bounds__(256) void k_lt_bsgs_sum(KsArgsF a, HoistGeom h, const HxBsgsTerm* terms, u32 n_terms) {
+    const u32 L = a.L, n = 1u << h.logn;
+    const u32 gid = blockIdx.x * blockDim.x + threadIdx.x;        // (slot, j)
+    const u32 slot = gid >> h.logn;
+    if (slot > L) return;
+    const u32 pos = posB(gid & (n - 1), h);
+    const u32 i = slot < L ? slot : a.K - 1;
+    const Mod m = a.mods[i].m;
+    for (u32 b = blockIdx.y; b < a.nb; b += gridDim.y) {
+        const size_t o0 = ((size_t(b) * 2 + 0) * (L + 1) + slot) * n + pos, o1 = ((size_t(b) * 2 + 1) * (L + 1) + slot) * n + pos;
+        const HxBsgsTerm first = terms[0];                        // uniform: scalar loads
+        const double t0 = hxf::lt_pt(hxf::to_f64(first.pt[gid]), m);
+        double acc0 = hxf::lt_mac(first.B[o0], t0, m), acc1 = hxf::lt_mac(first.B[o1], t0, m);
+        for (u32 r = 1; r < n_terms; ++r) {
+            const HxBsgsTerm term = terms[r];
+            const double t = hxf::lt_pt(hxf::to_f64(term.pt[gid]), m);
+            acc0 = hxf::lt_mac_acc(term.B[o0], t, acc0, m);
+            acc1 = hxf::lt_mac_acc(term.B[o1], t, acc1, m);
+        }
+        __builtin_nontemporal_store(acc0, a.prod + o0);           // streamed to k_ksf_intt_sp / k_ksf_moddown, as k_ksf_mac_galois
+        __builtin_nontemporal_store(acc1, a.prod + o1);
+    }
+}
+
 // step 4: s'_k = INTT_{q_sp}(prod[k][special]) + floor(q_sp/2)  (mod q_sp), canonical
 template <int LOGN, int LOGE, int LAZY>
 __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ksf_intt_sp(KsArgsF a) {
@@ -684,11 +720,10 @@ static int run_hoist_up(hexl_ctx* c, const KsArgsF& a) {
     return (int)hipGetLastError();
 }
 
-// steps 3-7 of one rotation of one chunk: sigma_g inside the multiply-accumulate, then the keyswitch's own steps 4-7
-template <int LOGN, int LOGE, int LAZY>
-static int run_hoist_down(hexl_ctx* c, const KsArgsF& a, u32 g) {
+// step 3 of one rotation of one chunk into a.prod: sigma_g inside the multiply-accumulate
+template <int LOGN, int LOGE>
+static int run_hoist_mac(hexl_ctx* c, const KsArgsF& a, u32 g) {
     using G = Geom<LOGN, LOGE>;
-    if (int rc = hx_lds_optin<k_ksf_intt_sp<LOGN, LOGE, LAZY>, k_ksf_moddown<LOGN, LOGE, LAZY>>(c->device, G::LDS_USED)) return rc;
     const u32 L = a.L, nb = a.nb;
     const u32 by = nb < 8 ? nb : 8;                                // as run_chunk_f64
     if (g == 1) {                                                  // the identity: the keyswitch's own step 3
@@ -702,6 +737,16 @@ static int run_hoist_down(hexl_ctx* c, const KsArgsF& a, u32 g) {
         if (L <= 8) hipLaunchKernelGGL((k_ksf_mac_galois<8>), dim3((L + 1) * G::N / wg, by), dim3(wg), 0, c->stream, a, h);
         else        hipLaunchKernelGGL((k_ksf_mac_galois<16>), dim3((L + 1) * G::N / wg, by), dim3(wg), 0, c->stream, a, h);
     }
+    return (int)hipGetLastError();
+}
+
+// steps 3-7 of one rotation of one chunk: the multiply-accumulate above, then the keyswitch's own steps 4-7
+template <int LOGN, int LOGE, int LAZY>
+static int run_hoist_down(hexl_ctx* c, const KsArgsF& a, u32 g) {
+    using G = Geom<LOGN, LOGE>;
+    if (int rc = hx_lds_optin<k_ksf_intt_sp<LOGN, LOGE, LAZY>, k_ksf_moddown<LOGN, LOGE, LAZY>>(c->device, G::LDS_USED)) return rc;
+    const u32 L = a.L, nb = a.nb;
+    if (int rc = run_hoist_mac<LOGN, LOGE>(c, a, g)) return rc;
     hipLaunchKernelGGL((k_ksf_intt_sp<LOGN, LOGE, LAZY>), dim3(nb * 2), dim3(G::T), G::LDS_USED, c->stream, a);
     hipLaunchKernelGGL((k_ksf_moddown<LOGN, LOGE, LAZY>), dim3(nb * L * 2), dim3(G::T), G::LDS_USED, c->stream, a);
     return (int)hipGetLastError();
@@ -803,6 +848,127 @@ int hx_launch_linear_transform(hexl_ks_plan* const* plans, const u64* galois_elt
         KsArgsF down = ksf_args(p0, p0, out, nullptr, nb);
         down.overwrite = 0;                                        // accumulated into what the c0 kernel wrote
         if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto Z) { return run_lt_down<N, E, Z>(c, down); })) return rc;
+    }
+    return 0;
+}
+
+// ---- baby-step/giant-step linear transform (hexl_linear_transform_bsgs): out = sum_j Rot_{G_j}( sum_i pt_{j,i} . Rot_{g_i}(ct) ) ----
+// one giant step's step 3: the weighted sum of the stored baby products into a.prod, no keys
+template <int LOGN, int LOGE>
+static int run_lt_bsgs_sum(hexl_ctx* c, const KsArgsF& a, const HxBsgsTerm* d_terms, u32 n_terms) {
+    using G = Geom<LOGN, LOGE>;
+    const HoistGeom h{LOGN, LOGE, G::KL, G::WB, 1};
+    const u32 by = a.nb < 8 ? a.nb : 8;                            // as run_chunk_f64
+    hipLaunchKernelGGL(k_lt_bsgs_sum, dim3((a.L + 1) * G::N / 256, by), dim3(256), 0, c->stream, a, h, d_terms, n_terms);
+    return (int)hipGetLastError();
+}
+
+static size_t bsgs_slice_bytes(const hexl_ks_plan* p) { return 2 * (size_t(p->L) + 1) * p->n * sizeof(double); }   // one baby step, one instance
+size_t hx_lt_bsgs_chunk(const hexl_ks_plan* p, size_t n_baby, size_t batch) {
+    const size_t chunk = hx_ks_chunk_of(p, batch);
+    if (hx_knob("HEXL_KS_CHUNK", 0) > 0 || !n_baby || !chunk) return chunk;      // a forced chunk stays
+    const size_t fit = HX_LT_BSGS_STORE_BYTES / bsgs_slice_bytes(p) / n_baby;
+    return fit >= chunk ? chunk : fit ? fit : 1;
+}
+size_t hexl_lt_bsgs_scratch_bytes(const hexl_ks_plan* p, size_t n_baby, size_t batch) {
+    if (!p) return 0;
+    const size_t chunk = hx_lt_bsgs_chunk(p, n_baby, batch);
+    const size_t fixed = 2 * size_t(p->L) * p->n * sizeof(u64) + hexl_ks_scratch_bytes(p, 1);   // t_j and the keyswitch scratch, per instance
+    if (chunk && n_baby > (SIZE_MAX / chunk - fixed) / bsgs_slice_bytes(p)) return SIZE_MAX;
+    return chunk * (n_baby * bsgs_slice_bytes(p) + fixed);
+}
+
+// Arguments checked by hexl_linear_transform_bsgs (ckks_ops.hip). One lane on the context's stream; per chunk:
+//   the mod-up of c1 once; one multiply-accumulate per baby step that some row uses, its prod pointed at that step's slice of the baby store
+//   (u is free after the last of them);
+//   per giant step j: the key-free part of row j into t_j (hx_launch_galois_c0_pt), the weighted sum of the stored products into prod
+//   (k_lt_bsgs_sum) and the mod-down ONCE, added into t_j -- hexl_linear_transform's words for row j; then t_j rotated by G_j as
+//   hexl_rotate_hoisted rotates it (mod-up of t_j's component 1 into the same u, giant_plans[j]'s keys) with the key-free part
+//   sigma_{G_j}(t_j[0]) WRITTEN to d_out by the first giant step and ADDED by the later ones, and the mod-down accumulating on top.
+//   G_j = 1: t_j itself is written (the first giant step computes it in place in d_out) or added.
+// Every word that reaches d_out is canonical and every addition is modulo q_i, so d_out holds the sum of the per-row results of the
+// two parent entry points, word for word.
+int hx_launch_linear_transform_bsgs(hexl_ks_plan* p0, hexl_ks_plan* const* baby_plans, const u64* baby_elts, size_t n_baby,
+                                    hexl_ks_plan* const* giant_plans, const u64* giant_elts, size_t n_giant, const u64* const* d_pts,
+                                    const u64* const* d_pt_identity, u64* d_out, const u64* d_ct, size_t batch) {
+    hexl_ctx* c = p0->ctx;
+    const size_t n = p0->n, L = p0->L, per = 2 * L * n, slice = 2 * (L + 1) * n;
+    const size_t chunk = hx_lt_bsgs_chunk(p0, n_baby, batch);
+    if (int rc = hx_grow_device((void**)&p0->d_scratch, &p0->cap, chunk, hexl_ks_scratch_bytes(p0, 1), nullptr)) return rc;
+    if (n_baby)
+        if (int rc = hx_grow_device((void**)&p0->d_bsgs_b, &p0->bsgs_b_cap, n_baby * chunk, slice * sizeof(double), nullptr)) return rc;
+    if (int rc = hx_grow_device((void**)&p0->d_bsgs_t, &p0->bsgs_t_cap, chunk, per * sizeof(u64), nullptr)) return rc;
+    // the per-call tables, row after row: what the c0 kernel walks (plaintext, Galois element) and what the sum kernel walks (plaintext,
+    // baby slice). Pageable sources, stream-ordered behind the previous call's readers, as hx_launch_linear_transform's table
+    std::vector<HxLtRot> rots;
+    std::vector<HxBsgsTerm> terms;
+    std::vector<size_t> off(n_giant + 1);
+    std::vector<char> used(n_baby, 0);
+    for (size_t j = 0; j < n_giant; ++j) {
+        off[j] = rots.size();
+        for (size_t i = 0; i < n_baby; ++i)
+            if (const u64* pt = d_pts[j * n_baby + i]) {
+                rots.push_back(HxLtRot{pt, baby_elts[i]});
+                terms.push_back(HxBsgsTerm{pt, p0->d_bsgs_b + i * chunk * slice});
+                used[i] = 1;
+            }
+    }
+    const size_t total = off[n_giant] = rots.size();
+    static_assert(sizeof(HxLtRot) == 16 && sizeof(HxBsgsTerm) == 16, "the two tables share one 16-byte-aligned reservation");
+    if (total) {
+        if (int rc = hx_reserve_device(c, &c->d_shared, &c->d_shared_bytes, total * (sizeof(HxLtRot) + sizeof(HxBsgsTerm)))) return rc;
+        HX_CHECK(hipMemcpyAsync(c->d_shared, rots.data(), total * sizeof(HxLtRot), hipMemcpyHostToDevice, c->stream));
+        HX_CHECK(hipMemcpyAsync((HxLtRot*)c->d_shared + total, terms.data(), total * sizeof(HxBsgsTerm), hipMemcpyHostToDevice, c->stream));
+    }
+    const HxLtRot* d_rots = (const HxLtRot*)c->d_shared;
+    const HxBsgsTerm* d_terms = (const HxBsgsTerm*)(d_rots + total);
+    p0->cur = c->stream;
+    p0->cur_scratch = p0->d_scratch;
+    const int lazy = ksf_lazy(p0);
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t nb = batch - b0 < chunk ? batch - b0 : chunk;
+        const u64* ct = d_ct + b0 * per;
+        u64* out = d_out + b0 * per;
+        if (total) {
+            const KsArgsF up = ksf_args(p0, p0, nullptr, ct + L * n, nb);
+            if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto Z) { return run_hoist_up<N, E, Z>(c, up); })) return rc;
+            for (size_t i = 0; i < n_baby; ++i) {
+                if (!used[i]) continue;
+                KsArgsF a = ksf_args(baby_plans[i], p0, nullptr, nullptr, nb);       // plan i's keys, p0's u
+                a.prod = p0->d_bsgs_b + i * chunk * slice;
+                if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto) {
+                        return run_hoist_mac<decltype(N)::value, decltype(E)::value>(c, a, (u32)baby_elts[i]);
+                    }))
+                    return rc;
+            }
+        }
+        for (size_t j = 0; j < n_giant; ++j) {
+            const size_t cnt = off[j + 1] - off[j];
+            const u32 g = (u32)giant_elts[j];
+            u64* t = (j == 0 && g == 1) ? out : p0->d_bsgs_t;
+            if (int rc = hx_launch_galois_c0_pt(p0, t, ct, d_rots + off[j], cnt, d_pt_identity ? d_pt_identity[j] : nullptr, nb)) return rc;
+            if (cnt) {
+                KsArgsF down = ksf_args(p0, p0, t, nullptr, nb);
+                down.overwrite = 0;                                // accumulated into what the c0 kernel wrote
+                if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto) {
+                        return run_lt_bsgs_sum<decltype(N)::value, decltype(E)::value>(c, down, d_terms + off[j], (u32)cnt);
+                    }))
+                    return rc;
+                if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto Z) { return run_lt_down<N, E, Z>(c, down); })) return rc;
+            }
+            if (g == 1) {
+                if (j)
+                    if (int rc = hx_launch_galois_add(p0, out, t, nb, 1, 2)) return rc;
+                continue;
+            }
+            const KsArgsF up = ksf_args(p0, p0, nullptr, t + L * n, nb);             // the babies are stored: u is free
+            if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto Z) { return run_hoist_up<N, E, Z>(c, up); })) return rc;
+            if (int rc = j ? hx_launch_galois_add(p0, out, t, nb, g, 1) : hx_launch_galois_c0(c, out, t, nb, (u32)L, p0->logn, g)) return rc;
+            KsArgsF a = ksf_args(giant_plans[j], p0, out, nullptr, nb);
+            a.overwrite = 0;
+            if (int rc = hx_with_f64_geom(p0->logn, ksf_lazy(giant_plans[j]), [&](auto N, auto E, auto Z) { return run_hoist_down<N, E, Z>(c, a, g); }))
+                return rc;
+        }
     }
     return 0;
 }

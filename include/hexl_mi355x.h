@@ -214,6 +214,52 @@ int hexl_rotate_hoisted(hexl_ks_plan* const* plans, const uint64_t* galois_elts,
  * accumulator), and n_rot x 16 bytes of the context's grow-only table space; nothing else is allocated. */
 int hexl_linear_transform(hexl_ks_plan* const* plans, const uint64_t* galois_elts, const uint64_t* const* d_pts, size_t n_rot,
                           const uint64_t* d_pt_identity, uint64_t* d_out, const uint64_t* d_ct, size_t batch);
+/* Baby-step/giant-step linear transform: the diagonal method for many diagonals in one call,
+ *   d_out = sum_j Rotate_{G_j}( sum_i pt_{j,i} . Rotate_{g_i}(ct) + pt_id_j . ct ),
+ * with n_baby + n_giant Galois keys and key multiply-accumulate passes instead of n_baby * n_giant: the mod-up of ct and the n_baby key
+ * passes run once and their outputs are kept, every giant step weights and sums the kept products without touching a key, and only the
+ * n_giant outer rotations run a keyswitch of their own.
+ *   baby_plans[i], baby_elts[i]     i < n_baby: the switching key from s(X^g_i) to s and g_i, as for hexl_linear_transform
+ *   giant_plans[j], giant_elts[j]   j < n_giant: the switching key from s(X^G_j) to s and G_j; giant_plans[j] may be NULL when G_j = 1
+ *   d_pts           HOST array of n_giant * n_baby DEVICE pointers, row-major (j, i): NULL for an absent diagonal, else a [L + 1][n]
+ *                   plaintext with the rows and the order of hexl_linear_transform's d_pts[r]. As in every baby-step/giant-step scheme
+ *                   the caller supplies diagonal (j, i) already rotated by G_j^-1: this call applies Rotate_{G_j} to the whole inner sum.
+ *   d_pt_identity   NULL, or a HOST array of n_giant entries, each NULL or a device [L][n] plaintext: the key-free baby step g = 1 of
+ *                   giant step j
+ *   d_ct, d_out     [batch][2][L][n]; d_out is WRITTEN (whatever it held)
+ * The output is fixed by the entry points above. For every giant step j
+ *   t_j = hexl_linear_transform(the baby plans, elements and plaintexts of row j that are not NULL, in the order of i,
+ *                               d_pt_identity[j], ct)        -- a row with only an identity term: t_j = pt_id_j . (c0, c1) mod q_i
+ *   r_j = t_j                                                    if G_j = 1
+ *         hexl_rotate_hoisted(&giant_plans[j], &G_j, 1, ., t_j)  otherwise
+ *   out = sum_j r_j mod q_i, every word canonical
+ * and the call is word for word that composition: both building blocks end in canonical words that depend on exact residue classes
+ * only, so neither the order of accumulation nor the fact that the baby products are stored rather than recomputed changes a word. As
+ * for the two building blocks, these are NOT the words of a route through hexl_rotate (digits lifted after the permutation there,
+ * before it here), nor of hexl_rotate_hoisted -> hexl_multiply_plain -> accumulate; all of them decrypt to the same plaintext.
+ * Plans: every non-NULL plan, baby or giant, under hexl_linear_transform's matching rules -- one context, the same n, L, K and moduli,
+ * FP64 plans only, n = 1024 ... 32768, equal twiddles the caller's responsibility. A baby plan may be NULL when no row has a plaintext
+ * in its column. Every plan that is used (a baby plan whose column has a plaintext, a giant plan with G_j != 1) needs keys, else
+ * HEXL_E_NOKEYS. The same g may serve as a baby and as a giant step, and a plan may appear more than once.
+ * HEXL_E_BADARG: a null argument (d_pt_identity excepted; the arrays are looked at even when n_baby = 0), n_giant == 0, no plan at all
+ * in the two arrays, a giant row with neither a plaintext nor an identity term, a non-NULL plan that does not match the first one or
+ * runs on the integer kernels, a NULL baby plan whose column has a plaintext, a NULL giant plan with G_j != 1, an element that is even
+ * or >= 2n (used or not), d_out overlapping d_ct, any plaintext or any identity plaintext, a size that overflows. n_baby == 0 is
+ * allowed when every row has its identity term. batch == 0 returns 0 after these checks and writes nothing.
+ * Asynchronous on the context's stream (one lane; the stream contract of hexl_ctx_set_stream holds as for any single launch); all host
+ * arrays may be reused as soon as the call returns. The input-range flag (hexl_ks_range_check) is raised on the first non-NULL plan of
+ * baby_plans, then of giant_plans -- baby_plans[0] whenever it is given -- for a word of d_ct that is not below its modulus.
+ * Device memory, all of it on that same plan and grow-only: its keyswitch scratch as for hexl_rotate_hoisted; the baby store,
+ * n_baby x chunk x 2 (L + 1) n doubles (2 MiB per baby step and instance at n = 16384, L = 7); one giant step's inner result, chunk x
+ * 2 L n words. chunk = min(batch, the keyswitch's chunk), cut down so that the baby store stays within 2 GiB (never below one
+ * instance; at n = 16384, L = 7 the full chunk of 256 up to 4 baby steps, 128 instances at 8, 64 at 16); HEXL_KS_CHUNK forces the
+ * chunk whatever the store then takes. hexl_lt_bsgs_scratch_bytes(plan, n_baby, batch) is the sum of the three for a call with that
+ * plan first (capacity planning, as hexl_ks_scratch_bytes). The context's grow-only table space takes 32 bytes per plaintext. */
+int hexl_linear_transform_bsgs(hexl_ks_plan* const* baby_plans, const uint64_t* baby_elts, size_t n_baby,
+                               hexl_ks_plan* const* giant_plans, const uint64_t* giant_elts, size_t n_giant,
+                               const uint64_t* const* d_pts, const uint64_t* const* d_pt_identity, uint64_t* d_out,
+                               const uint64_t* d_ct, size_t batch);
+size_t hexl_lt_bsgs_scratch_bytes(const hexl_ks_plan* plan, size_t n_baby, size_t batch);
 /* Domain changes and the plaintext product for ciphertexts that live on the device: the ends of a flow (encode / encrypt need the
  * forward transform, decrypt / decode the inverse) and the multiplier of a linear layer (rotate -> multiply_plain -> accumulate).
  * All three are asynchronous on the context's stream, need no keys and keep no device memory in the plan. FP64 plans only (every
