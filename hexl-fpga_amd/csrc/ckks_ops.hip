@@ -378,6 +378,21 @@ int hx_launch_rotate(hexl_ks_plan* p, u64* d_out, const u64* d_ct, size_t batch,
 // capi.hip and host_staging.hip against stubs of the launchers those two call, and needs none for these. ----
 static bool ring_dimension_ok(u64 n) { return n >= 1024 && n <= 32768 && !(n & (n - 1)); }
 static bool galois_elt_ok(u64 g, u64 n) { return (g & 1) && g < 2 * n; }
+static bool f64_ring_ok(const hexl_ks_plan* p) { return p->use_f64 && p->logn >= 10 && p->logn <= 15; }   // the (b, d)-major FP64 kernels only
+// a plan of a hoisted call works in p0's scratch with p0's geometry: same context, same FP64 ring
+static bool same_ring(const hexl_ks_plan* p, const hexl_ks_plan* p0) {
+    return p->ctx == p0->ctx && p->n == p0->n && p->L == p0->L && p->K == p0->K && p->use_f64 && p->moduli == p0->moduli;
+}
+// bytes of one component [L][n], of one ciphertext, of `batch` of them and of one plaintext [L + 1][n]; false when `bytes` overflows
+struct CtBytes { size_t row, per, bytes, pt_bytes; };
+static bool ct_bytes(const hexl_ks_plan* p0, size_t batch, CtBytes& s) {
+    s.row = size_t(p0->L) * p0->n * sizeof(u64);
+    s.per = 2 * s.row;
+    if (batch > SIZE_MAX / s.per) return false;
+    s.bytes = batch * s.per;
+    s.pt_bytes = s.row + p0->n * sizeof(u64);
+    return true;
+}
 
 extern "C" int hexl_apply_galois(hexl_ctx* c, uint64_t* d_out, const uint64_t* d_in, size_t count, uint64_t n, uint64_t g) {
     if (!c || !d_out || !d_in || !ring_dimension_ok(n) || !galois_elt_ok(g, n)) return HEXL_E_BADARG;
@@ -393,7 +408,7 @@ extern "C" int hexl_apply_galois(hexl_ctx* c, uint64_t* d_out, const uint64_t* d
 
 extern "C" int hexl_rescale(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_in, size_t batch, uint64_t n_limbs,
                             uint64_t n_components) {
-    if (!p || !d_out || !d_in || !p->use_f64 || p->logn < 10 || p->logn > 15) return HEXL_E_BADARG;
+    if (!p || !d_out || !d_in || !f64_ring_ok(p)) return HEXL_E_BADARG;
     if (n_limbs < 2 || n_limbs > p->K - 1 || n_components < 1 || n_components > 3) return HEXL_E_BADARG;
     const size_t per = size_t(n_components) * p->n * sizeof(u64);
     if (batch > SIZE_MAX / (per * n_limbs)) return HEXL_E_BADARG;
@@ -404,14 +419,16 @@ extern "C" int hexl_rescale(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_
 
 extern "C" int hexl_rotate(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t g) {
     if (!p || !d_out || !d_ct || !galois_elt_ok(g, p->n)) return HEXL_E_BADARG;
-    const size_t per = 2 * size_t(p->L) * p->n * sizeof(u64);
-    if (batch > SIZE_MAX / per) return HEXL_E_BADARG;
-    if (hx_ranges_overlap(d_out, batch * per, d_ct, batch * per)) return HEXL_E_BADARG;   // component 1 of d_out is zeroed before the keyswitch
+    CtBytes s;
+    if (!ct_bytes(p, batch, s)) return HEXL_E_BADARG;
+    if (hx_ranges_overlap(d_out, s.bytes, d_ct, s.bytes)) return HEXL_E_BADARG;   // component 1 of d_out is zeroed before the keyswitch
     if (!p->have_keys) return HEXL_E_NOKEYS;
     HX_CHECK(hipSetDevice(p->ctx->device));
     return hx_launch_rotate(p, d_out, d_ct, batch, (u32)g);
 }
 
+// The three hoisted entry points check in one order: HEXL_E_BADARG for anything malformed in any plan or buffer, then HEXL_E_NOKEYS,
+// then nothing to do for an empty batch.
 extern "C" int hexl_rotate_hoisted(hexl_ks_plan* const* plans, const uint64_t* galois_elts, size_t n_rot, uint64_t* const* d_outs,
                                    const uint64_t* d_ct, size_t batch) {
     if (!plans || !galois_elts || !d_outs || !d_ct) return HEXL_E_BADARG;
@@ -419,18 +436,13 @@ extern "C" int hexl_rotate_hoisted(hexl_ks_plan* const* plans, const uint64_t* g
     for (size_t r = 0; r < n_rot; ++r)
         if (!plans[r] || !d_outs[r]) return HEXL_E_BADARG;
     const hexl_ks_plan* p0 = plans[0];
-    if (!p0->use_f64 || p0->logn < 10 || p0->logn > 15) return HEXL_E_BADARG;     // the (b, d)-major FP64 kernels only
-    const size_t per = 2 * size_t(p0->L) * p0->n * sizeof(u64);
-    if (batch > SIZE_MAX / per) return HEXL_E_BADARG;
-    const size_t bytes = batch * per;
+    CtBytes s;
+    if (!f64_ring_ok(p0) || !ct_bytes(p0, batch, s)) return HEXL_E_BADARG;
     for (size_t r = 0; r < n_rot; ++r) {
-        const hexl_ks_plan* p = plans[r];
-        if (p->ctx != p0->ctx || p->n != p0->n || p->L != p0->L || p->K != p0->K || !p->use_f64 || p->moduli != p0->moduli)
-            return HEXL_E_BADARG;
-        if (!galois_elt_ok(galois_elts[r], p0->n)) return HEXL_E_BADARG;
-        if (hx_ranges_overlap(d_outs[r], bytes, d_ct, bytes)) return HEXL_E_BADARG;
+        if (!same_ring(plans[r], p0) || !galois_elt_ok(galois_elts[r], p0->n)) return HEXL_E_BADARG;
+        if (hx_ranges_overlap(d_outs[r], s.bytes, d_ct, s.bytes)) return HEXL_E_BADARG;
         for (size_t q = 0; q < r; ++q)
-            if (hx_ranges_overlap(d_outs[r], bytes, d_outs[q], bytes)) return HEXL_E_BADARG;
+            if (hx_ranges_overlap(d_outs[r], s.bytes, d_outs[q], s.bytes)) return HEXL_E_BADARG;
     }
     for (size_t r = 0; r < n_rot; ++r)
         if (!plans[r]->have_keys) return HEXL_E_NOKEYS;
@@ -446,18 +458,13 @@ extern "C" int hexl_linear_transform(hexl_ks_plan* const* plans, const uint64_t*
     for (size_t r = 0; r < n_rot; ++r)
         if (!plans[r] || !d_pts[r]) return HEXL_E_BADARG;
     const hexl_ks_plan* p0 = plans[0];
-    if (!p0->use_f64 || p0->logn < 10 || p0->logn > 15) return HEXL_E_BADARG;     // as hexl_rotate_hoisted
-    const size_t row = size_t(p0->L) * p0->n * sizeof(u64), per = 2 * row;
-    if (batch > SIZE_MAX / per) return HEXL_E_BADARG;
-    const size_t bytes = batch * per, pt_bytes = row + p0->n * sizeof(u64);       // [L + 1][n]
-    if (hx_ranges_overlap(d_out, bytes, d_ct, bytes)) return HEXL_E_BADARG;
-    if (d_pt_identity && hx_ranges_overlap(d_out, bytes, d_pt_identity, row)) return HEXL_E_BADARG;
+    CtBytes s;
+    if (!f64_ring_ok(p0) || !ct_bytes(p0, batch, s)) return HEXL_E_BADARG;
+    if (hx_ranges_overlap(d_out, s.bytes, d_ct, s.bytes)) return HEXL_E_BADARG;
+    if (d_pt_identity && hx_ranges_overlap(d_out, s.bytes, d_pt_identity, s.row)) return HEXL_E_BADARG;
     for (size_t r = 0; r < n_rot; ++r) {
-        const hexl_ks_plan* p = plans[r];
-        if (p->ctx != p0->ctx || p->n != p0->n || p->L != p0->L || p->K != p0->K || !p->use_f64 || p->moduli != p0->moduli)
-            return HEXL_E_BADARG;
-        if (!galois_elt_ok(galois_elts[r], p0->n)) return HEXL_E_BADARG;
-        if (hx_ranges_overlap(d_out, bytes, d_pts[r], pt_bytes)) return HEXL_E_BADARG;
+        if (!same_ring(plans[r], p0) || !galois_elt_ok(galois_elts[r], p0->n)) return HEXL_E_BADARG;
+        if (hx_ranges_overlap(d_out, s.bytes, d_pts[r], s.pt_bytes)) return HEXL_E_BADARG;
     }
     for (size_t r = 0; r < n_rot; ++r)
         if (!plans[r]->have_keys) return HEXL_E_NOKEYS;
@@ -477,26 +484,21 @@ extern "C" int hexl_linear_transform_bsgs(hexl_ks_plan* const* baby_plans, const
     for (size_t i = 0; i < n_baby && !p0; ++i) p0 = baby_plans[i];
     for (size_t j = 0; j < n_giant && !p0; ++j) p0 = giant_plans[j];
     if (!p0) return HEXL_E_BADARG;
-    if (!p0->use_f64 || p0->logn < 10 || p0->logn > 15) return HEXL_E_BADARG;     // as hexl_rotate_hoisted
-    const size_t row = size_t(p0->L) * p0->n * sizeof(u64), per = 2 * row;
-    if (batch > SIZE_MAX / per) return HEXL_E_BADARG;
-    if (n_baby > HX_LT_BSGS_STORE_BYTES / (2 * (row + p0->n * sizeof(u64)))) return HEXL_E_BADARG;   // not one instance would fit the baby store
-    const size_t bytes = batch * per, pt_bytes = row + p0->n * sizeof(u64);       // [L + 1][n]
-    if (hx_ranges_overlap(d_out, bytes, d_ct, bytes)) return HEXL_E_BADARG;
-    auto matches = [&](const hexl_ks_plan* p) {
-        return p->ctx == p0->ctx && p->n == p0->n && p->L == p0->L && p->K == p0->K && p->use_f64 && p->moduli == p0->moduli;
-    };
+    CtBytes s;
+    if (!f64_ring_ok(p0) || !ct_bytes(p0, batch, s)) return HEXL_E_BADARG;
+    if (n_baby > HX_LT_BSGS_STORE_BYTES / (2 * s.pt_bytes)) return HEXL_E_BADARG;   // not one instance would fit the baby store
+    if (hx_ranges_overlap(d_out, s.bytes, d_ct, s.bytes)) return HEXL_E_BADARG;
     for (size_t i = 0; i < n_baby; ++i)
-        if ((baby_plans[i] && !matches(baby_plans[i])) || !galois_elt_ok(baby_elts[i], p0->n)) return HEXL_E_BADARG;
+        if ((baby_plans[i] && !same_ring(baby_plans[i], p0)) || !galois_elt_ok(baby_elts[i], p0->n)) return HEXL_E_BADARG;
     for (size_t j = 0; j < n_giant; ++j) {
-        if ((giant_plans[j] && !matches(giant_plans[j])) || !galois_elt_ok(giant_elts[j], p0->n)) return HEXL_E_BADARG;
+        if ((giant_plans[j] && !same_ring(giant_plans[j], p0)) || !galois_elt_ok(giant_elts[j], p0->n)) return HEXL_E_BADARG;
         if (!giant_plans[j] && giant_elts[j] != 1) return HEXL_E_BADARG;
         const u64* pt_id = d_pt_identity ? d_pt_identity[j] : nullptr;
-        if (pt_id && hx_ranges_overlap(d_out, bytes, pt_id, row)) return HEXL_E_BADARG;
+        if (pt_id && hx_ranges_overlap(d_out, s.bytes, pt_id, s.row)) return HEXL_E_BADARG;
         bool any = pt_id != nullptr;
         for (size_t i = 0; i < n_baby; ++i)
             if (const u64* pt = d_pts[j * n_baby + i]) {
-                if (!baby_plans[i] || hx_ranges_overlap(d_out, bytes, pt, pt_bytes)) return HEXL_E_BADARG;
+                if (!baby_plans[i] || hx_ranges_overlap(d_out, s.bytes, pt, s.pt_bytes)) return HEXL_E_BADARG;
                 any = true;
             }
         if (!any) return HEXL_E_BADARG;                             // a giant row with no term at all

@@ -110,8 +110,8 @@ HX_HD double pt_mul(double c, double t, const Mod m) { return lift(pt_mul_centre
 // sum is exact and inside reduce's domain.
 HX_HD double pt_mul_acc(double c, double t, double prev, const Mod m) { return lift(reduce(pt_mul_centred(c, t, m) + prev, m), m); }
 
-// ---- the scalar chains of the linear transform (keyswitch_f64.hip k_ksf_mac_galois_pt, ckks_ops.hip k_galois_c0_pt), here so that
-// tests/cpp/lt_mac_selftest.cpp replays the kernels' own source against 128-bit integers --------------------------------------------
+// ---- the scalar chains of the linear transform (keyswitch_f64.hip k_ksf_mac_galois's plaintext modes, ckks_ops.hip k_galois_c0_pt),
+// here so that tests/cpp/lt_mac_selftest.cpp replays the kernels' own source against 128-bit integers -------------------------------
 // a plaintext word as the multiply-accumulate takes it: canonical (0 <= t < p < 2^52, exact as a double) -> centred, |.| <= p/2 + 2;
 // converted once per thread, the same for every instance it meets
 HX_HD double lt_pt(double t, const Mod m) { return reduce(t, m); }

@@ -59,6 +59,8 @@ inline int hx_knob_ks_lat() { static const int v = (int)hx_knob("HEXL_KS_LAT", -
 // HEXL_KS_PIPE: 1 = FP64 plans keep the (b, d)-major pipeline and integer plans run the first-generation kernels, 3 = the slot-major
 // pipeline for every batch (tests, comparisons)
 inline int hx_knob_ks_pipe() { static const int v = (int)hx_knob("HEXL_KS_PIPE", 2); return v; }
+// HEXL_KS_FUSE: bit 0 clear = the (b, d)-major pipeline runs steps 1-2 as one transform per workgroup even for large batches
+inline int hx_knob_ks_fuse() { static const int v = (int)hx_knob("HEXL_KS_FUSE", 1); return v; }
 
 struct hexl_ctx {
     int device = 0;
@@ -205,6 +207,7 @@ int hx_launch_keyswitch_x(hexl_ks_plan*, u64* d_result, const u64* d_t_target, s
                           hipEvent_t* ev);
 bool hx_ks_x_applies(const hexl_ks_plan*, size_t nb);
 size_t hx_ks_chunk(const hexl_ks_plan*);      // instances per scratch chunk (HEXL_KS_CHUNK or the default for the ring dimension)
+bool hx_ks_chunk_forced();                    // HEXL_KS_CHUNK is set: hx_ks_chunk is that number whatever the plan
 // true when a batch of nb runs entirely on kernels that honour hexl_ks_plan::overwrite_result
 bool hx_ks_can_overwrite(const hexl_ks_plan*, size_t nb);
 // the lone-keyswitch latency path (keyswitch_lat.hip): N = 16384, FP64 plans; one instance per call on p->cur / p->cur_scratch

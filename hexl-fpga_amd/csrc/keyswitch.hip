@@ -397,9 +397,10 @@ static int run_chunk(hexl_ks_plan* p, const KsArgs& a, int stage_mask, hipEvent_
 
 // instances per scratch chunk: HEXL_KS_CHUNK, else 256 at N = 16384 and the same number of COEFFICIENTS per chunk at the
 // other ring dimensions (4096 instances at N = 1024: a chunk's kernels must fill the chip whatever the transform size)
+static long ks_chunk_knob() { static const long v = hx_knob("HEXL_KS_CHUNK", 0); return v; }   // (read once per process; <= 0 = unset)
+bool hx_ks_chunk_forced() { return ks_chunk_knob() > 0; }
 size_t hx_ks_chunk(const hexl_ks_plan* p) {
-    static const long v = hx_knob("HEXL_KS_CHUNK", 0);             // (negative = unset)
-    if (v > 0) return (size_t)v;
+    if (hx_ks_chunk_forced()) return (size_t)ks_chunk_knob();
     return p->logn >= 14 ? size_t(256) >> (p->logn - 14) : size_t(256) << (14 - p->logn);
 }
 size_t hx_ks_f64_scratch_words(size_t L);

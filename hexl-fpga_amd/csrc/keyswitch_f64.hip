@@ -181,6 +181,11 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ksf_up(KsArgsF a) {
     }
 }
 
+// the inner chain of step 3: one accumulator takes one coefficient of one digit times its key word
+__device__ __forceinline__ double ksf_mac_term(double acc, double u, double key, Mod m) {
+    return hxf::reduce(acc + hxf::mul_mod(u, key, m), m);
+}
+
 // step 3: prod[b][k][slot] = sum_d u[b][slot][d] . key[d][k][slot]  (dyadmult.hpp:128-140). Pure streaming:
 // a thread owns two adjacent coefficients of one slot, keeps their 2*L*2 key words in registers and walks the
 // batch, so keys are read once per launch and u / prod exactly once.
@@ -211,8 +216,8 @@ __global__ __launch_bounds__(256) void k_ksf_mac(KsArgsF a, u32 n) {
                 const d2 u = __builtin_nontemporal_load(reinterpret_cast<const d2*>(ub + size_t(d) * n));   // read exactly once
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
-                    acc0[e] = hxf::reduce(acc0[e] + hxf::mul_mod(u[e], key[d][0][e], m), m);
-                    acc1[e] = hxf::reduce(acc1[e] + hxf::mul_mod(u[e], key[d][1][e], m), m);
+                    acc0[e] = ksf_mac_term(acc0[e], u[e], key[d][0][e], m);
+                    acc1[e] = ksf_mac_term(acc1[e], u[e], key[d][1][e], m);
                 }
             }
         __builtin_nontemporal_store(acc0, reinterpret_cast<d2*>(a.prod + ((size_t(b) * 2 + 0) * (L + 1) + slot) * n + j));
@@ -220,18 +225,28 @@ __global__ __launch_bounds__(256) void k_ksf_mac(KsArgsF a, u32 n) {
     }
 }
 
-// step 3 of a hoisted rotation (hexl_rotate_hoisted): prod[b][k][slot] = sum_d sigma_g(u[b][slot][d]) . key[d][k][slot] -- the Galois
-// automorphism applied to the mod-up output, which every rotation of the same ciphertext shares. In NTT-output index space sigma_g is
-// out[j] = in[galois_src(j)]; u, the keys and prod are stored in B order, so a thread takes ONE output index j (gid = slot*n + j), reads
-// the keys and writes prod at position posB(j), and gathers u from posB(galois_src(j)): src = idxB^-1 . pi_g . idxB without a table.
+// step 3 with the Galois automorphism inside it, for the callers that share one mod-up among many rotations:
+//     sum[b][k][slot] = sum_d sigma_g(u[b][slot][d]) . key[d][k][slot]
+// In NTT-output index space sigma_g is out[j] = in[galois_src(j)]; u, the keys and prod are stored in B order, so a thread takes ONE
+// output index j (gid = slot*n + j), reads the keys and writes prod at position posB(j), and gathers u from posB(galois_src(j)):
+// src = idxB^-1 . pi_g . idxB without a table.
 // The gather reads global memory directly, 8 bytes per lane. pi_g maps every aligned block of 2^k indices onto an aligned block of
 // 2^k indices (the low k bits of j are the high k bits of brv(j), and (2 brv(j) + 1) g only carries upwards), and B order keeps an
 // aligned block of 64 indices as 2^KL rows of 64 >> KL adjacent words: a wave's 64 sources fill exactly as many cache lines as its 64
 // outputs, merely in another order, and a workgroup's (256 indices; 512 at N = 32768, where KL = 5) are whole 128-byte lines. No LDS, no
 // barrier; the price against k_ksf_mac is 8-byte instead of 16-byte accesses. The keys stay in registers while the thread walks the batch.
 // u is not range-reduced (|u| <= 2.14p, KsArgsF) and a permutation moves words without changing them, so the bound holds for every
-// word gathered and the mul_mod / reduce chain below is k_ksf_mac's, term for term.
+// word gathered and the inner chain is k_ksf_mac's (ksf_mac_term). g = 1 is served too (galois_src(j) = j).
+// What becomes of the reduced sum is the kernel's mode:
+//   KSF_MAC_STORE    hexl_rotate_hoisted, and the baby steps of hexl_linear_transform_bsgs: prod = sum, streamed to the kernels of steps 4-7
+//                    (or to k_lt_bsgs_sum)
+//   KSF_MAC_PT_FIRST hexl_linear_transform, a chunk's first rotation: prod = pt[slot] . sum (hxf::lt_mac), prod is not read
+//   KSF_MAC_PT_ACC   ... its later rotations: prod = prod + pt[slot] . sum (hxf::lt_mac_acc), the old word requested in front of the gather
+// pt is [L + 1][n] u64 in plain NTT-output order, row L modulo the special prime: the thread's word is pt[slot][j], coalesced in j,
+// converted once and the same for every instance the thread walks. The plaintext modes store plainly -- the next rotation reads the
+// words -- and prod never leaves the extended basis between rotations, so steps 4-7 run once for all of them.
 struct HoistGeom { u32 logn, loge, kl, wb, g; };                 // Geom<LOGN, LOGE>: N, E, KL, WB as exponents; the Galois element
+enum KsfMacMode : int { KSF_MAC_STORE, KSF_MAC_PT_FIRST, KSF_MAC_PT_ACC };
 
 __device__ __forceinline__ u32 posB(u32 j, const HoistGeom& h) {  // inverse of Geom::idxB: position r*T + tid that holds NTT-output index j
     const u32 r = (j & ((1u << h.kl) - 1)) | (((j >> (h.kl + h.wb)) & ((1u << (h.loge - h.kl)) - 1)) << h.kl);
@@ -239,56 +254,29 @@ __device__ __forceinline__ u32 posB(u32 j, const HoistGeom& h) {  // inverse of 
     return (r << (h.logn - h.loge)) | tid;
 }
 
-template <int MAXL>
-__global__ __launch_bounds__(512) void k_ksf_mac_galois(KsArgsF a, HoistGeom h) {
-    const u32 L = a.L, n = 1u << h.logn;
-    const u32 gid = blockIdx.x * blockDim.x + threadIdx.x;        // (slot, j)
-    const u32 slot = gid >> h.logn;
-    if (slot > L) return;
-    const u32 j = gid & (n - 1);
-    const u32 pos = posB(j, h), src = posB(galois_src(j, h.logn, h.g), h);
-    const u32 i = slot < L ? slot : a.K - 1;
-    const Mod m = a.mods[i].m;
-    double key[MAXL][2];
-#pragma unroll
-    for (int d = 0; d < MAXL; ++d)
-        if (d < (int)L) {
-            key[d][0] = a.keys[((size_t(d) * (L + 1) + slot) * 2 + 0) * n + pos];
-            key[d][1] = a.keys[((size_t(d) * (L + 1) + slot) * 2 + 1) * n + pos];
-        }
-    for (u32 b = blockIdx.y; b < a.nb; b += gridDim.y) {
-        const double* ub = a.u + ((size_t(b) * (L + 1) + slot) * L) * n + src;
-        double acc0 = 0.0, acc1 = 0.0;
-#pragma unroll
-        for (int d = 0; d < MAXL; ++d)
-            if (d < (int)L) {
-                const double u = ub[size_t(d) * n];               // plain load: the rest of the line is another lane's, or the next wave's
-                acc0 = hxf::reduce(acc0 + hxf::mul_mod(u, key[d][0], m), m);
-                acc1 = hxf::reduce(acc1 + hxf::mul_mod(u, key[d][1], m), m);
-            }
-        __builtin_nontemporal_store(acc0, a.prod + ((size_t(b) * 2 + 0) * (L + 1) + slot) * n + pos);
-        __builtin_nontemporal_store(acc1, a.prod + ((size_t(b) * 2 + 1) * (L + 1) + slot) * n + pos);
-    }
+// a thread of the kernels that own ONE NTT-output index j of one slot: gid = slot * n + j; false for the threads past slot L. The caller
+// reads and writes B-ordered rows at posB(j)
+__device__ __forceinline__ bool hoist_item(const KsArgsF& a, const HoistGeom& h, u32& gid, u32& slot, u32& j) {
+    gid = blockIdx.x * blockDim.x + threadIdx.x;
+    slot = gid >> h.logn;
+    if (slot > a.L) return false;
+    j = gid & ((1u << h.logn) - 1);
+    return true;
 }
 
-// step 3 of a linear transform (hexl_linear_transform): one rotation's term of
-//     prod[b][k][slot] = sum_r pt_r[slot] . ( sum_d sigma_{g_r}(u[b][slot][d]) . key_r[d][k][slot] )
-// k_ksf_mac_galois's addressing and inner sum, term for term; the reduced inner sum is then multiplied by the rotation's plaintext word
-// and added to what the earlier rotations left in prod (hxf::lt_mac_acc; FIRST: the chunk's first rotation writes prod without reading
-// it). pt is [L + 1][n] u64 in plain NTT-output order, row L modulo the special prime: the thread's word is pt[slot][j], coalesced in j,
-// converted once and the same for every instance the thread walks. prod never leaves the extended basis between rotations, so the
-// special-prime inverse and the mod-down run once for all of them. g = 1 takes the same kernel (galois_src(j) = j).
-template <int MAXL, bool FIRST>
-__global__ __launch_bounds__(512) void k_ksf_mac_galois_pt(KsArgsF a, HoistGeom h, const u64* pt) {
+// PT: `const u64*` in the plaintext modes, nothing in KSF_MAC_STORE -- the hidden kernel arguments follow the declared ones, so an
+// argument nobody reads would still move the offsets the kernel loads them from
+template <int MAXL, KsfMacMode MODE, class... PT>
+__global__ __launch_bounds__(512) void k_ksf_mac_galois(KsArgsF a, HoistGeom h, PT... pt) {
+    static_assert(sizeof...(PT) == (MODE != KSF_MAC_STORE), "one plaintext, in the plaintext modes only");
     const u32 L = a.L, n = 1u << h.logn;
-    const u32 gid = blockIdx.x * blockDim.x + threadIdx.x;        // (slot, j)
-    const u32 slot = gid >> h.logn;
-    if (slot > L) return;
-    const u32 j = gid & (n - 1);
+    u32 gid, slot, j;
+    if (!hoist_item(a, h, gid, slot, j)) return;
     const u32 pos = posB(j, h), src = posB(galois_src(j, h.logn, h.g), h);
     const u32 i = slot < L ? slot : a.K - 1;
     const Mod m = a.mods[i].m;
-    const double t = hxf::lt_pt(hxf::to_f64(pt[gid]), m);         // gid = slot * n + j
+    double w = 0.0;
+    if constexpr (MODE != KSF_MAC_STORE) w = hxf::lt_pt(hxf::to_f64((pt, ...)[gid]), m);   // (pt, ...): the one pointer of the pack
     double key[MAXL][2];
 #pragma unroll
     for (int d = 0; d < MAXL; ++d)
@@ -301,38 +289,43 @@ __global__ __launch_bounds__(512) void k_ksf_mac_galois_pt(KsArgsF a, HoistGeom 
         double* p0 = a.prod + ((size_t(b) * 2 + 0) * (L + 1) + slot) * n + pos;
         double* p1 = a.prod + ((size_t(b) * 2 + 1) * (L + 1) + slot) * n + pos;
         double prev0 = 0.0, prev1 = 0.0;
-        if constexpr (!FIRST) { prev0 = *p0; prev1 = *p1; }        // requested in front of the gather
+        if constexpr (MODE == KSF_MAC_PT_ACC) { prev0 = *p0; prev1 = *p1; }   // requested in front of the gather
         double acc0 = 0.0, acc1 = 0.0;
 #pragma unroll
         for (int d = 0; d < MAXL; ++d)
             if (d < (int)L) {
-                const double u = ub[size_t(d) * n];               // plain load, as k_ksf_mac_galois
-                acc0 = hxf::reduce(acc0 + hxf::mul_mod(u, key[d][0], m), m);
-                acc1 = hxf::reduce(acc1 + hxf::mul_mod(u, key[d][1], m), m);
+                const double u = ub[size_t(d) * n];               // plain load: the rest of the line is another lane's, or the next wave's
+                acc0 = ksf_mac_term(acc0, u, key[d][0], m);
+                acc1 = ksf_mac_term(acc1, u, key[d][1], m);
             }
-        if constexpr (FIRST) { *p0 = hxf::lt_mac(acc0, t, m); *p1 = hxf::lt_mac(acc1, t, m); }
-        else { *p0 = hxf::lt_mac_acc(acc0, t, prev0, m); *p1 = hxf::lt_mac_acc(acc1, t, prev1, m); }   // plain stores: the next rotation reads them
+        if constexpr (MODE == KSF_MAC_STORE) {
+            __builtin_nontemporal_store(acc0, p0);
+            __builtin_nontemporal_store(acc1, p1);
+        } else if constexpr (MODE == KSF_MAC_PT_FIRST) {
+            *p0 = hxf::lt_mac(acc0, w, m); *p1 = hxf::lt_mac(acc1, w, m);
+        } else {
+            *p0 = hxf::lt_mac_acc(acc0, w, prev0, m); *p1 = hxf::lt_mac_acc(acc1, w, prev1, m);
+        }
     }
 }
 
 // step 3 of one giant step of a baby-step/giant-step linear transform (hexl_linear_transform_bsgs):
 //     prod[b][k][slot] = sum_i pt_{j,i}[slot] . B_i[b][k][slot]
-// B_i is what k_ksf_mac_galois (k_ksf_mac for g = 1) stored for baby step i: sum_d sigma_{g_i}(u[b][slot][d]) . key_i[d][k][slot], the
-// inner sum of k_ksf_mac_galois_pt, computed once per chunk instead of once per giant step. No keys, no gather: a thread owns NTT-output
-// index j of one slot as k_ksf_mac_galois_pt does (gid = slot * n + j), reads its plaintext word pt[slot][j] (plain order, coalesced in
-// j) and the two stored words at posB(j) per term of the per-call table, keeps both accumulators in registers across the terms and
-// writes prod once -- no read-modify-write of prod per rotation. The plaintext words come from L2 from the second instance on.
-// The scalar chain is k_ksf_mac_galois_pt's unchanged -- lt_pt, lt_mac for the first term, lt_mac_acc after it -- and its inner operand
-// is, as there, an output of reduce (the last operation of the stored multiply-accumulate): the bound chain of f64_arith.hpp and its
-// host replay (tests/cpp/lt_mac_selftest.cpp) cover this kernel as they stand.
+// B_i is what k_ksf_mac_galois<., KSF_MAC_STORE> (k_ksf_mac for g = 1) stored for baby step i, the inner sum of the plaintext modes,
+// computed once per chunk instead of once per giant step. No keys, no gather: a thread owns NTT-output index j of one slot as
+// k_ksf_mac_galois does (hoist_item), reads its plaintext word pt[slot][j] (plain order, coalesced in j) and the two stored words at
+// posB(j) per term of the per-call table, keeps both accumulators in registers across the terms and writes prod once -- no
+// read-modify-write of prod per rotation. The plaintext words come from L2 from the second instance on.
+// The scalar chain is that of k_ksf_mac_galois's plaintext modes unchanged -- lt_pt, lt_mac for the first term, lt_mac_acc after it --
+// and its inner operand is, as there, an output of reduce (the last operation of the stored multiply-accumulate): the bound chain of
+// f64_arith.hpp and its host replay (tests/cpp/lt_mac_selftest.cpp) cover this kernel as they stand.
 struct HxBsgsTerm { const u64* pt; const double* B; };           // pt: [L + 1][n]; B: baby step's slice [nb][2][L + 1][n], B order
 
 __global__ __launch_bounds__(256) void k_lt_bsgs_sum(KsArgsF a, HoistGeom h, const HxBsgsTerm* terms, u32 n_terms) {
     const u32 L = a.L, n = 1u << h.logn;
-    const u32 gid = blockIdx.x * blockDim.x + threadIdx.x;        // (slot, j)
-    const u32 slot = gid >> h.logn;
-    if (slot > L) return;
-    const u32 pos = posB(gid & (n - 1), h);
+    u32 gid, slot, j;
+    if (!hoist_item(a, h, gid, slot, j)) return;
+    const u32 pos = posB(j, h);
     const u32 i = slot < L ? slot : a.K - 1;
     const Mod m = a.mods[i].m;
     for (u32 b = blockIdx.y; b < a.nb; b += gridDim.y) {
@@ -342,11 +335,11 @@ __global__ __launch_bounds__(256) void k_lt_bsgs_sum(KsArgsF a, HoistGeom h, con
         double acc0 = hxf::lt_mac(first.B[o0], t0, m), acc1 = hxf::lt_mac(first.B[o1], t0, m);
         for (u32 r = 1; r < n_terms; ++r) {
             const HxBsgsTerm term = terms[r];
-            const double t = hxf::lt_pt(hxf::to_f64(term.pt[gid]), m);
-            acc0 = hxf::lt_mac_acc(term.B[o0], t, acc0, m);
-            acc1 = hxf::lt_mac_acc(term.B[o1], t, acc1, m);
+            const double w = hxf::lt_pt(hxf::to_f64(term.pt[gid]), m);
+            acc0 = hxf::lt_mac_acc(term.B[o0], w, acc0, m);
+            acc1 = hxf::lt_mac_acc(term.B[o1], w, acc1, m);
         }
-        __builtin_nontemporal_store(acc0, a.prod + o0);           // streamed to k_ksf_intt_sp / k_ksf_moddown, as k_ksf_mac_galois
+        __builtin_nontemporal_store(acc0, a.prod + o0);           // streamed to k_ksf_intt_sp / k_ksf_moddown, as k_ksf_mac_galois stores
         __builtin_nontemporal_store(acc1, a.prod + o1);
     }
 }
@@ -600,15 +593,88 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ksl_down(KsArgsF a) {
     hxf::report_range(bad, a.range_flag);
 }
 
-// ---------------------------------------------------------------------------------------------
+// ---- the stages of a chunk, each launched from ONE place: the keyswitch (run_chunk_f64) and the hoisted callers (HoistRun) share them.
+// A stage opts its kernels in to their dynamic LDS before it launches them and returns the launch error. ----
+static u32 ksf_batch_lanes(u32 nb) { return nb < 8 ? nb : 8; }    // step 3's grid.y: 8 batch lanes keep >= 2048 workgroups in flight
+template <class F>
+static void ksf_with_maxl(u32 L, F f) {                           // step 3's key registers: room for 8 or 16 digits
+    if (L <= 8) f(hx_int<8>{});
+    else        f(hx_int<16>{});
+}
+
+// steps 1-2 (inverse + mod-up transforms). CT: t_target is component 1 of a ciphertext batch, read in place
+template <int LOGN, int LOGE, int LAZY, bool CT>
+static int ksf_stage_up(hexl_ctx* c, hipStream_t st, const KsArgsF& a) {
+    using G = Geom<LOGN, LOGE>;
+    const u32 L = a.L, nb = a.nb;
+    // one workgroup per input polynomial (all its transforms back to back) once that alone fills the chip twice;
+    // below that one workgroup per transform, so that small batches still spread over the CUs (N = 32768: 64 VGPRs of data already)
+    const bool fused_up = LAZY >= 0 && (hx_knob_ks_fuse() & 1) && nb * L >= 2 * (u32)c->num_cu && !G::HALF_ONLY;
+    if constexpr (LAZY >= 0)
+        if (fused_up) {
+            if (int rc = hx_lds_optin<k_ksf_up<LOGN, LOGE, LAZY, CT>>(c->device, G::LDS_USED)) return rc;
+            hipLaunchKernelGGL((k_ksf_up<LOGN, LOGE, LAZY, CT>), dim3(nb * L), dim3(G::T), G::LDS_USED, st, a);
+            return (int)hipGetLastError();
+        }
+    if (int rc = hx_lds_optin<k_ksf_intt<LOGN, LOGE, LAZY, CT>, k_ksf_ntt_up<LOGN, LOGE, LAZY>>(c->device, G::LDS_USED)) return rc;
+    hipLaunchKernelGGL((k_ksf_intt<LOGN, LOGE, LAZY, CT>), dim3(nb * L), dim3(G::T), G::LDS_USED, st, a);
+    hipLaunchKernelGGL((k_ksf_ntt_up<LOGN, LOGE, LAZY>), dim3(nb * L * L), dim3(G::T), G::LDS_USED, st, a);
+    return (int)hipGetLastError();
+}
+
+// step 3 into a.prod
+template <int LOGN, int LOGE>
+static int ksf_stage_mac(hipStream_t st, const KsArgsF& a) {
+    using G = Geom<LOGN, LOGE>;
+    const dim3 grid((a.L + 1) * (G::N / 2) / 256, ksf_batch_lanes(a.nb));
+    ksf_with_maxl(a.L, [&](auto M) { hipLaunchKernelGGL((k_ksf_mac<decltype(M)::value>), grid, dim3(256), 0, st, a, (u32)G::N); });
+    return (int)hipGetLastError();
+}
+
+// step 3 with sigma_g inside the multiply-accumulate; d_pt: the rotation's plaintext (the plaintext modes). The identity that only
+// stores is the keyswitch's own step 3
+template <int LOGN, int LOGE>
+static int ksf_stage_mac_galois(hipStream_t st, const KsArgsF& a, u32 g, KsfMacMode mode, const u64* d_pt) {
+    using G = Geom<LOGN, LOGE>;
+    if (g == 1 && mode == KSF_MAC_STORE) return ksf_stage_mac<LOGN, LOGE>(st, a);
+    const HoistGeom h{LOGN, LOGE, G::KL, G::WB, g};
+    const u32 wg = G::KL + 4 > 8 ? 1u << (G::KL + 4) : 256u;       // 2^KL rows of >= 16 adjacent words: whole 128-byte lines per workgroup
+    static_assert(G::KL + 4 <= 9, "k_ksf_mac_galois is bounded at 512 threads");
+    const dim3 grid((a.L + 1) * G::N / wg, ksf_batch_lanes(a.nb)), block(wg);
+    ksf_with_maxl(a.L, [&](auto M) {
+        constexpr int MAXL = decltype(M)::value;
+        if (mode == KSF_MAC_STORE)         hipLaunchKernelGGL((k_ksf_mac_galois<MAXL, KSF_MAC_STORE>), grid, block, 0, st, a, h);
+        else if (mode == KSF_MAC_PT_FIRST) hipLaunchKernelGGL((k_ksf_mac_galois<MAXL, KSF_MAC_PT_FIRST>), grid, block, 0, st, a, h, d_pt);
+        else                               hipLaunchKernelGGL((k_ksf_mac_galois<MAXL, KSF_MAC_PT_ACC>), grid, block, 0, st, a, h, d_pt);
+    });
+    return (int)hipGetLastError();
+}
+
+// step 3 of a giant step: the weighted sum of the stored baby products into a.prod, no keys
+template <int LOGN, int LOGE>
+static int ksf_stage_bsgs_sum(hipStream_t st, const KsArgsF& a, const HxBsgsTerm* d_terms, u32 n_terms) {
+    using G = Geom<LOGN, LOGE>;
+    const HoistGeom h{LOGN, LOGE, G::KL, G::WB, 1};
+    hipLaunchKernelGGL(k_lt_bsgs_sum, dim3((a.L + 1) * G::N / 256, ksf_batch_lanes(a.nb)), dim3(256), 0, st, a, h, d_terms, n_terms);
+    return (int)hipGetLastError();
+}
+
+// step 4 (steps & 1) and steps 5-7 (steps & 2) on a.prod, into a.result
+// (the fusion of steps 1-2 applied here -- s' in registers, L mod-down transforms per workgroup -- measured 8 % slower
+// than the two kernels: its epilogue loads cannot be requested early, tools/experiments/fused_down.patch)
+template <int LOGN, int LOGE, int LAZY>
+static int ksf_stage_down(hexl_ctx* c, hipStream_t st, const KsArgsF& a, int steps = 3) {
+    using G = Geom<LOGN, LOGE>;
+    if (int rc = hx_lds_optin<k_ksf_intt_sp<LOGN, LOGE, LAZY>, k_ksf_moddown<LOGN, LOGE, LAZY>>(c->device, G::LDS_USED)) return rc;
+    if (steps & 1) hipLaunchKernelGGL((k_ksf_intt_sp<LOGN, LOGE, LAZY>), dim3(a.nb * 2), dim3(G::T), G::LDS_USED, st, a);
+    if (steps & 2) hipLaunchKernelGGL((k_ksf_moddown<LOGN, LOGE, LAZY>), dim3(a.nb * a.L * 2), dim3(G::T), G::LDS_USED, st, a);
+    return (int)hipGetLastError();
+}
+
 template <int LOGN, int LOGE, int LAZY>
 static int run_chunk_f64(hexl_ks_plan* p, const KsArgsF& a, int stage_mask, hipEvent_t* ev) {
     using G = Geom<LOGN, LOGE>;
-    if constexpr (LAZY >= 0)
-        if (int rc = hx_lds_optin<k_ksf_up<LOGN, LOGE, LAZY>>(p->ctx->device, G::LDS_USED)) return rc;
-    if (int rc = hx_lds_optin<k_ksf_intt<LOGN, LOGE, LAZY>, k_ksf_ntt_up<LOGN, LOGE, LAZY>, k_ksf_intt_sp<LOGN, LOGE, LAZY>,
-                              k_ksf_moddown<LOGN, LOGE, LAZY>>(p->ctx->device, G::LDS_USED))
-        return rc;
+    hexl_ctx* c = p->ctx;
     hipStream_t st = p->cur;
     const u32 L = a.L, nb = a.nb;
     // latency path (three kernels, above): a LONE keyswitch. Measured (tools/batch_sweep.py, N = 16384, device-resident): 70.3 us
@@ -622,49 +688,33 @@ static int run_chunk_f64(hexl_ks_plan* p, const KsArgsF& a, int stage_mask, hipE
     const int lat = hx_knob_ks_lat();
     if constexpr (!G::HALF_ONLY)
     if (!ev && stage_mask == 7 && L <= 15 && (lat == 1 || (lat != 0 && nb == 1))) {
-        if (int rc = hx_lds_optin<k_ksl_intt<LOGN, LOGE, LAZY>, k_ksl_up<LOGN, LOGE, LAZY>, k_ksl_down<LOGN, LOGE, LAZY>>(p->ctx->device, G::LDS_USED))
+        if (int rc = hx_lds_optin<k_ksl_intt<LOGN, LOGE, LAZY>, k_ksl_up<LOGN, LOGE, LAZY>, k_ksl_down<LOGN, LOGE, LAZY>>(c->device, G::LDS_USED))
             return rc;
         hipLaunchKernelGGL((k_ksl_intt<LOGN, LOGE, LAZY>), dim3(nb * L), dim3(G::T), G::LDS_USED, st, a);
         hipLaunchKernelGGL((k_ksl_up<LOGN, LOGE, LAZY>), dim3(nb * (L + 1) * L), dim3(G::T), G::LDS_USED, st, a);
         hipLaunchKernelGGL((k_ksl_down<LOGN, LOGE, LAZY>), dim3(nb * 2 * L), dim3(G::T), G::LDS_USED, st, a);
         return (int)hipGetLastError();
     }
-    // one workgroup per input polynomial (all its transforms back to back) once that alone fills the chip twice;
-    // below that one workgroup per transform, so that small batches still spread over the CUs
-    const u32 cus = (u32)p->ctx->num_cu;
-    // (the same fusion of steps 4-7 -- s' in registers, L mod-down transforms per workgroup -- measured 8 % slower
-    // than the two kernels below: its epilogue loads cannot be requested early, tools/experiments/fused_down.patch)
-    static const int fuse = (int)hx_knob("HEXL_KS_FUSE", 1);
-    const bool fused_up = LAZY >= 0 && (fuse & 1) && nb * L >= 2 * cus && !G::HALF_ONLY;   // N = 32768: 64 VGPRs of data already
     // timing stages: 1 = steps 1-2 (inverse + mod-up transforms), 2 = steps 3-4, 4 = steps 5-7
     if (ev) HX_CHECK(hipEventRecord(ev[0], st));
-    if (stage_mask & 1) {
-        if (fused_up) {
-            if constexpr (LAZY >= 0) hipLaunchKernelGGL((k_ksf_up<LOGN, LOGE, LAZY>), dim3(nb * L), dim3(G::T), G::LDS_USED, st, a);
-        } else {
-            hipLaunchKernelGGL((k_ksf_intt<LOGN, LOGE, LAZY>), dim3(nb * L), dim3(G::T), G::LDS_USED, st, a);
-            hipLaunchKernelGGL((k_ksf_ntt_up<LOGN, LOGE, LAZY>), dim3(nb * L * L), dim3(G::T), G::LDS_USED, st, a);
-        }
-    }
+    if (stage_mask & 1)
+        if (int rc = ksf_stage_up<LOGN, LOGE, LAZY, false>(c, st, a)) return rc;
     if (ev) HX_CHECK(hipEventRecord(ev[1], st));
     if (stage_mask & 2) {
-        const u32 threads = (L + 1) * (G::N / 2);
-        const u32 by = nb < 8 ? nb : 8;                            // 8 batch lanes keep >= 2048 workgroups in flight
-        if (L <= 8) hipLaunchKernelGGL((k_ksf_mac<8>), dim3(threads / 256, by), dim3(256), 0, st, a, (u32)G::N);
-        else        hipLaunchKernelGGL((k_ksf_mac<16>), dim3(threads / 256, by), dim3(256), 0, st, a, (u32)G::N);
-        hipLaunchKernelGGL((k_ksf_intt_sp<LOGN, LOGE, LAZY>), dim3(nb * 2), dim3(G::T), G::LDS_USED, st, a);
+        if (int rc = ksf_stage_mac<LOGN, LOGE>(st, a)) return rc;
+        if (int rc = ksf_stage_down<LOGN, LOGE, LAZY>(c, st, a, 1)) return rc;
     }
     if (ev) HX_CHECK(hipEventRecord(ev[2], st));
     if (stage_mask & 4)
-        hipLaunchKernelGGL((k_ksf_moddown<LOGN, LOGE, LAZY>), dim3(nb * L * 2), dim3(G::T), G::LDS_USED, st, a);
+        if (int rc = ksf_stage_down<LOGN, LOGE, LAZY>(c, st, a, 2)) return rc;
     if (ev) HX_CHECK(hipEventRecord(ev[3], st));
-    return (int)hipGetLastError();
+    return 0;
 }
 
 size_t hx_ks_f64_scratch_words(size_t L) { return L + (L + 1) * L + 2 * (L + 1) + 2; }   // per instance, in units of n
 
 // constants, tables and keys of `p`; scratch (the chunk `mem->cur_scratch` points at) and range flag of `mem` -- the same plan, except for
-// hexl_rotate_hoisted, where every rotation's plan works in plans[0]'s scratch
+// the hoisted callers, where every rotation's plan works in plans[0]'s scratch
 static KsArgsF ksf_args(const hexl_ks_plan* p, const hexl_ks_plan* mem, u64* d_result, const u64* d_t_target, size_t nb) {
     const size_t n = p->n, L = p->L;
     KsArgsF a;
@@ -701,172 +751,110 @@ int hx_launch_keyswitch_f64(hexl_ks_plan* p, u64* d_result, const u64* d_t_targe
     return hx_with_f64_geom(p->logn, ksf_lazy(p), [&](auto N, auto E, auto Z) { return run_chunk_f64<N, E, Z>(p, a, stage_mask, ev); });
 }
 
-// ---- hoisted rotations (hexl_rotate_hoisted): R rotations of one ciphertext share the keyswitch's steps 1-2 ----
-// steps 1-2 of one chunk on component 1 of the ciphertext batch, read in place (the CT kernels); the route is run_chunk_f64's
-template <int LOGN, int LOGE, int LAZY>
-static int run_hoist_up(hexl_ctx* c, const KsArgsF& a) {
-    using G = Geom<LOGN, LOGE>;
-    const u32 L = a.L, nb = a.nb;
-    const bool fused_up = LAZY >= 0 && (hx_knob("HEXL_KS_FUSE", 1) & 1) && nb * L >= 2 * (u32)c->num_cu && !G::HALF_ONLY;
-    if constexpr (LAZY >= 0)
-        if (fused_up) {
-            if (int rc = hx_lds_optin<k_ksf_up<LOGN, LOGE, LAZY, true>>(c->device, G::LDS_USED)) return rc;
-            hipLaunchKernelGGL((k_ksf_up<LOGN, LOGE, LAZY, true>), dim3(nb * L), dim3(G::T), G::LDS_USED, c->stream, a);
-            return (int)hipGetLastError();
-        }
-    if (int rc = hx_lds_optin<k_ksf_intt<LOGN, LOGE, LAZY, true>, k_ksf_ntt_up<LOGN, LOGE, LAZY>>(c->device, G::LDS_USED)) return rc;
-    hipLaunchKernelGGL((k_ksf_intt<LOGN, LOGE, LAZY, true>), dim3(nb * L), dim3(G::T), G::LDS_USED, c->stream, a);
-    hipLaunchKernelGGL((k_ksf_ntt_up<LOGN, LOGE, LAZY>), dim3(nb * L * L), dim3(G::T), G::LDS_USED, c->stream, a);
-    return (int)hipGetLastError();
-}
+// ---- the hoisted callers: many rotations of one ciphertext batch share the keyswitch's steps 1-2 (hexl_rotate_hoisted,
+// hexl_linear_transform, hexl_linear_transform_bsgs). One run works in p0's keyswitch scratch, chunk after chunk, everything on the
+// context's stream: one lane, so nothing has to be joined and the next mod-up overwrites u behind the last multiply-accumulate that read
+// it. The stage methods take the plan whose keys (mac) or whose constants and tier (down) the kernels use; u, prod, s' and the range flag
+// are always p0's. ----
+struct HoistRun {
+    hexl_ks_plan* p0;
+    hexl_ctx* c;
+    size_t chunk, per;                                             // instances per chunk; words of one ciphertext, 2 L n
 
-// step 3 of one rotation of one chunk into a.prod: sigma_g inside the multiply-accumulate
-template <int LOGN, int LOGE>
-static int run_hoist_mac(hexl_ctx* c, const KsArgsF& a, u32 g) {
-    using G = Geom<LOGN, LOGE>;
-    const u32 L = a.L, nb = a.nb;
-    const u32 by = nb < 8 ? nb : 8;                                // as run_chunk_f64
-    if (g == 1) {                                                  // the identity: the keyswitch's own step 3
-        const u32 threads = (L + 1) * (G::N / 2);
-        if (L <= 8) hipLaunchKernelGGL((k_ksf_mac<8>), dim3(threads / 256, by), dim3(256), 0, c->stream, a, (u32)G::N);
-        else        hipLaunchKernelGGL((k_ksf_mac<16>), dim3(threads / 256, by), dim3(256), 0, c->stream, a, (u32)G::N);
-    } else {
-        const HoistGeom h{LOGN, LOGE, G::KL, G::WB, g};
-        const u32 wg = G::KL + 4 > 8 ? 1u << (G::KL + 4) : 256u;   // 2^KL rows of >= 16 adjacent words: whole 128-byte lines per workgroup
-        static_assert(G::KL + 4 <= 9, "k_ksf_mac_galois is bounded at 512 threads");
-        if (L <= 8) hipLaunchKernelGGL((k_ksf_mac_galois<8>), dim3((L + 1) * G::N / wg, by), dim3(wg), 0, c->stream, a, h);
-        else        hipLaunchKernelGGL((k_ksf_mac_galois<16>), dim3((L + 1) * G::N / wg, by), dim3(wg), 0, c->stream, a, h);
+    HoistRun(hexl_ks_plan* p, size_t chunk_) : p0(p), c(p->ctx), chunk(chunk_), per(2 * size_t(p->L) * p->n) {}
+    // p0's keyswitch scratch, grown as hx_launch_keyswitch grows it (hexl_ks_scratch_bytes(p, 1): one instance of a chunk, every lane)
+    int reserve() {
+        if (int rc = hx_grow_device((void**)&p0->d_scratch, &p0->cap, chunk, hexl_ks_scratch_bytes(p0, 1), nullptr)) return rc;
+        p0->cur = c->stream;
+        p0->cur_scratch = p0->d_scratch;
+        return 0;
     }
-    return (int)hipGetLastError();
-}
+    // f(b0, nb) for every chunk of `batch` instances
+    template <class F>
+    int chunks(size_t batch, F f) const {
+        for (size_t b0 = 0; b0 < batch; b0 += chunk)
+            if (int rc = f(b0, batch - b0 < chunk ? batch - b0 : chunk)) return rc;
+        return 0;
+    }
+    // steps 1-2 on d_c1 = component 1 of nb ciphertexts [nb][2][L][n], read in place, into u
+    int up(const u64* d_c1, size_t nb) const {
+        const KsArgsF a = ksf_args(p0, p0, nullptr, d_c1, nb);
+        return hx_with_f64_geom(p0->logn, ksf_lazy(p0), [&](auto N, auto E, auto Z) { return ksf_stage_up<N, E, Z, true>(c, c->stream, a); });
+    }
+    // step 3 of one rotation with the keys of `keys`: sigma_g(u) . key into prod (`mode`, d_pt: KsfMacMode), or into `prod` when given.
+    // (No transform, so no tier: only the geometry is dispatched on, here and in sum)
+    int mac(const hexl_ks_plan* keys, u32 g, KsfMacMode mode, const u64* d_pt, double* prod, size_t nb) const {
+        KsArgsF a = ksf_args(keys, p0, nullptr, nullptr, nb);
+        if (prod) a.prod = prod;
+        return hx_with_f64_geom(p0->logn, 0, [&](auto N, auto E, auto) { return ksf_stage_mac_galois<N, E>(c->stream, a, g, mode, d_pt); });
+    }
+    // step 3 of a giant step: the weighted sum of stored products into prod
+    int sum(const HxBsgsTerm* d_terms, size_t n_terms, size_t nb) const {
+        const KsArgsF a = ksf_args(p0, p0, nullptr, nullptr, nb);
+        return hx_with_f64_geom(p0->logn, 0, [&](auto N, auto E, auto) { return ksf_stage_bsgs_sum<N, E>(c->stream, a, d_terms, (u32)n_terms); });
+    }
+    // steps 4-7 on prod with the constants and on the tier of `tier`, ADDED into d_out (whatever the plan's overwrite_result says)
+    int down(const hexl_ks_plan* tier, u64* d_out, size_t nb) const {
+        KsArgsF a = ksf_args(tier, p0, d_out, nullptr, nb);
+        a.overwrite = 0;
+        return hx_with_f64_geom(p0->logn, ksf_lazy(tier), [&](auto N, auto E, auto Z) { return ksf_stage_down<N, E, Z>(c, c->stream, a); });
+    }
+};
 
-// steps 3-7 of one rotation of one chunk: the multiply-accumulate above, then the keyswitch's own steps 4-7
-template <int LOGN, int LOGE, int LAZY>
-static int run_hoist_down(hexl_ctx* c, const KsArgsF& a, u32 g) {
-    using G = Geom<LOGN, LOGE>;
-    if (int rc = hx_lds_optin<k_ksf_intt_sp<LOGN, LOGE, LAZY>, k_ksf_moddown<LOGN, LOGE, LAZY>>(c->device, G::LDS_USED)) return rc;
-    const u32 L = a.L, nb = a.nb;
-    if (int rc = run_hoist_mac<LOGN, LOGE>(c, a, g)) return rc;
-    hipLaunchKernelGGL((k_ksf_intt_sp<LOGN, LOGE, LAZY>), dim3(nb * 2), dim3(G::T), G::LDS_USED, c->stream, a);
-    hipLaunchKernelGGL((k_ksf_moddown<LOGN, LOGE, LAZY>), dim3(nb * L * 2), dim3(G::T), G::LDS_USED, c->stream, a);
-    return (int)hipGetLastError();
-}
-
-// Arguments checked by hexl_rotate_hoisted (ckks_ops.hip). Everything goes to the context's stream, chunk after chunk, rotation after
-// rotation: one lane, so nothing has to be joined and the next chunk's mod-up overwrites u behind the last rotation that read it.
+// Arguments checked by hexl_rotate_hoisted (ckks_ops.hip). Per chunk: the mod-up of c1 on plans[0]'s tier, then per rotation
+// (sigma_g(c0), 0) into its output, its multiply-accumulate and steps 4-7 on ITS plan's tier, accumulated into the output.
 int hx_launch_rotate_hoisted(hexl_ks_plan* const* plans, const u64* galois_elts, size_t n_rot, u64* const* d_outs, const u64* d_ct,
                              size_t batch) {
     hexl_ks_plan* p0 = plans[0];
-    hexl_ctx* c = p0->ctx;
-    const size_t n = p0->n, L = p0->L, per = 2 * L * n;
-    const size_t chunk = hx_ks_chunk_of(p0, batch);
-    // plans[0]'s keyswitch scratch, grown as hx_launch_keyswitch grows it (hexl_ks_scratch_bytes(p, 1): one instance of a chunk, every lane)
-    if (int rc = hx_grow_device((void**)&p0->d_scratch, &p0->cap, chunk, hexl_ks_scratch_bytes(p0, 1), nullptr)) return rc;
-    p0->cur = c->stream;
-    p0->cur_scratch = p0->d_scratch;
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-        const size_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-        const u64* ct = d_ct + b0 * per;
-        const KsArgsF up = ksf_args(p0, p0, nullptr, ct + L * n, nb);
-        if (int rc = hx_with_f64_geom(p0->logn, ksf_lazy(p0), [&](auto N, auto E, auto Z) { return run_hoist_up<N, E, Z>(c, up); })) return rc;
+    HoistRun run(p0, hx_ks_chunk_of(p0, batch));
+    if (int rc = run.reserve()) return rc;
+    const size_t half = run.per / 2;
+    return run.chunks(batch, [&](size_t b0, size_t nb) {
+        const u64* ct = d_ct + b0 * run.per;
+        if (int rc = run.up(ct + half, nb)) return rc;
         for (size_t r = 0; r < n_rot; ++r) {
             const u32 g = (u32)galois_elts[r];
-            u64* out = d_outs[r] + b0 * per;
-            if (int rc = hx_launch_galois_c0(c, out, ct, nb, (u32)L, p0->logn, g)) return rc;
-            KsArgsF a = ksf_args(plans[r], p0, out, nullptr, nb);
-            a.overwrite = 0;                                       // accumulated into (sigma_g(c0), 0)
-            if (int rc = hx_with_f64_geom(p0->logn, ksf_lazy(plans[r]), [&](auto N, auto E, auto Z) { return run_hoist_down<N, E, Z>(c, a, g); }))
-                return rc;
+            u64* out = d_outs[r] + b0 * run.per;
+            if (int rc = hx_launch_galois_c0(run.c, out, ct, nb, p0->L, p0->logn, g)) return rc;
+            if (int rc = run.mac(plans[r], g, KSF_MAC_STORE, nullptr, nullptr, nb)) return rc;
+            if (int rc = run.down(plans[r], out, nb)) return rc;
         }
-    }
-    return 0;
+        return 0;
+    });
 }
 
-// ---- linear transform (hexl_linear_transform): the hoisted rotations with their plaintext weights, summed BEFORE the mod-down ----
-// step 3 of one rotation of one chunk: its term goes into prod (`first`: prod is written)
-template <int LOGN, int LOGE>
-static int run_lt_mac(hexl_ctx* c, const KsArgsF& a, u32 g, const u64* d_pt, bool first) {
-    using G = Geom<LOGN, LOGE>;
-    const u32 L = a.L, nb = a.nb;
-    const u32 by = nb < 8 ? nb : 8;                                // as run_chunk_f64
-    const HoistGeom h{LOGN, LOGE, G::KL, G::WB, g};
-    const u32 wg = G::KL + 4 > 8 ? 1u << (G::KL + 4) : 256u;       // as run_hoist_down: whole 128-byte lines per workgroup
-    const dim3 grid((L + 1) * G::N / wg, by), block(wg);
-    if (L <= 8) {
-        if (first) hipLaunchKernelGGL((k_ksf_mac_galois_pt<8, true>), grid, block, 0, c->stream, a, h, d_pt);
-        else       hipLaunchKernelGGL((k_ksf_mac_galois_pt<8, false>), grid, block, 0, c->stream, a, h, d_pt);
-    } else {
-        if (first) hipLaunchKernelGGL((k_ksf_mac_galois_pt<16, true>), grid, block, 0, c->stream, a, h, d_pt);
-        else       hipLaunchKernelGGL((k_ksf_mac_galois_pt<16, false>), grid, block, 0, c->stream, a, h, d_pt);
-    }
-    return (int)hipGetLastError();
-}
-
-// steps 4-7 of one chunk, once for all rotations: the keyswitch's own kernels on the accumulated prod
-template <int LOGN, int LOGE, int LAZY>
-static int run_lt_down(hexl_ctx* c, const KsArgsF& a) {
-    using G = Geom<LOGN, LOGE>;
-    if (int rc = hx_lds_optin<k_ksf_intt_sp<LOGN, LOGE, LAZY>, k_ksf_moddown<LOGN, LOGE, LAZY>>(c->device, G::LDS_USED)) return rc;
-    hipLaunchKernelGGL((k_ksf_intt_sp<LOGN, LOGE, LAZY>), dim3(a.nb * 2), dim3(G::T), G::LDS_USED, c->stream, a);
-    hipLaunchKernelGGL((k_ksf_moddown<LOGN, LOGE, LAZY>), dim3(a.nb * a.L * 2), dim3(G::T), G::LDS_USED, c->stream, a);
-    return (int)hipGetLastError();
-}
-
-// Arguments checked by hexl_linear_transform (ckks_ops.hip). One lane on the context's stream, as hx_launch_rotate_hoisted; per chunk:
-// the shared mod-up, the plaintext-weighted c0 / identity terms into d_out (hx_launch_galois_c0_pt), one multiply-accumulate launch per
-// rotation into plans[0]'s prod, then the special-prime inverse and the mod-down ONCE, added into d_out.
+// Arguments checked by hexl_linear_transform (ckks_ops.hip). Per chunk, all on plans[0]'s tier: the shared mod-up, the plaintext-weighted
+// c0 / identity terms into d_out (hx_launch_galois_c0_pt), one multiply-accumulate launch per rotation into plans[0]'s prod (plan r's
+// keys), then the special-prime inverse and the mod-down ONCE, added into d_out.
 int hx_launch_linear_transform(hexl_ks_plan* const* plans, const u64* galois_elts, const u64* const* d_pts, size_t n_rot,
                                const u64* d_pt_identity, u64* d_out, const u64* d_ct, size_t batch) {
     hexl_ks_plan* p0 = plans[0];
-    hexl_ctx* c = p0->ctx;
-    const size_t n = p0->n, L = p0->L, per = 2 * L * n;
-    const size_t chunk = hx_ks_chunk_of(p0, batch);
-    if (int rc = hx_grow_device((void**)&p0->d_scratch, &p0->cap, chunk, hexl_ks_scratch_bytes(p0, 1), nullptr)) return rc;
+    HoistRun run(p0, hx_ks_chunk_of(p0, batch));
+    if (int rc = run.reserve()) return rc;
+    hexl_ctx* c = run.c;
     // the per-call table of the c0 kernel. The source is pageable host memory: the copy has left it when hipMemcpyAsync returns, and
     // the stream orders it behind the previous call's kernels that read the table
     std::vector<HxLtRot> table(n_rot);
     for (size_t r = 0; r < n_rot; ++r) table[r] = HxLtRot{d_pts[r], galois_elts[r]};
     if (int rc = hx_reserve_device(c, &c->d_shared, &c->d_shared_bytes, n_rot * sizeof(HxLtRot))) return rc;
     HX_CHECK(hipMemcpyAsync(c->d_shared, table.data(), n_rot * sizeof(HxLtRot), hipMemcpyHostToDevice, c->stream));
-    p0->cur = c->stream;
-    p0->cur_scratch = p0->d_scratch;
-    const int lazy = ksf_lazy(p0);
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-        const size_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-        const u64* ct = d_ct + b0 * per;
-        u64* out = d_out + b0 * per;
-        const KsArgsF up = ksf_args(p0, p0, nullptr, ct + L * n, nb);
-        if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto Z) { return run_hoist_up<N, E, Z>(c, up); })) return rc;
+    const size_t half = run.per / 2;
+    return run.chunks(batch, [&](size_t b0, size_t nb) {
+        const u64* ct = d_ct + b0 * run.per;
+        u64* out = d_out + b0 * run.per;
+        if (int rc = run.up(ct + half, nb)) return rc;
         if (int rc = hx_launch_galois_c0_pt(p0, out, ct, (const HxLtRot*)c->d_shared, n_rot, d_pt_identity, nb)) return rc;
-        for (size_t r = 0; r < n_rot; ++r) {
-            const KsArgsF a = ksf_args(plans[r], p0, nullptr, nullptr, nb);          // plan r's keys, plans[0]'s scratch
-            if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto) {
-                    return run_lt_mac<decltype(N)::value, decltype(E)::value>(c, a, (u32)galois_elts[r], d_pts[r], r == 0);
-                }))
-                return rc;
-        }
-        KsArgsF down = ksf_args(p0, p0, out, nullptr, nb);
-        down.overwrite = 0;                                        // accumulated into what the c0 kernel wrote
-        if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto Z) { return run_lt_down<N, E, Z>(c, down); })) return rc;
-    }
-    return 0;
+        for (size_t r = 0; r < n_rot; ++r)
+            if (int rc = run.mac(plans[r], (u32)galois_elts[r], r ? KSF_MAC_PT_ACC : KSF_MAC_PT_FIRST, d_pts[r], nullptr, nb)) return rc;
+        return run.down(p0, out, nb);
+    });
 }
 
 // ---- baby-step/giant-step linear transform (hexl_linear_transform_bsgs): out = sum_j Rot_{G_j}( sum_i pt_{j,i} . Rot_{g_i}(ct) ) ----
-// one giant step's step 3: the weighted sum of the stored baby products into a.prod, no keys
-template <int LOGN, int LOGE>
-static int run_lt_bsgs_sum(hexl_ctx* c, const KsArgsF& a, const HxBsgsTerm* d_terms, u32 n_terms) {
-    using G = Geom<LOGN, LOGE>;
-    const HoistGeom h{LOGN, LOGE, G::KL, G::WB, 1};
-    const u32 by = a.nb < 8 ? a.nb : 8;                            // as run_chunk_f64
-    hipLaunchKernelGGL(k_lt_bsgs_sum, dim3((a.L + 1) * G::N / 256, by), dim3(256), 0, c->stream, a, h, d_terms, n_terms);
-    return (int)hipGetLastError();
-}
-
 static size_t bsgs_slice_bytes(const hexl_ks_plan* p) { return 2 * (size_t(p->L) + 1) * p->n * sizeof(double); }   // one baby step, one instance
 size_t hx_lt_bsgs_chunk(const hexl_ks_plan* p, size_t n_baby, size_t batch) {
     const size_t chunk = hx_ks_chunk_of(p, batch);
-    if (hx_knob("HEXL_KS_CHUNK", 0) > 0 || !n_baby || !chunk) return chunk;      // a forced chunk stays
+    if (hx_ks_chunk_forced() || !n_baby || !chunk) return chunk;   // a forced chunk stays
     const size_t fit = HX_LT_BSGS_STORE_BYTES / bsgs_slice_bytes(p) / n_baby;
     return fit >= chunk ? chunk : fit ? fit : 1;
 }
@@ -878,26 +866,26 @@ size_t hexl_lt_bsgs_scratch_bytes(const hexl_ks_plan* p, size_t n_baby, size_t b
     return chunk * (n_baby * bsgs_slice_bytes(p) + fixed);
 }
 
-// Arguments checked by hexl_linear_transform_bsgs (ckks_ops.hip). One lane on the context's stream; per chunk:
+// Arguments checked by hexl_linear_transform_bsgs (ckks_ops.hip). Per chunk:
 //   the mod-up of c1 once; one multiply-accumulate per baby step that some row uses, its prod pointed at that step's slice of the baby store
 //   (u is free after the last of them);
 //   per giant step j: the key-free part of row j into t_j (hx_launch_galois_c0_pt), the weighted sum of the stored products into prod
 //   (k_lt_bsgs_sum) and the mod-down ONCE, added into t_j -- hexl_linear_transform's words for row j; then t_j rotated by G_j as
-//   hexl_rotate_hoisted rotates it (mod-up of t_j's component 1 into the same u, giant_plans[j]'s keys) with the key-free part
+//   hexl_rotate_hoisted rotates it (mod-up of t_j's component 1 into the same u, giant_plans[j]'s keys and tier) with the key-free part
 //   sigma_{G_j}(t_j[0]) WRITTEN to d_out by the first giant step and ADDED by the later ones, and the mod-down accumulating on top.
 //   G_j = 1: t_j itself is written (the first giant step computes it in place in d_out) or added.
-// Every word that reaches d_out is canonical and every addition is modulo q_i, so d_out holds the sum of the per-row results of the
-// two parent entry points, word for word.
+// Everything but a rotated giant step's steps 4-7 runs on p0's tier. Every word that reaches d_out is canonical and every addition is
+// modulo q_i, so d_out holds the sum of the per-row results of the two parent entry points, word for word.
 int hx_launch_linear_transform_bsgs(hexl_ks_plan* p0, hexl_ks_plan* const* baby_plans, const u64* baby_elts, size_t n_baby,
                                     hexl_ks_plan* const* giant_plans, const u64* giant_elts, size_t n_giant, const u64* const* d_pts,
                                     const u64* const* d_pt_identity, u64* d_out, const u64* d_ct, size_t batch) {
-    hexl_ctx* c = p0->ctx;
-    const size_t n = p0->n, L = p0->L, per = 2 * L * n, slice = 2 * (L + 1) * n;
-    const size_t chunk = hx_lt_bsgs_chunk(p0, n_baby, batch);
-    if (int rc = hx_grow_device((void**)&p0->d_scratch, &p0->cap, chunk, hexl_ks_scratch_bytes(p0, 1), nullptr)) return rc;
+    HoistRun run(p0, hx_lt_bsgs_chunk(p0, n_baby, batch));
+    if (int rc = run.reserve()) return rc;
+    hexl_ctx* c = run.c;
+    const size_t chunk = run.chunk, half = run.per / 2, slice = 2 * (size_t(p0->L) + 1) * p0->n;
     if (n_baby)
         if (int rc = hx_grow_device((void**)&p0->d_bsgs_b, &p0->bsgs_b_cap, n_baby * chunk, slice * sizeof(double), nullptr)) return rc;
-    if (int rc = hx_grow_device((void**)&p0->d_bsgs_t, &p0->bsgs_t_cap, chunk, per * sizeof(u64), nullptr)) return rc;
+    if (int rc = hx_grow_device((void**)&p0->d_bsgs_t, &p0->bsgs_t_cap, chunk, run.per * sizeof(u64), nullptr)) return rc;
     // the per-call tables, row after row: what the c0 kernel walks (plaintext, Galois element) and what the sum kernel walks (plaintext,
     // baby slice). Pageable sources, stream-ordered behind the previous call's readers, as hx_launch_linear_transform's table
     std::vector<HxLtRot> rots;
@@ -922,25 +910,14 @@ int hx_launch_linear_transform_bsgs(hexl_ks_plan* p0, hexl_ks_plan* const* baby_
     }
     const HxLtRot* d_rots = (const HxLtRot*)c->d_shared;
     const HxBsgsTerm* d_terms = (const HxBsgsTerm*)(d_rots + total);
-    p0->cur = c->stream;
-    p0->cur_scratch = p0->d_scratch;
-    const int lazy = ksf_lazy(p0);
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-        const size_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-        const u64* ct = d_ct + b0 * per;
-        u64* out = d_out + b0 * per;
+    return run.chunks(batch, [&](size_t b0, size_t nb) {
+        const u64* ct = d_ct + b0 * run.per;
+        u64* out = d_out + b0 * run.per;
         if (total) {
-            const KsArgsF up = ksf_args(p0, p0, nullptr, ct + L * n, nb);
-            if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto Z) { return run_hoist_up<N, E, Z>(c, up); })) return rc;
-            for (size_t i = 0; i < n_baby; ++i) {
-                if (!used[i]) continue;
-                KsArgsF a = ksf_args(baby_plans[i], p0, nullptr, nullptr, nb);       // plan i's keys, p0's u
-                a.prod = p0->d_bsgs_b + i * chunk * slice;
-                if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto) {
-                        return run_hoist_mac<decltype(N)::value, decltype(E)::value>(c, a, (u32)baby_elts[i]);
-                    }))
-                    return rc;
-            }
+            if (int rc = run.up(ct + half, nb)) return rc;
+            for (size_t i = 0; i < n_baby; ++i)
+                if (used[i])
+                    if (int rc = run.mac(baby_plans[i], (u32)baby_elts[i], KSF_MAC_STORE, nullptr, p0->d_bsgs_b + i * chunk * slice, nb)) return rc;
         }
         for (size_t j = 0; j < n_giant; ++j) {
             const size_t cnt = off[j + 1] - off[j];
@@ -948,27 +925,19 @@ int hx_launch_linear_transform_bsgs(hexl_ks_plan* p0, hexl_ks_plan* const* baby_
             u64* t = (j == 0 && g == 1) ? out : p0->d_bsgs_t;
             if (int rc = hx_launch_galois_c0_pt(p0, t, ct, d_rots + off[j], cnt, d_pt_identity ? d_pt_identity[j] : nullptr, nb)) return rc;
             if (cnt) {
-                KsArgsF down = ksf_args(p0, p0, t, nullptr, nb);
-                down.overwrite = 0;                                // accumulated into what the c0 kernel wrote
-                if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto) {
-                        return run_lt_bsgs_sum<decltype(N)::value, decltype(E)::value>(c, down, d_terms + off[j], (u32)cnt);
-                    }))
-                    return rc;
-                if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto Z) { return run_lt_down<N, E, Z>(c, down); })) return rc;
+                if (int rc = run.sum(d_terms + off[j], cnt, nb)) return rc;
+                if (int rc = run.down(p0, t, nb)) return rc;        // accumulated into what the c0 kernel wrote
             }
             if (g == 1) {
                 if (j)
                     if (int rc = hx_launch_galois_add(p0, out, t, nb, 1, 2)) return rc;
                 continue;
             }
-            const KsArgsF up = ksf_args(p0, p0, nullptr, t + L * n, nb);             // the babies are stored: u is free
-            if (int rc = hx_with_f64_geom(p0->logn, lazy, [&](auto N, auto E, auto Z) { return run_hoist_up<N, E, Z>(c, up); })) return rc;
-            if (int rc = j ? hx_launch_galois_add(p0, out, t, nb, g, 1) : hx_launch_galois_c0(c, out, t, nb, (u32)L, p0->logn, g)) return rc;
-            KsArgsF a = ksf_args(giant_plans[j], p0, out, nullptr, nb);
-            a.overwrite = 0;
-            if (int rc = hx_with_f64_geom(p0->logn, ksf_lazy(giant_plans[j]), [&](auto N, auto E, auto Z) { return run_hoist_down<N, E, Z>(c, a, g); }))
-                return rc;
+            if (int rc = run.up(t + half, nb)) return rc;           // the babies are stored: u is free
+            if (int rc = j ? hx_launch_galois_add(p0, out, t, nb, g, 1) : hx_launch_galois_c0(c, out, t, nb, p0->L, p0->logn, g)) return rc;
+            if (int rc = run.mac(giant_plans[j], g, KSF_MAC_STORE, nullptr, nullptr, nb)) return rc;
+            if (int rc = run.down(giant_plans[j], out, nb)) return rc;
         }
-    }
-    return 0;
+        return 0;
+    });
 }

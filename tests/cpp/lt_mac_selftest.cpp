@@ -1,6 +1,6 @@
 // lt_mac_selftest.cpp -- host replay of the linear transform's scalar chain (hexl-fpga_amd/csrc/f64_arith.hpp lt_pt / lt_mac / lt_mac_acc,
-// called by keyswitch_f64.hip k_ksf_mac_galois_pt and ckks_ops.hip k_galois_c0_pt) against unsigned __int128, as pt_mul_selftest.cpp
-// replays the plaintext multiply's: IEEE-754 double mul / add / fma / rint round the same way on x86 (-mfma) and on gfx950.
+// called by keyswitch_f64.hip k_ksf_mac_galois's plaintext modes and ckks_ops.hip k_galois_c0_pt) against unsigned __int128, as
+// pt_mul_selftest.cpp replays the plaintext multiply's: IEEE-754 double mul / add / fma / rint round the same way on x86 (-mfma) and on gfx950.
 //   usage: lt_mac_selftest <draws> <modulus>...      (tests/test_lt_model.py builds it: g++ -O2 -mfma -ffp-contract=off)
 // Per modulus q: the plaintext word, the inner sum and the previous accumulator over {0, 1, q - 1, q/2 - 1, q/2, q/2 + 1} (every
 // triple), then <draws> pseudo-random triples. The kernels hand the chain CENTRED inner sums and accumulators (outputs of reduce), so
