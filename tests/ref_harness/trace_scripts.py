@@ -25,7 +25,11 @@ STUB = """#!/bin/bash
 python3 - "$0" "$@" <<'EOF'
 import json, os, sys
 base = json.load(open(os.environ["HEXL_TRACE_BASE_ENV"]))
-env = {k: v for k, v in os.environ.items() if base.get(k) != v and not k.startswith("HEXL_TRACE_") and k not in ("_", "SHLVL", "PWD", "OLDPWD")}
+try:    # the environment this interpreter was STARTED with: what a start-up hook sets afterwards (os.environ) is not in it
+    seen = dict(os.fsdecode(kv).split("=", 1) for kv in open("/proc/self/environ", "rb").read().split(b"\\0") if b"=" in kv)
+except OSError:
+    seen = dict(os.environ)
+env = {k: v for k, v in seen.items() if base.get(k) != v and not k.startswith("HEXL_TRACE_") and k not in ("_", "SHLVL", "PWD", "OLDPWD")}
 with open(os.environ["HEXL_TRACE_FILE"], "a") as f:
     f.write(json.dumps({"script": os.environ["HEXL_TRACE_SCRIPT"], "exe": os.path.basename(sys.argv[1]), "argv": sys.argv[2:], "env": env}) + "\\n")
 EOF
@@ -53,6 +57,8 @@ def trace(ref: Path, out: Path) -> int:
         # calibration: a stub started directly, without a script in between, reports what its own interpreters add to the environment
         # (bash, python3: locale coercion, start-up hooks of the machine; such values may differ from process to process). Those names
         # are no script's doing and are dropped from every recorded invocation, so the trace does not depend on where it is made.
+        # (The stub reads the environment its python3 was started with, so what python3's own start-up sets never reaches it: a
+        # calibration by name alone misses a variable whose value happens to equal the tracer's in this one run and differs later.)
         cal = tmp / "calibration.jsonl"
         subprocess.run([str(tmp / "test_fwd_ntt")], cwd=tmp, capture_output=True, text=True, timeout=120,
                        env=dict(env, HEXL_TRACE_FILE=str(cal), HEXL_TRACE_BASE_ENV=str(base), HEXL_TRACE_SCRIPT=""))

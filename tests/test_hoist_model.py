@@ -29,6 +29,22 @@ def test_identity_rotation_is_the_oracles_keyswitch(orc, n, L, K, chain):
         assert np.array_equal(got, want), first_mismatch(got, want, ("component", "limb", "coefficient"), (2, L, n))
 
 
+@pytest.mark.parametrize("n,L,K,chain", [(1024, 2, 4, "gen"), (2048, 3, 5, "seal")])
+def test_identity_rotation_with_more_key_moduli_than_digits_plus_one(orc, n, L, K, chain):
+    """K = L + 2: the special prime is modulus K - 1 and modulus L is not used at all; the host keys keep K rows per component. The
+    oracle's keyswitch takes rns_modulus_size = L + 1 (ckks_model.rotate), as the GPU tests of such plans do. An L where K - 1 belongs
+    anywhere in the model -- slot list, key row, special prime -- would show here"""
+    case = KsCase(orc, n, L, K, seed=81, moduli=seal_chain(orc, K, n) if chain == "seal" else None)
+    assert int(case.moduli[L]) != int(case.moduli[K - 1]) and case.rns == L + 1
+    for ct in (ct_of(orc, case, 0), extreme_ciphertext(case, 1, 2)):
+        got, want = rotate_hoisted(orc, case, ct, 1), rotate(orc, case, ct, 1)
+        assert np.array_equal(got, want), first_mismatch(got, want, ("component", "limb", "coefficient"), (2, L, n))
+    unused = KsCase(orc, n, L, K, seed=81, moduli=case.moduli)
+    for key in unused.keys:                                            # rows of the unused modulus L: read by nobody
+        key.reshape(2, K, n)[:, L] = 0
+    assert np.array_equal(rotate_hoisted(orc, unused, ct, 1), want), "the model read a key row of the unused modulus"
+
+
 @pytest.fixture(scope="module")
 def rlwe(orc):
     return RlweCase(orc, 1024, 2, 3, 50, seed=4)

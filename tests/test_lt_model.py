@@ -46,6 +46,22 @@ def test_all_ones_plaintext_is_the_hoisted_rotation(orc, g):
         assert np.array_equal(got, want), first_mismatch(got, want, ("component", "limb", "coefficient"), (2, L, n))
 
 
+@pytest.mark.parametrize("g", ["1", "3"])
+def test_all_ones_plaintext_is_the_hoisted_rotation_with_more_key_moduli_than_digits_plus_one(orc, g):
+    """K = L + 2: row L of a plaintext is modulo the special prime moduli[K - 1]; hoist_model is pinned to the oracle at this K in
+    test_hoist_model.py. A plaintext of ones in every row but row L shows that row L is read"""
+    n, L, K = 1024, 2, 4
+    g = int(g)
+    case = KsCase(orc, n, L, K, seed=83)
+    assert int(case.moduli[L]) != int(case.moduli[K - 1])
+    for ct in (ct_of(orc, case, 0), extreme_ciphertext(case, 1, 2)):
+        got, want = linear_transform(orc, [case], [g], [ones_plaintext(case)], None, ct), rotate_hoisted(orc, case, ct, g)
+        assert np.array_equal(got, want), first_mismatch(got, want, ("component", "limb", "coefficient"), (2, L, n))
+    twos = ones_plaintext(case)
+    twos[L * n:] = 2
+    assert not np.array_equal(linear_transform(orc, [case], [g], [twos], None, ct), want), "row L of the plaintext is not read"
+
+
 @pytest.mark.parametrize("identity", [False, True])
 def test_decrypts_to_the_weighted_sum_of_rotations(orc, identity):
     rc = RlweCase(orc, 1024, 2, 3, 50, seed=4)
