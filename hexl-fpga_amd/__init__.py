@@ -63,6 +63,10 @@ C_ABI = {
     "hexl_rns_ntt_fwd": [_vp, _vp, _vp, _sz, _u64],
     "hexl_rns_ntt_inv": [_vp, _vp, _vp, _sz, _u64],
     "hexl_multiply_plain": [_vp, _vp, _vp, _vp, _sz, _u64, _u64, _sz, _i],
+    "hexl_rns_from_f64": [_vp, _vp, _vp, _sz, _u64],
+    "hexl_rns_to_f64": [_vp, _vp, _vp, _sz, _u64],
+    "hexl_ckks_encode": [_vp, _vp, _vp, _sz, _u64, ctypes.c_double],
+    "hexl_ckks_decode": [_vp, _vp, _vp, _sz, _u64, ctypes.c_double],
     "hexl_ks_scratch_bytes": [_vp, _sz],
     "hexl_ntt_fwd_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64],
     "hexl_ntt_inv_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64, _u64, _u64],
@@ -256,6 +260,25 @@ class KeySwitchPlan:
         form; pt_batch = 1 or batch; out may be ct unless accumulating"""
         _check(lib().hexl_multiply_plain(self.h, _ptr(out), _ptr(ct), _ptr(pt), batch, n_components, n_limbs, pt_batch,
                                          1 if accumulate else 0), "hexl_multiply_plain")
+
+    def rns_from_f64(self, out, coeffs, count: int, n_limbs: int):
+        """out[count][n_limbs][n] = NTT_i(rint(coeffs[count][n]) mod q_i): real coefficients (float64, natural order) to NTT-form limbs,
+        exact for |rint(c)| < 2^62; a coefficient outside that raises the range flag (range_check)"""
+        _check(lib().hexl_rns_from_f64(self.h, _ptr(out), _ptr(coeffs), count, n_limbs), "hexl_rns_from_f64")
+
+    def rns_to_f64(self, coeffs, inp, count: int, n_limbs: int):
+        """coeffs[count][n] (float64) = the centred CRT value of every coefficient of inp[count][n_limbs][n] (NTT form): exact below 2^53,
+        within 2^-50 relative above"""
+        _check(lib().hexl_rns_to_f64(self.h, _ptr(coeffs), _ptr(inp), count, n_limbs), "hexl_rns_to_f64")
+
+    def ckks_encode(self, out, slots, count: int, n_limbs: int, scale: float):
+        """out[count][n_limbs][n] = the NTT-form plaintext of slots[count][n/2][2] (float64 re, im) at `scale`: slot k at the evaluation
+        point zeta^(5^k), coefficients rounded to nearest"""
+        _check(lib().hexl_ckks_encode(self.h, _ptr(out), _ptr(slots), count, n_limbs, scale), "hexl_ckks_encode")
+
+    def ckks_decode(self, slots, inp, count: int, n_limbs: int, scale: float):
+        """slots[count][n/2][2] = the slot values of the plaintext inp[count][n_limbs][n] divided by `scale`"""
+        _check(lib().hexl_ckks_decode(self.h, _ptr(slots), _ptr(inp), count, n_limbs, scale), "hexl_ckks_decode")
 
     def keyswitch_host(self, results, t_targets):
         n = len(results)

@@ -339,6 +339,11 @@ extern "C" int hexl_ks_plan_destroy(hexl_ks_plan* p) {
     if (p->d_rot_t) (void)hipFree(p->d_rot_t);
     if (p->d_bsgs_b) (void)hipFree(p->d_bsgs_b);
     if (p->d_bsgs_t) (void)hipFree(p->d_bsgs_t);
+    if (p->d_emb_roots) (void)hipFree(p->d_emb_roots);
+    if (p->d_emb_perm) (void)hipFree(p->d_emb_perm);
+    if (p->d_garner) (void)hipFree(p->d_garner);
+    if (p->d_enc_coeffs) (void)hipFree(p->d_enc_coeffs);
+    if (p->d_enc_words) (void)hipFree(p->d_enc_words);
     delete p;
     return 0;
 }

@@ -123,6 +123,26 @@ HX_HD double lt_mac_acc(double inner, double pt, double prev, const Mod m) { ret
 // the first term of a sum: no prev (the accumulator is written, not read)
 HX_HD double lt_mac(double inner, double pt, const Mod m) { return reduce(mul_mod(pt, inner, m), m); }
 
+// ---- the scalar chain of hexl_rns_from_f64 / hexl_ckks_encode (ckks_encode.hip k_rns_from_f64), here so that
+// tests/cpp/from_f64_selftest.cpp replays the kernel's own source against __int128 ------------------------------------------------
+// A real coefficient c -> the centred residue of rint(c) modulo p (|result| <= p/2 + 2), EXACT for every finite c with
+// |rint(c)| < 2^62 -- doubles above 2^53 are integers already and are reduced as the integers they are, not as "the double":
+//   x = rint(c)                        ties to even; -0.0 stays -0.0 and ends as the word 0
+//   x = a 2^31 + b                     a = rint(x 2^-31): a power-of-two scaling and a rounding to an integer below 2^31 (+1), both
+//                                      exact; b = x - a 2^31 is an integer with |b| <= 2^30, so the fma's single rounding is the identity
+//   x mod p = (a mod p)(2^31 mod p) + (b mod p): mul_mod on two reduce outputs (|.| <= p/2 + 2: its operand range, |product| <= 0.7p)
+//   plus a reduce output, |sum| <= 1.2p + 2 < 2^53 -- exact and inside reduce's domain.
+// 2^31 mod p is one more reduce (no table: the chain runs once per coefficient, in front of a whole transform).
+constexpr double F64_INT_LIMIT = 4611686018427387904.0;          // 2^62
+// the precondition, on x = rint(c): finite and below 2^62 in magnitude (false for NaN)
+HX_HD bool f64_int_in_range(double x) { return __builtin_fabs(x) < F64_INT_LIMIT; }
+HX_HD double f64_to_residue(double c, const Mod m) {
+    const double x = __builtin_rint(c);
+    const double a = __builtin_rint(x * (1.0 / 2147483648.0));
+    const double b = __builtin_fma(-a, 2147483648.0, x);
+    return reduce(mul_mod(reduce(a, m), reduce(2147483648.0, m), m) + reduce(b, m), m);
+}
+
 // The STRICT butterflies (every value reduced after every operation) leave room above 2^52: the largest intermediate is the
 // inverse butterfly's |h - k p| <= (1.31 + 0.22) p for |d| = |X - Y| <= p + 4 (quotient from the product: three roundings of a
 // value near p/2, ulp 1/2), the forward's |X + t| <= 1.4 p, all below 2^53 up to p ~ 2^52.39. The standalone _NTT / _INTT fast

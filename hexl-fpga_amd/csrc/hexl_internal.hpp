@@ -189,6 +189,14 @@ struct hexl_ks_plan {
     size_t bsgs_b_cap = 0;            // (baby step, instance) slices of 2 (L + 1) n doubles
     u64* d_bsgs_t = nullptr;          // one giant step's inner sum t_j: [bsgs_t_cap][2][L][n] canonical words
     size_t bsgs_t_cap = 0;
+    // device-side encode / decode (ckks_encode.hip), all allocated at first use
+    double* d_emb_roots = nullptr;    // [2n][2]: zeta^t = exp(i pi t / n) as (re, im), computed in long double and rounded once
+    u32* d_emb_perm = nullptr;        // [n/2]: slot k held by position p of the embedding FFT's bit-reversed side (5^k = 4 bitrev(p) + 1 mod 2n)
+    double* d_garner = nullptr;       // [16][16][2]: row i, column j < i = (q_j^-1 mod q_i centred, fl(./q_i)): Garner's constants for every prefix
+    double* d_enc_coeffs = nullptr;   // real coefficients of enc_coeffs_cap instances, n doubles each (grow-only)
+    size_t enc_coeffs_cap = 0;
+    u64* d_enc_words = nullptr;       // coefficient-form limbs of enc_words_cap (instance, limb) polynomials, n words each (grow-only)
+    size_t enc_words_cap = 0;
 };
 
 // launcher prototypes implemented per translation unit
@@ -249,6 +257,10 @@ int hx_launch_galois_add(hexl_ks_plan* p, u64* d_out, const u64* d_t, size_t nb,
 int hx_launch_rns_ntt(hexl_ks_plan*, u64* d_out, const u64* d_in, size_t count, u32 n_limbs, bool inverse);
 int hx_launch_multiply_plain(hexl_ks_plan*, u64* d_out, const u64* d_ct, const u64* d_pt, size_t batch, u32 n_components, u32 n_limbs,
                              bool per_instance, bool accumulate);
+// device-side encode / decode (ckks_encode.hip); arguments checked by their entry points (hexl_rns_from_f64, hexl_rns_to_f64,
+// hexl_ckks_encode, hexl_ckks_decode). d_slots = nullptr: the real coefficients themselves are the caller's (d_coeffs).
+int hx_launch_encode(hexl_ks_plan*, u64* d_out, const double* d_coeffs, const double* d_slots, size_t count, u32 n_limbs, double scale);
+int hx_launch_decode(hexl_ks_plan*, double* d_coeffs, double* d_slots, const u64* d_in, size_t count, u32 n_limbs, double scale);
 u32 hx_ks_x_loge();
 // index of coefficient held in register r of thread tid after a forward transform ("B layout")
 u32 hx_idxB(u32 logn, u32 r, u32 tid);

@@ -283,6 +283,37 @@ int hexl_rns_ntt_inv(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_in, 
  * with accumulate != 0 among them), another pt_batch or a size that overflows: HEXL_E_BADARG. */
 int hexl_multiply_plain(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_ct, const uint64_t* d_pt, size_t batch,
                         uint64_t n_components, uint64_t n_limbs, size_t pt_batch, int accumulate);
+/* Encode and decode on the device: the canonical embedding and the change between real coefficients and RNS limbs, so that weights and
+ * results can cross the bus as slot vectors (n/2 complex doubles) instead of [n_limbs][n] words. All four are asynchronous on the
+ * context's stream and need no keys. FP64 plans only (every modulus < 2^52), n = 1024 ... 32768, 1 <= n_limbs <= K: the moduli are the
+ * plan's first n_limbs, as for hexl_rns_ntt_fwd. The word side is [count][n_limbs][n] in NTT form, in the transforms' bit-reversed output
+ * order: what hexl_rns_ntt_fwd writes and what hexl_multiply_plain and the d_pts of hexl_linear_transform read (n_limbs = K = L + 1).
+ * zeta = exp(i pi / n); slot k < n/2 belongs to the evaluation point zeta^(5^k mod 2n) (SEAL's convention), so hexl_rotate with g = 5
+ * moves slot k + 1 to slot k.
+ *   hexl_rns_from_f64   d_coeffs double [count][n], real coefficients in natural order; out[c][i] = NTT_i(rint(coeff_j) mod q_i), every
+ *                       word canonical. rint rounds to nearest, ties to even; a negative integer r maps to q_i - (|r| mod q_i), or 0.
+ *                       Exact for every finite coefficient with |rint(c)| < 2^62 (doubles above 2^53 are reduced as the integers they
+ *                       are). A coefficient outside that raises the plan's input-range flag (hexl_ks_range_check); the words of that
+ *                       instance are then unspecified, nothing else is affected.
+ *   hexl_rns_to_f64     the reverse: INTT_i of every limb, then per coefficient the CRT value x in (-Q/2, Q/2), Q = q_0 ... q_(n_limbs-1),
+ *                       as a double: exact when |x| < 2^53, relative error at most 2^-50 otherwise. Precondition: every input word is
+ *                       below its modulus.
+ *   hexl_ckks_encode    d_slots double [count][n/2][2] (re, im); out = hexl_rns_from_f64 of
+ *                       coeff_j = scale (2/n) Re(sum_k z_k zeta^(-j 5^k)), the real polynomial m with m(zeta^(5^k)) = scale z_k before
+ *                       rounding. The range precondition and flag are those of hexl_rns_from_f64, on the scaled coefficients.
+ *   hexl_ckks_decode    z_k = m(zeta^(5^k)) / scale with m's coefficients from hexl_rns_to_f64.
+ * The transforms between slots and coefficients are FFTs in double on correctly rounded twiddles: the 2-norm error of a result is
+ * within 16 log2(n) 2^-53 of its 2-norm.
+ * HEXL_E_BADARG: a null pointer (count == 0 does not excuse it), a plan on the integer kernels, n_limbs outside 1 ... K, a scale that is
+ * not finite and positive, a size that overflows, input and output ranges that overlap. count == 0 returns 0 after these checks.
+ * Device memory, kept in the plan and grow-only: the real coefficients of one chunk (encode, decode: n doubles per instance) and its
+ * coefficient-form limbs (rns_to_f64, decode: n_limbs x n words per instance); a chunk is 256 instances at n = 16384 and the same number
+ * of coefficients at every other n. Tables made at first use: the 2n-th roots of unity (32 n bytes), the slot order (2 n bytes) and
+ * Garner's constants (4 KiB). */
+int hexl_rns_from_f64(hexl_ks_plan* plan, uint64_t* d_out, const double* d_coeffs, size_t count, uint64_t n_limbs);
+int hexl_rns_to_f64(hexl_ks_plan* plan, double* d_coeffs, const uint64_t* d_in, size_t count, uint64_t n_limbs);
+int hexl_ckks_encode(hexl_ks_plan* plan, uint64_t* d_out, const double* d_slots, size_t count, uint64_t n_limbs, double scale);
+int hexl_ckks_decode(hexl_ks_plan* plan, double* d_slots, const uint64_t* d_in, size_t count, uint64_t n_limbs, double scale);
 /* Arithmetic tier per limb (introspection for logs and tests): tiers[i], i < key_modulus_size, = the forward transforms' range-
  * reduction period modulo q_i on the FP64 path -- 12 / 6 / 3 for q_i <= 2^49 / 2^50 / 2^51 (1 + 2^-7), 0 = every value reduced after
  * every operation (q_i up to 2^52); -1 for every limb of a plan on the integer kernels (a modulus >= 2^52). Every transform runs modulo
