@@ -63,6 +63,7 @@ C_ABI = {
     "hexl_rns_ntt_fwd": [_vp, _vp, _vp, _sz, _u64],
     "hexl_rns_ntt_inv": [_vp, _vp, _vp, _sz, _u64],
     "hexl_multiply_plain": [_vp, _vp, _vp, _vp, _sz, _u64, _u64, _sz, _i],
+    "hexl_ct_lincomb": [_vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _sz, _vp, _sz, _vp, _sz, _u64, _u64],
     "hexl_rns_from_f64": [_vp, _vp, _vp, _sz, _u64],
     "hexl_rns_to_f64": [_vp, _vp, _vp, _sz, _u64],
     "hexl_ckks_encode": [_vp, _vp, _vp, _sz, _u64, ctypes.c_double],
@@ -260,6 +261,21 @@ class KeySwitchPlan:
         form; pt_batch = 1 or batch; out may be ct unless accumulating"""
         _check(lib().hexl_multiply_plain(self.h, _ptr(out), _ptr(ct), _ptr(pt), batch, n_components, n_limbs, pt_batch,
                                          1 if accumulate else 0), "hexl_multiply_plain")
+
+    def ct_lincomb(self, out, cts, batch: int, n_components: int, n_limbs: int, weights=None, in_limbs=None, pt=None, pt_batch: int = 1,
+                   const=None):
+        """out[batch][n_components][n_limbs][n] = sum_t weights[t][i] * cts[t] + (component 0 only) pt[pt_batch][n_limbs][n] + const[i]
+        mod q_i, word by word in NTT form. cts: 1 ... 8 device tensors, term t [batch][n_components][in_limbs[t]][n] read through its first
+        n_limbs limbs (in_limbs None: all n_limbs); weights: host [n_terms][n_limbs] residues (None: all 1; q_i - 1 subtracts); const: host
+        [n_limbs] residues or None; out may be a term whose in_limbs is n_limbs"""
+        u64s = lambda a: None if a is None else np.ascontiguousarray(np.asarray([int(v) for v in np.asarray(a, dtype=object).reshape(-1)],
+                                                                                dtype=np.uint64))
+        w, il, c = u64s(weights), u64s(in_limbs), u64s(const)
+        if (w is not None and w.size != len(cts) * n_limbs) or (il is not None and il.size != len(cts)) or (c is not None and c.size != n_limbs):
+            raise ValueError("ct_lincomb: weights are [n_terms][n_limbs], in_limbs [n_terms], const [n_limbs]")
+        hp = lambda a: None if a is None else a.ctypes.data
+        _check(lib().hexl_ct_lincomb(self.h, _ptr(out), ptr_array(cts), hp(il), hp(w), len(cts), None if pt is None else _ptr(pt), pt_batch,
+                                     hp(c), batch, n_components, n_limbs), "hexl_ct_lincomb")
 
     def rns_from_f64(self, out, coeffs, count: int, n_limbs: int):
         """out[count][n_limbs][n] = NTT_i(rint(coeffs[count][n]) mod q_i): real coefficients (float64, natural order) to NTT-form limbs,

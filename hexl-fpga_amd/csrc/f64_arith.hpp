@@ -123,6 +123,20 @@ HX_HD double lt_mac_acc(double inner, double pt, double prev, const Mod m) { ret
 // the first term of a sum: no prev (the accumulator is written, not read)
 HX_HD double lt_mac(double inner, double pt, const Mod m) { return reduce(mul_mod(pt, inner, m), m); }
 
+// ---- the scalar chains of the ciphertext linear combination (rns_ops.hip k_ct_lincomb), here so that tests/cpp/lincomb_selftest.cpp
+// replays the kernel's own source against 128-bit integers -----------------------------------------------------------------------------
+// One term: a canonical word x (0 <= x < p < 2^52, exact as a double) times a constant weight, w the weight centred (|w| <= p/2) and
+// wp = fl(w / p), both made on the host. x is inside mul_shoup's |x| <= 1.5p as it is -- no range reduction of the word -- so
+// |result| <= (0.5 + x / (2p)) p <= p. Exact: |h - k p| <= |result| + |l| <= p + 2^50 < 2^53.
+HX_HD double lc_term(double x, double w, double wp, const Mod m) { return mul_shoup(x, w, wp, m); }
+// acc' = (acc + u) mod p, centred: acc a partial sum as this function leaves it (|acc| <= p/2 + 2; 0 in front of the first term), u an
+// addend with |u| <= p -- an lc_term output, a canonical word taken as it is (a term of weight 1, a plaintext word: 0 <= u < p), or a
+// centred constant (|u| <= p/2). |acc + u| <= 1.5p + 2 < 0.75 2^53 + 2: the sum is an exact integer inside reduce's domain, and
+// |acc'| <= p/2 + 2 again. EVERY partial sum is reduced: two un-reduced addends on a centred sum would reach 2.5p > 2^53 at p ~ 2^52.
+HX_HD double lc_add(double acc, double u, const Mod m) { return reduce(acc + u, m); }
+// the sum after its last addend -> the canonical word (lift takes |x| <= p/2 + 2)
+HX_HD double lc_finish(double acc, const Mod m) { return lift(acc, m); }
+
 // ---- the scalar chain of hexl_rns_from_f64 / hexl_ckks_encode (ckks_encode.hip k_rns_from_f64), here so that
 // tests/cpp/from_f64_selftest.cpp replays the kernel's own source against __int128 ------------------------------------------------
 // A real coefficient c -> the centred residue of rint(c) modulo p (|result| <= p/2 + 2), EXACT for every finite c with

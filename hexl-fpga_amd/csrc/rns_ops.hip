@@ -4,6 +4,8 @@
 //                               plan's own tables and that limb's arithmetic tier: the per-limb transform of the rescale
 //                               (ckks_ops.hip k_rs_intt / k_rs_down) without its epilogues                          k_rns_fwd / k_rns_inv
 //   multiply_plain              out[b][k][i] (+)= ct[b][k][i] * pt[b or 0][i] mod q_i, word by word in NTT form     k_pt_mul
+//   ct_lincomb                  out[b][k][i] = sum_t w[t][i] ct_t[b][k][i] + [k == 0] (pt[b or 0][i] + const[i]) mod q_i: up to eight
+//                               ciphertexts, each read once through its first n_limbs limbs     k_ct_lincomb
 // FP64 plans only (moduli < 2^52). Nothing here keeps device memory in the plan or reads its keys.
 #include "hexl_internal.hpp"
 #include "ntt_core_f64.hpp"
@@ -167,6 +169,130 @@ int hx_launch_multiply_plain(hexl_ks_plan* p, u64* d_out, const u64* d_ct, const
     return (int)hipGetLastError();
 }
 
+// ---- ciphertext linear combination ----
+constexpr u32 LC_MAX_TERMS = 8, LC_MAX_LIMBS = 16;               // hexl_ks_plan::tier has 16 limbs
+struct LcWeight { double w, wp; };                                // one term's weight modulo one q_i: centred, and fl(w / q_i) (hxf::lc_term)
+
+// Everything a launch needs travels BY VALUE in the kernel arguments (2.3 KiB of the 4 KiB there are): nothing is uploaded, so there is
+// no copy to order in front of the kernel and no device or pinned memory to keep alive behind an asynchronous call.
+struct LcArgs {
+    const KsModF64* mods;       // [K]
+    const u64* ct[LC_MAX_TERMS];    // term t: [batch][NCOMP][in_limbs[t]][n], read through its first L limbs
+    const u64* pt;              // nullptr, or [pt_stride ? batch : 1][L][n]: component 0 only
+    u64* out;                   // [batch][NCOMP][L][n]; may be ct[t] where in_limbs[t] == L (a lane reads the words it writes, nobody else's)
+    u32 in_limbs[LC_MAX_TERMS];
+    LcWeight wt[LC_MAX_LIMBS][LC_MAX_TERMS];    // limb-major: a workgroup's NT weights are one contiguous run of scalar loads
+    double cst[LC_MAX_LIMBS];   // the constant addend of component 0 modulo q_i, centred (0 when there is none)
+    u32 logn, L;
+    u32 pt_stride;              // 1: one plaintext per instance, 0: one for all
+    u32 has_cst;
+};
+static_assert(sizeof(LcArgs) <= 4096, "the kernel arguments of k_ct_lincomb must fit the 4 KiB kernarg segment");
+
+// One workgroup per (instance, limb, chunk of the polynomial), as k_pt_mul: the modulus and the NT weights of the limb are found once per
+// workgroup (wave-uniform: scalar registers). The component loop runs inside, so the plaintext words and the constant meet component 0
+// only. Every load of a component -- NT x PT_VECS 16-byte vectors per lane, 64 VGPRs at NT = 8 -- is requested before its first product;
+// when all components together are no more than that (NT * NCOMP <= 8) all of them are, as d_out may be a term and a component's loads
+// cannot move above the previous component's stores otherwise. A weight of exactly 1 (wave-uniform test) adds the word as it is.
+template <int NT, int NCOMP>
+__global__ __launch_bounds__(PT_THREADS) void k_ct_lincomb(LcArgs a) {
+    typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
+    constexpr bool ALL = NT * NCOMP <= 8;
+    const u32 bi = blockIdx.x >> (a.logn - PT_LOG_CHUNK), ch = blockIdx.x - (bi << (a.logn - PT_LOG_CHUNK));
+    const u32 b = bi / a.L, i = bi - b * a.L;
+    const Mod m = a.mods[i].m;
+    const size_t n = size_t(1) << a.logn, chunk = size_t(ch) << PT_LOG_CHUNK;
+    const bool has_pt = a.pt != nullptr;
+    u2 p[PT_VECS], c[ALL ? NCOMP : 1][NT][PT_VECS];
+    if (has_pt) {
+        const u2* pt = reinterpret_cast<const u2*>(a.pt + (size_t(b) * a.pt_stride * a.L + i) * n + chunk);
+#pragma unroll
+        for (u32 j = 0; j < PT_VECS; ++j) p[j] = pt[threadIdx.x + j * PT_THREADS];
+    }
+    auto load = [&](int k, int slot) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const u2* src = reinterpret_cast<const u2*>(a.ct[t] + ((size_t(b) * NCOMP + k) * a.in_limbs[t] + i) * n + chunk);
+#pragma unroll
+            for (u32 j = 0; j < PT_VECS; ++j) c[slot][t][j] = src[threadIdx.x + j * PT_THREADS];
+        }
+    };
+    if constexpr (ALL) {
+#pragma unroll
+        for (int k = 0; k < NCOMP; ++k) load(k, k);
+    }
+#pragma unroll
+    for (int k = 0; k < NCOMP; ++k) {
+        if constexpr (!ALL) load(k, 0);
+        double acc[PT_VECS][2];
+#pragma unroll
+        for (u32 j = 0; j < PT_VECS; ++j) acc[j][0] = acc[j][1] = 0.0;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const LcWeight wt = a.wt[i][t];
+            const bool one = wt.w == 1.0;                        // the same in every lane: a scalar branch, not a select
+#pragma unroll
+            for (u32 j = 0; j < PT_VECS; ++j) {
+                const u2 v = c[ALL ? k : 0][t][j];
+                double x = hxf::to_f64(v.x), y = hxf::to_f64(v.y);
+                if (!one) {
+                    x = hxf::lc_term(x, wt.w, wt.wp, m);
+                    y = hxf::lc_term(y, wt.w, wt.wp, m);
+                }
+                acc[j][0] = hxf::lc_add(acc[j][0], x, m);
+                acc[j][1] = hxf::lc_add(acc[j][1], y, m);
+            }
+        }
+        if (k == 0) {
+            if (has_pt) {
+#pragma unroll
+                for (u32 j = 0; j < PT_VECS; ++j) {
+                    acc[j][0] = hxf::lc_add(acc[j][0], hxf::to_f64(p[j].x), m);
+                    acc[j][1] = hxf::lc_add(acc[j][1], hxf::to_f64(p[j].y), m);
+                }
+            }
+            if (a.has_cst) {
+                const double cst = a.cst[i];
+#pragma unroll
+                for (u32 j = 0; j < PT_VECS; ++j) {
+                    acc[j][0] = hxf::lc_add(acc[j][0], cst, m);
+                    acc[j][1] = hxf::lc_add(acc[j][1], cst, m);
+                }
+            }
+        }
+        u2* dst = reinterpret_cast<u2*>(a.out + ((size_t(b) * NCOMP + k) * a.L + i) * n + chunk);
+#pragma unroll
+        for (u32 j = 0; j < PT_VECS; ++j) {
+            u2 o;
+            o.x = hxf::from_f64(hxf::lc_finish(acc[j][0], m));
+            o.y = hxf::from_f64(hxf::lc_finish(acc[j][1], m));
+            dst[threadIdx.x + j * PT_THREADS] = o;
+        }
+    }
+}
+
+static int hx_launch_ct_lincomb(hexl_ks_plan* p, const LcArgs& a, size_t batch, u32 n_terms, u32 n_components) {
+    if (!batch) return 0;
+    const dim3 grid((u32)pt_mul_grid(p, batch, a.L)), block(PT_THREADS);
+    auto comps = [&](auto NT) {
+        constexpr int T = decltype(NT)::value;
+        if (n_components == 1) hipLaunchKernelGGL((k_ct_lincomb<T, 1>), grid, block, 0, p->ctx->stream, a);
+        else if (n_components == 2) hipLaunchKernelGGL((k_ct_lincomb<T, 2>), grid, block, 0, p->ctx->stream, a);
+        else hipLaunchKernelGGL((k_ct_lincomb<T, 3>), grid, block, 0, p->ctx->stream, a);
+    };
+    switch (n_terms) {
+        case 1: comps(hx_int<1>{}); break;
+        case 2: comps(hx_int<2>{}); break;
+        case 3: comps(hx_int<3>{}); break;
+        case 4: comps(hx_int<4>{}); break;
+        case 5: comps(hx_int<5>{}); break;
+        case 6: comps(hx_int<6>{}); break;
+        case 7: comps(hx_int<7>{}); break;
+        default: comps(hx_int<8>{}); break;
+    }
+    return (int)hipGetLastError();
+}
+
 // ---- entry points of include/hexl_mi355x.h (beside their launchers, as in ckks_ops.hip: the CPU staging model needs no stubs for them) ----
 // FP64 plan of a ring dimension the transforms are built for, 1 <= n_limbs <= K (the special prime included)
 static bool rns_plan_ok(const hexl_ks_plan* p, u64 n_limbs) {
@@ -205,4 +331,49 @@ extern "C" int hexl_multiply_plain(hexl_ks_plan* p, uint64_t* d_out, const uint6
     HX_CHECK(hipSetDevice(p->ctx->device));
     return hx_launch_multiply_plain(p, d_out, d_ct, d_pt, batch, (u32)n_components, (u32)n_limbs, pt_batch == batch,
                                     accumulate != 0);
+}
+
+extern "C" int hexl_ct_lincomb(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* const* d_cts, const uint64_t* in_limbs,
+                               const uint64_t* h_weights, size_t n_terms, const uint64_t* d_pt, size_t pt_batch, const uint64_t* h_const,
+                               size_t batch, uint64_t n_components, uint64_t n_limbs) {
+    if (!d_out || !d_cts || n_terms < 1 || n_terms > LC_MAX_TERMS || !rns_plan_ok(p, n_limbs) || n_limbs > LC_MAX_LIMBS) return HEXL_E_BADARG;
+    if (n_components < 1 || n_components > 3) return HEXL_E_BADARG;
+    if (d_pt && pt_batch != 1 && pt_batch != batch) return HEXL_E_BADARG;
+    const size_t poly = size_t(p->n) * sizeof(u64), pt_per = size_t(n_limbs) * poly;
+    // the largest term has K limbs: if that size fits, every other one does
+    if (batch > SIZE_MAX / (size_t(p->K) * poly * n_components) || batch > RNS_MAX_GRID / (n_limbs * (p->n >> PT_LOG_CHUNK))) return HEXL_E_BADARG;
+    const size_t bytes = batch * n_components * pt_per;
+    LcArgs a{};
+    for (size_t t = 0; t < n_terms; ++t) {
+        const u64 lt = in_limbs ? in_limbs[t] : n_limbs;
+        if (!d_cts[t] || lt < n_limbs || lt > p->K) return HEXL_E_BADARG;
+        // in place over a term of the output's own layout, or apart
+        if ((d_out != d_cts[t] || lt != n_limbs) && hx_ranges_overlap(d_out, bytes, d_cts[t], batch * n_components * size_t(lt) * poly))
+            return HEXL_E_BADARG;
+        a.ct[t] = d_cts[t];
+        a.in_limbs[t] = (u32)lt;
+    }
+    if (d_pt && hx_ranges_overlap(d_out, bytes, d_pt, (batch ? pt_batch : 0) * pt_per)) return HEXL_E_BADARG;
+    for (u64 i = 0; i < n_limbs; ++i) {
+        const u64 q = p->moduli[i];
+        for (size_t t = 0; t < n_terms; ++t) {
+            const u64 w = h_weights ? h_weights[t * n_limbs + i] : 1;
+            if (w >= q) return HEXL_E_BADARG;
+            const double wc = hx_centre(w, q);
+            a.wt[i][t] = LcWeight{wc, wc / (double)q};
+        }
+        if (h_const) {
+            if (h_const[i] >= q) return HEXL_E_BADARG;
+            a.cst[i] = hx_centre(h_const[i], q);
+        }
+    }
+    a.mods = p->d_mods_f64;
+    a.pt = d_pt;
+    a.out = d_out;
+    a.logn = p->logn;
+    a.L = (u32)n_limbs;
+    a.pt_stride = d_pt && pt_batch == batch ? 1u : 0u;
+    a.has_cst = h_const ? 1u : 0u;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    return hx_launch_ct_lincomb(p, a, batch, (u32)n_terms, (u32)n_components);
 }

@@ -283,6 +283,34 @@ int hexl_rns_ntt_inv(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_in, 
  * with accumulate != 0 among them), another pt_batch or a size that overflows: HEXL_E_BADARG. */
 int hexl_multiply_plain(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_ct, const uint64_t* d_pt, size_t batch,
                         uint64_t n_components, uint64_t n_limbs, size_t pt_batch, int accumulate);
+/* Weighted sum of up to eight ciphertexts, limb by limb, everything in NTT form: ct + ct, ct - ct, -ct, ct . constant, ct + plaintext,
+ * ct + constant and the CKKS level drop are all this one call with special weights. For b < batch, k < n_components, i < n_limbs, j < n
+ *   out[b][k][i][j] = ( sum_t w[t][i] . ct_t[b][k][i][j]  +  [k == 0] . (pt[b or 0][i][j] + const[i]) ) mod q_i, canonical.
+ *   d_cts       HOST array of n_terms DEVICE pointers, 1 <= n_terms <= 8; term t is [batch][n_components][in_limbs[t]][n], every word
+ *               below its modulus
+ *   in_limbs    HOST [n_terms], n_limbs <= in_limbs[t] <= K, or NULL: every term has n_limbs. A term with more limbs than the output is
+ *               read through its first n_limbs limbs only -- the CKKS level drop: the last moduli of the plan's chain are discarded, as
+ *               hexl_rescale and hexl_rns_ntt_* do when they use "the plan's first n_limbs"
+ *   h_weights   HOST [n_terms][n_limbs] residues, each below q_i, or NULL: every weight is 1. 1 adds the term, q_i - 1 subtracts it,
+ *               rint(a . scale) mod q_i multiplies it by a scaled constant
+ *   d_pt        NULL, or a DEVICE plaintext [pt_batch][n_limbs][n], words below q_i, added to component 0 only; pt_batch = 1 or batch as
+ *               for hexl_multiply_plain, ignored when d_pt is NULL
+ *   h_const     NULL, or HOST [n_limbs] residues below q_i, added to every word of component 0 (in NTT form a constant polynomial is the
+ *               same word at every index)
+ *   d_out       [batch][n_components][n_limbs][n], WRITTEN
+ * 1 <= n_components <= 3, 1 <= n_limbs <= K; FP64 plans only, n = 1024 ... 32768, no keys needed, as hexl_multiply_plain. Every term is
+ * read once and the output written once: n_terms + 1 passes over memory.
+ * Overlap: d_out may be exactly d_cts[t] for terms with in_limbs[t] == n_limbs (a lane reads only the words it writes: in place, and
+ * accumulation with d_out among the terms); terms may overlap each other and d_pt. Any other overlap of d_out with a term or with d_pt:
+ * HEXL_E_BADARG.
+ * HEXL_E_BADARG as well: a null plan, d_out, d_cts or d_cts[t] (batch == 0 does not excuse it), n_terms outside 1 ... 8, an in_limbs[t]
+ * outside its range, a weight or a constant that is not below its modulus, another pt_batch, a plan on the integer kernels, a size or
+ * a grid that overflows. batch == 0 returns 0 after these checks.
+ * Asynchronous on the context's stream. Pointers, limb counts, weights and the constant travel in the kernel's arguments: every host
+ * array may be reused as soon as the call returns, and the call allocates and keeps no device memory. */
+int hexl_ct_lincomb(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* const* d_cts, const uint64_t* in_limbs,
+                    const uint64_t* h_weights, size_t n_terms, const uint64_t* d_pt, size_t pt_batch,
+                    const uint64_t* h_const, size_t batch, uint64_t n_components, uint64_t n_limbs);
 /* Encode and decode on the device: the canonical embedding and the change between real coefficients and RNS limbs, so that weights and
  * results can cross the bus as slot vectors (n/2 complex doubles) instead of [n_limbs][n] words. All four are asynchronous on the
  * context's stream and need no keys. FP64 plans only (every modulus < 2^52), n = 1024 ... 32768, 1 <= n_limbs <= K: the moduli are the
