@@ -68,6 +68,9 @@ C_ABI = {
     "hexl_rns_to_f64": [_vp, _vp, _vp, _sz, _u64],
     "hexl_ckks_encode": [_vp, _vp, _vp, _sz, _u64, ctypes.c_double],
     "hexl_ckks_decode": [_vp, _vp, _vp, _sz, _u64, ctypes.c_double],
+    "hexl_sample": [_vp, _vp, _i, _vp, _u64, _u64, _sz, _u64],
+    "hexl_rlwe_encrypt": [_vp, _vp, _vp, _sz, _vp, _vp, _u64, _u64, _sz, _u64],
+    "hexl_rlwe_decrypt": [_vp, _vp, _vp, _vp, _sz, _u64, _u64],
     "hexl_ks_scratch_bytes": [_vp, _sz],
     "hexl_ntt_fwd_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64],
     "hexl_ntt_inv_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64, _u64, _u64],
@@ -111,6 +114,21 @@ def lib() -> ctypes.CDLL:
             fn.argtypes = args
             fn.restype = _sz if name in ("hexl_ks_scratch_bytes", "hexl_lt_bsgs_scratch_bytes") else _i
     return _lib
+
+
+SAMPLE_UNIFORM, SAMPLE_TERNARY, SAMPLE_CBD21 = 1, 2, 3            # include/hexl_mi355x.h HEXL_SAMPLE_*
+
+
+def seed_words(seed=None):
+    """the 32-byte seed of hexl_sample / hexl_rlwe_encrypt as (ctypes uint32[8], the bytes): `seed` is 32 bytes, eight u32 words, or
+    None for 32 fresh bytes from os.urandom -- keep the returned bytes if the stream has to be expanded again"""
+    if seed is None:
+        seed = os.urandom(32)
+    if not isinstance(seed, (bytes, bytearray)):
+        seed = np.asarray(seed, dtype="<u4").tobytes()
+    if len(seed) != 32:
+        raise ValueError("a seed is 32 bytes (eight little-endian u32 words)")
+    return (ctypes.c_uint32 * 8)(*np.frombuffer(bytes(seed), dtype="<u4").tolist()), bytes(seed)
 
 
 def _check(rc: int, what: str):
@@ -296,6 +314,28 @@ class KeySwitchPlan:
         """slots[count][n/2][2] = the slot values of the plaintext inp[count][n_limbs][n] divided by `scale`"""
         _check(lib().hexl_ckks_decode(self.h, _ptr(slots), _ptr(inp), count, n_limbs, scale), "hexl_ckks_decode")
 
+    def sample(self, out, kind: int, count: int, n_limbs: int, seed=None, stream: int = 0, first: int = 0) -> bytes:
+        """out[count][n_limbs][n] = polynomials first ... first + count - 1 of the ChaCha20 stream (seed, stream, kind) modulo the plan's
+        first n_limbs moduli, NTT form: SAMPLE_UNIFORM, SAMPLE_TERNARY (secrets) or SAMPLE_CBD21 (errors). seed: 32 bytes / eight u32,
+        None = os.urandom(32); returns the seed's bytes. Never use (seed, stream, index) twice with one secret."""
+        words, raw = seed_words(seed)
+        _check(lib().hexl_sample(self.h, _ptr(out), kind, words, stream, first, count, n_limbs), "hexl_sample")
+        return raw
+
+    def rlwe_encrypt(self, out, secret, count: int, n_limbs: int, pt=None, pt_batch: int = 1, seed=None, stream: int = 0,
+                     first: int = 0) -> bytes:
+        """out[count][2][n_limbs][n] = (pt + e - a secret, a) with a = the UNIFORM and e = the CBD21 polynomial first + b of (seed,
+        stream); pt None (an encryption of zero) or [pt_batch][n_limbs][n], pt_batch = 1 or count; secret [>= n_limbs][n] in NTT form.
+        count = L, n_limbs = K, pt_batch = count: out is the h_keys layout of set_keys. Returns the seed's bytes (None = os.urandom)."""
+        words, raw = seed_words(seed)
+        _check(lib().hexl_rlwe_encrypt(self.h, _ptr(out), None if pt is None else _ptr(pt), pt_batch, _ptr(secret), words, stream, first,
+                                       count, n_limbs), "hexl_rlwe_encrypt")
+        return raw
+
+    def rlwe_decrypt(self, out, ct, secret, count: int, n_components: int, n_limbs: int):
+        """out[count][n_limbs][n] = c0 + c1 secret (+ c2 secret^2 when n_components = 3) of ct[count][n_components][n_limbs][n]"""
+        _check(lib().hexl_rlwe_decrypt(self.h, _ptr(out), _ptr(ct), _ptr(secret), count, n_components, n_limbs), "hexl_rlwe_decrypt")
+
     def keyswitch_host(self, results, t_targets):
         n = len(results)
         r = (_vp * n)(*[_ptr(a) for a in results])
@@ -382,5 +422,5 @@ def lt_bsgs_scratch_bytes(plan, n_baby: int, batch: int) -> int:
 from .host_api import HexlFpga  # noqa: E402  (mirror of host/inc/hexl-fpga.h)
 
 __all__ = ["Context", "KeySwitchPlan", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform",
-           "linear_transform_bsgs", "lt_bsgs_scratch_bytes", "C_ABI",
+           "linear_transform_bsgs", "lt_bsgs_scratch_bytes", "C_ABI", "SAMPLE_UNIFORM", "SAMPLE_TERNARY", "SAMPLE_CBD21", "seed_words",
            "LIB_PATH", "ROOT"]

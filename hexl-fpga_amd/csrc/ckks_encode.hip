@@ -35,8 +35,8 @@ __device__ __forceinline__ cplx root(const double2* roots, u32 t) {
 constexpr u32 EMB_MAX_LOGB = 13;            // complex points one workgroup holds in LDS: 8192 x 16 bytes = 128 KiB of the CU's 160
 constexpr u32 EMB_MAX_THREADS = 1024;
 constexpr u32 EMB_TOP_THREADS = 256;
-// instances per scratch chunk: 256 at n = 16384 and the same number of coefficients at every other n
-static size_t emb_chunk(const hexl_ks_plan* p) { return (size_t(256) << 14) >> p->logn; }
+// instances per scratch chunk (hexl_internal.hpp: rlwe.hip fills the same scratch under the same rule)
+static size_t emb_chunk(const hexl_ks_plan* p) { return hx_enc_chunk(p); }
 
 struct EmbArgs {
     const double2* roots;       // [2n]

@@ -193,9 +193,10 @@ struct hexl_ks_plan {
     double* d_emb_roots = nullptr;    // [2n][2]: zeta^t = exp(i pi t / n) as (re, im), computed in long double and rounded once
     u32* d_emb_perm = nullptr;        // [n/2]: slot k held by position p of the embedding FFT's bit-reversed side (5^k = 4 bitrev(p) + 1 mod 2n)
     double* d_garner = nullptr;       // [16][16][2]: row i, column j < i = (q_j^-1 mod q_i centred, fl(./q_i)): Garner's constants for every prefix
-    double* d_enc_coeffs = nullptr;   // real coefficients of enc_coeffs_cap instances, n doubles each (grow-only)
+    double* d_enc_coeffs = nullptr;   // real coefficients of enc_coeffs_cap instances, n doubles each (grow-only; rlwe.hip: the small samples)
     size_t enc_coeffs_cap = 0;
-    u64* d_enc_words = nullptr;       // coefficient-form limbs of enc_words_cap (instance, limb) polynomials, n words each (grow-only)
+    u64* d_enc_words = nullptr;       // coefficient-form limbs of enc_words_cap (instance, limb) polynomials, n words each (grow-only; rlwe.hip:
+                                      // NTT_i of an encryption's error)
     size_t enc_words_cap = 0;
 };
 
@@ -261,6 +262,14 @@ int hx_launch_multiply_plain(hexl_ks_plan*, u64* d_out, const u64* d_ct, const u
 // hexl_ckks_encode, hexl_ckks_decode). d_slots = nullptr: the real coefficients themselves are the caller's (d_coeffs).
 int hx_launch_encode(hexl_ks_plan*, u64* d_out, const double* d_coeffs, const double* d_slots, size_t count, u32 n_limbs, double scale);
 int hx_launch_decode(hexl_ks_plan*, double* d_coeffs, double* d_slots, const u64* d_in, size_t count, u32 n_limbs, double scale);
+// instances per chunk of the encode scratch (d_enc_coeffs, d_enc_words): 256 at n = 16384 and the same number of coefficients at every other n
+inline size_t hx_enc_chunk(const hexl_ks_plan* p) { return (size_t(256) << 14) >> p->logn; }
+// the sampler, symmetric encryption and decryption (rlwe.hip); arguments checked by their entry points (hexl_sample, hexl_rlwe_encrypt,
+// hexl_rlwe_decrypt). The small kinds and the error of an encryption pass through d_enc_coeffs / d_enc_words in chunks of hx_enc_chunk.
+int hx_launch_sample(hexl_ks_plan*, u64* d_out, int kind, const u32* seed, u64 stream, u64 first, size_t count, u32 n_limbs);
+int hx_launch_rlwe_encrypt(hexl_ks_plan*, u64* d_out, const u64* d_pt, bool per_instance, const u64* d_secret, const u32* seed, u64 stream,
+                           u64 first, size_t count, u32 n_limbs);
+int hx_launch_rlwe_decrypt(hexl_ks_plan*, u64* d_out, const u64* d_ct, const u64* d_secret, size_t count, u32 n_components, u32 n_limbs);
 u32 hx_ks_x_loge();
 // index of coefficient held in register r of thread tid after a forward transform ("B layout")
 u32 hx_idxB(u32 logn, u32 r, u32 tid);

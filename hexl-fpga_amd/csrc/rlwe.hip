@@ -1,0 +1,259 @@
+// rlwe.hip -- the sampler on the device and the two ends of a flow that need it (DESIGN.md 4.6.6 "Sampling, encrypt and decrypt"):
+//   sample         out[c][i] = polynomial `first + c` of the stream (seed, stream, kind) modulo q_i, NTT form
+//                  UNIFORM: the words themselves (uniform words are uniform in either domain)            k_sample_uniform
+//                  TERNARY / CBD21: one integer polynomial, NTT_i(v mod q_i) in every limb               k_sample_small + k_rns_from_f64
+//   rlwe_encrypt   out[b] = (pt + e - a s, a), a = UNIFORM and e = CBD21 of polynomial `first + b`       k_sample_small + k_rns_from_f64
+//                                                                                                          + k_rlwe_encrypt
+//   rlwe_decrypt   out[b] = c0 + c1 s (+ c2 s^2), Horner                                                  k_rlwe_decrypt
+// The streams are ChaCha20 in counter mode, addressed per word (sample_core.hpp): a result depends on (seed, stream, absolute
+// polynomial index, limb, coefficient) only. The three word kernels have k_pt_mul's shape (rns_ops.hip): one workgroup per (instance,
+// limb, 1024-word chunk), 256 lanes, the modulus found once per workgroup; a lane owns FOUR CONSECUTIVE words -- 32 contiguous bytes,
+// and exactly one UNIFORM block of 64 stream bytes, none of it wasted. FP64 plans only (moduli < 2^52). The small kinds and the error
+// of an encryption go through the plan's encode scratch (ckks_encode.hip: d_enc_coeffs, d_enc_words) under encode's chunk rule.
+#include "hexl_internal.hpp"
+#include "sample_core.hpp"
+
+using hxf::Mod;
+
+constexpr u32 RL_THREADS = 256, RL_LOG_CHUNK = 10;      // 1024 words of one polynomial per workgroup, four per lane
+static_assert(RL_THREADS * 4 == 1u << RL_LOG_CHUNK, "a workgroup covers its chunk exactly");
+typedef unsigned long long rl_u2 __attribute__((ext_vector_type(2)));
+
+struct SampleArgs {
+    const KsModF64* mods;       // [K]
+    u64* out;                   // uniform: [count][L][n]
+    double* coeffs;             // small: [count][n] (plan scratch)
+    hxs::Seed seed;             // by value: nothing of the caller's is read after the call returns
+    u64 stream, first;          // absolute index of instance 0 of this launch
+    u32 logn, L;
+    u32 count;                  // small: instances of this launch
+    int kind;
+};
+
+// the (instance, limb, chunk) of a workgroup and the offset of its chunk inside the polynomial
+struct RlWhere { u32 b, i, j0; };
+__device__ __forceinline__ RlWhere rl_where(u32 logn, u32 L) {
+    const u32 bi = blockIdx.x >> (logn - RL_LOG_CHUNK), ch = blockIdx.x - (bi << (logn - RL_LOG_CHUNK));
+    const u32 b = bi / L;
+    return {b, bi - b * L, (ch << RL_LOG_CHUNK) + 4 * threadIdx.x};
+}
+// the four UNIFORM words j0 ... j0 + 3 (j0 a multiple of 4: one block) of polynomial (c, limb i), canonical, as doubles
+__device__ __forceinline__ void rl_uniform4(double a[4], const hxs::Seed& seed, u64 stream, u64 c, u32 i, u32 logn, u32 j0, const Mod m) {
+    const hxs::Block blk = hxs::chacha20_block(seed, hxs::counter(hxs::KIND_UNIFORM, hxs::uniform_block(c, i, logn, j0)), stream);
+    const double c32 = hxs::mod_c32(m);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[k] = hxs::uniform_word(blk, k, c32, m);
+}
+__device__ __forceinline__ void rl_store4(u64* dst, const double v[4]) {
+    rl_u2 lo, hi;
+    lo.x = hxf::from_f64(v[0]); lo.y = hxf::from_f64(v[1]);
+    hi.x = hxf::from_f64(v[2]); hi.y = hxf::from_f64(v[3]);
+    reinterpret_cast<rl_u2*>(dst)[0] = lo;
+    reinterpret_cast<rl_u2*>(dst)[1] = hi;
+}
+__device__ __forceinline__ void rl_load4(double v[4], const u64* src) {
+    const rl_u2 lo = reinterpret_cast<const rl_u2*>(src)[0], hi = reinterpret_cast<const rl_u2*>(src)[1];
+    v[0] = hxf::to_f64(lo.x); v[1] = hxf::to_f64(lo.y);
+    v[2] = hxf::to_f64(hi.x); v[3] = hxf::to_f64(hi.y);
+}
+
+__global__ __launch_bounds__(RL_THREADS) void k_sample_uniform(SampleArgs a) {
+    const RlWhere w = rl_where(a.logn, a.L);
+    const Mod m = a.mods[w.i].m;
+    double v[4];
+    rl_uniform4(v, a.seed, a.stream, a.first + w.b, w.i, a.logn, w.j0, m);
+    rl_store4(a.out + ((size_t(w.b) * a.L + w.i) << a.logn) + w.j0, v);
+}
+
+// One block -- eight coefficients, 64 contiguous bytes of doubles -- per lane: lane g of the launch holds coefficients 8 (g mod n/8) ...
+// of instance g / (n/8). The doubles are what hexl_rns_from_f64 takes: k_rns_from_f64 turns them into NTT_i(v mod q_i) for every limb.
+__global__ __launch_bounds__(RL_THREADS) void k_sample_small(SampleArgs a) {
+    const size_t g = size_t(blockIdx.x) * RL_THREADS + threadIdx.x;
+    if (g >= size_t(a.count) << (a.logn - 3)) return;         // an odd count at n = 1024 ends in half a workgroup
+    const u32 b = (u32)(g >> (a.logn - 3)), j0 = (u32)(g - (size_t(b) << (a.logn - 3))) << 3;
+    const hxs::Block blk = hxs::chacha20_block(a.seed, hxs::counter(a.kind, hxs::small_block(a.first + b, a.logn, j0)), a.stream);
+    double2* dst = reinterpret_cast<double2*>(a.coeffs + (size_t(b) << a.logn) + j0);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        dst[t] = double2{(double)hxs::small_value(a.kind, hxs::lane(blk, 2 * t)), (double)hxs::small_value(a.kind, hxs::lane(blk, 2 * t + 1))};
+}
+
+struct EncryptArgs {
+    const KsModF64* mods;       // [K]
+    u64* out;                   // [nb][2][L][n]
+    const u64* e;               // [nb][L][n]: NTT_i of the error (plan scratch)
+    const u64* pt;              // nullptr, or [pt_stride ? nb : 1][L][n]
+    const u64* s;               // [>= L][n]
+    hxs::Seed seed;
+    u64 stream, first;
+    u32 logn, L, pt_stride;
+};
+
+// E, pt and s are requested before the block function runs (some 300 32-bit operations that hide their latency); `a` never leaves the
+// registers until it is stored as component 1: one read of E / pt / s and one write of the ciphertext.
+__global__ __launch_bounds__(RL_THREADS) void k_rlwe_encrypt(EncryptArgs a) {
+    const RlWhere w = rl_where(a.logn, a.L);
+    const Mod m = a.mods[w.i].m;
+    const size_t within = (size_t(w.i) << a.logn) + w.j0, per = size_t(a.L) << a.logn;
+    double e[4], s[4], p[4] = {0.0, 0.0, 0.0, 0.0}, u[4], c0[4];
+    rl_load4(e, a.e + size_t(w.b) * per + within);
+    rl_load4(s, a.s + within);
+    if (a.pt) rl_load4(p, a.pt + size_t(w.b) * a.pt_stride * per + within);
+    rl_uniform4(u, a.seed, a.stream, a.first + w.b, w.i, a.logn, w.j0, m);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c0[k] = hxs::encrypt_c0(u[k], s[k], e[k], p[k], m);
+    u64* dst = a.out + size_t(w.b) * 2 * per + within;
+    rl_store4(dst, c0);
+    rl_store4(dst + per, u);
+}
+
+struct DecryptArgs {
+    const KsModF64* mods;       // [K]
+    u64* out;                   // [count][L][n]
+    const u64* ct;              // [count][NCOMP][L][n]
+    const u64* s;               // [>= L][n]
+    u32 logn, L;
+};
+
+// every component is loaded before the first product; Horner from the top component
+template <int NCOMP>
+__global__ __launch_bounds__(RL_THREADS) void k_rlwe_decrypt(DecryptArgs a) {
+    const RlWhere w = rl_where(a.logn, a.L);
+    const Mod m = a.mods[w.i].m;
+    const size_t within = (size_t(w.i) << a.logn) + w.j0, per = size_t(a.L) << a.logn;
+    double c[NCOMP][4], s[4], r[4];
+#pragma unroll
+    for (int k = 0; k < NCOMP; ++k) rl_load4(c[k], a.ct + (size_t(w.b) * NCOMP + k) * per + within);
+    rl_load4(s, a.s + within);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const double sr = hxf::reduce(s[t], m);
+        double acc = hxf::reduce(c[NCOMP - 1][t], m);
+#pragma unroll
+        for (int k = NCOMP - 2; k >= 0; --k) acc = hxs::horner(acc, sr, c[k][t], m);
+        r[t] = hxf::lc_finish(acc, m);
+    }
+    rl_store4(a.out + size_t(w.b) * per + within, r);
+}
+
+// ---- launchers ----
+static dim3 rl_grid(const hexl_ks_plan* p, size_t count, u32 n_limbs) { return dim3((u32)(count * n_limbs * (p->n >> RL_LOG_CHUNK))); }
+
+// the small values of instances first ... first + nb - 1 into the plan's d_enc_coeffs (grown by the caller), as doubles
+static int launch_small(hexl_ks_plan* p, int kind, const hxs::Seed& seed, u64 stream, u64 first, size_t nb) {
+    SampleArgs a{};
+    a.coeffs = p->d_enc_coeffs;
+    a.seed = seed;
+    a.stream = stream;
+    a.first = first;
+    a.logn = p->logn;
+    a.count = (u32)nb;
+    a.kind = kind;
+    hipLaunchKernelGGL(k_sample_small, dim3((u32)(((nb << (p->logn - 3)) + RL_THREADS - 1) / RL_THREADS)), dim3(RL_THREADS), 0, p->ctx->stream, a);
+    return (int)hipGetLastError();
+}
+
+int hx_launch_sample(hexl_ks_plan* p, u64* d_out, int kind, const u32* seed, u64 stream, u64 first, size_t count, u32 n_limbs) {
+    if (!count) return 0;
+    hxs::Seed sd;
+    for (int k = 0; k < 8; ++k) sd.k[k] = seed[k];
+    if (kind == hxs::KIND_UNIFORM) {
+        SampleArgs a{};
+        a.mods = p->d_mods_f64;
+        a.out = d_out;
+        a.seed = sd;
+        a.stream = stream;
+        a.first = first;
+        a.logn = p->logn;
+        a.L = n_limbs;
+        a.kind = kind;
+        hipLaunchKernelGGL(k_sample_uniform, rl_grid(p, count, n_limbs), dim3(RL_THREADS), 0, p->ctx->stream, a);
+        return (int)hipGetLastError();
+    }
+    const size_t n = p->n, chunk = count < hx_enc_chunk(p) ? count : hx_enc_chunk(p);
+    if (int rc = hx_grow_device((void**)&p->d_enc_coeffs, &p->enc_coeffs_cap, chunk, n * sizeof(double), nullptr)) return rc;
+    for (size_t c0 = 0; c0 < count; c0 += chunk) {
+        const size_t nb = count - c0 < chunk ? count - c0 : chunk;
+        if (int rc = launch_small(p, kind, sd, stream, first + c0, nb)) return rc;
+        if (int rc = hx_launch_encode(p, d_out + c0 * n_limbs * n, p->d_enc_coeffs, nullptr, nb, n_limbs, 1.0)) return rc;
+    }
+    return 0;
+}
+
+int hx_launch_rlwe_encrypt(hexl_ks_plan* p, u64* d_out, const u64* d_pt, bool per_instance, const u64* d_secret, const u32* seed,
+                           u64 stream, u64 first, size_t count, u32 n_limbs) {
+    if (!count) return 0;
+    const size_t n = p->n, chunk = count < hx_enc_chunk(p) ? count : hx_enc_chunk(p), per = size_t(n_limbs) * n;
+    if (int rc = hx_grow_device((void**)&p->d_enc_coeffs, &p->enc_coeffs_cap, chunk, n * sizeof(double), nullptr)) return rc;
+    if (int rc = hx_grow_device((void**)&p->d_enc_words, &p->enc_words_cap, chunk * n_limbs, n * sizeof(u64), nullptr)) return rc;
+    EncryptArgs a{};
+    a.mods = p->d_mods_f64;
+    a.e = p->d_enc_words;
+    a.s = d_secret;
+    for (int k = 0; k < 8; ++k) a.seed.k[k] = seed[k];
+    a.stream = stream;
+    a.logn = p->logn;
+    a.L = n_limbs;
+    a.pt_stride = per_instance ? 1u : 0u;
+    for (size_t c0 = 0; c0 < count; c0 += chunk) {
+        const size_t nb = count - c0 < chunk ? count - c0 : chunk;
+        if (int rc = launch_small(p, hxs::KIND_CBD21, a.seed, stream, first + c0, nb)) return rc;
+        if (int rc = hx_launch_encode(p, p->d_enc_words, p->d_enc_coeffs, nullptr, nb, n_limbs, 1.0)) return rc;
+        a.out = d_out + c0 * 2 * per;
+        a.pt = d_pt ? d_pt + (per_instance ? c0 * per : 0) : nullptr;
+        a.first = first + c0;
+        hipLaunchKernelGGL(k_rlwe_encrypt, rl_grid(p, nb, n_limbs), dim3(RL_THREADS), 0, p->ctx->stream, a);
+        if (int rc = (int)hipGetLastError()) return rc;
+    }
+    return 0;
+}
+
+int hx_launch_rlwe_decrypt(hexl_ks_plan* p, u64* d_out, const u64* d_ct, const u64* d_secret, size_t count, u32 n_components, u32 n_limbs) {
+    if (!count) return 0;
+    const DecryptArgs a{p->d_mods_f64, d_out, d_ct, d_secret, p->logn, n_limbs};
+    const dim3 grid = rl_grid(p, count, n_limbs), block(RL_THREADS);
+    if (n_components == 2) hipLaunchKernelGGL(k_rlwe_decrypt<2>, grid, block, 0, p->ctx->stream, a);
+    else hipLaunchKernelGGL(k_rlwe_decrypt<3>, grid, block, 0, p->ctx->stream, a);
+    return (int)hipGetLastError();
+}
+
+// ---- entry points of include/hexl_mi355x.h ----
+constexpr size_t RL_MAX_GRID = 0x7fffffffu;      // workgroups of one launch (x dimension)
+// FP64 plan of a ring dimension the transforms are built for, 1 <= n_limbs <= K, and `count` instances of `comps` components whose
+// bytes and workgroups fit
+static bool rl_plan_ok(const hexl_ks_plan* p, size_t count, u64 comps, u64 n_limbs) {
+    if (!p || !p->use_f64 || p->logn < 10 || p->logn > 15 || n_limbs < 1 || n_limbs > p->K) return false;
+    const size_t per = size_t(n_limbs) * p->n * sizeof(u64) * comps;
+    return count <= SIZE_MAX / per && count <= RL_MAX_GRID / (n_limbs * (p->n >> RL_LOG_CHUNK));
+}
+static bool rl_index_ok(u64 first, size_t count) { return first <= hxs::MAX_INDEX && count <= hxs::MAX_INDEX - first; }
+
+extern "C" int hexl_sample(hexl_ks_plan* p, uint64_t* d_out, int kind, const uint32_t seed[8], uint64_t stream, uint64_t first,
+                           size_t count, uint64_t n_limbs) {
+    if (!d_out || !seed || !rl_plan_ok(p, count, 1, n_limbs) || !rl_index_ok(first, count)) return HEXL_E_BADARG;
+    if (kind != HEXL_SAMPLE_UNIFORM && kind != HEXL_SAMPLE_TERNARY && kind != HEXL_SAMPLE_CBD21) return HEXL_E_BADARG;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    return hx_launch_sample(p, d_out, kind, seed, stream, first, count, (u32)n_limbs);
+}
+
+extern "C" int hexl_rlwe_encrypt(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_pt, size_t pt_batch, const uint64_t* d_secret,
+                                 const uint32_t seed[8], uint64_t stream, uint64_t first, size_t count, uint64_t n_limbs) {
+    if (!d_out || !d_secret || !seed || !rl_plan_ok(p, count, 2, n_limbs) || !rl_index_ok(first, count)) return HEXL_E_BADARG;
+    if (d_pt && pt_batch != 1 && pt_batch != count) return HEXL_E_BADARG;
+    const size_t per = size_t(n_limbs) * p->n * sizeof(u64), bytes = count * 2 * per;
+    if (hx_ranges_overlap(d_out, bytes, d_secret, per)) return HEXL_E_BADARG;
+    if (d_pt && hx_ranges_overlap(d_out, bytes, d_pt, (count ? pt_batch : 0) * per)) return HEXL_E_BADARG;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    return hx_launch_rlwe_encrypt(p, d_out, d_pt, d_pt && pt_batch == count, d_secret, seed, stream, first, count, (u32)n_limbs);
+}
+
+extern "C" int hexl_rlwe_decrypt(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_ct, const uint64_t* d_secret, size_t count,
+                                 uint64_t n_components, uint64_t n_limbs) {
+    if (!d_out || !d_ct || !d_secret || (n_components != 2 && n_components != 3)) return HEXL_E_BADARG;
+    if (!rl_plan_ok(p, count, n_components, n_limbs)) return HEXL_E_BADARG;
+    const size_t per = size_t(n_limbs) * p->n * sizeof(u64);
+    if (hx_ranges_overlap(d_out, count * per, d_ct, count * n_components * per) || hx_ranges_overlap(d_out, count * per, d_secret, per))
+        return HEXL_E_BADARG;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    return hx_launch_rlwe_decrypt(p, d_out, d_ct, d_secret, count, (u32)n_components, (u32)n_limbs);
+}

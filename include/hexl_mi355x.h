@@ -342,6 +342,69 @@ int hexl_rns_from_f64(hexl_ks_plan* plan, uint64_t* d_out, const double* d_coeff
 int hexl_rns_to_f64(hexl_ks_plan* plan, double* d_coeffs, const uint64_t* d_in, size_t count, uint64_t n_limbs);
 int hexl_ckks_encode(hexl_ks_plan* plan, uint64_t* d_out, const double* d_slots, size_t count, uint64_t n_limbs, double scale);
 int hexl_ckks_decode(hexl_ks_plan* plan, double* d_slots, const uint64_t* d_in, size_t count, uint64_t n_limbs, double scale);
+/* Sampling, symmetric encryption and decryption on the device: with them a flow starts from slot vectors and a 32-byte seed and ends in
+ * slot vectors -- no ciphertext, error polynomial or mask crosses the bus, and the raw material of every switching key is one call.
+ *
+ * WARNING: (seed, stream, absolute polynomial index) MUST NEVER BE USED TWICE WITH ONE SECRET. The streams are deterministic: the same
+ * triple gives the same mask `a` and the same error `e`, and two encryptions under one (a, e) reveal the difference of their plaintexts
+ * (c0 - c0' = pt - pt'); an encryption and a hexl_sample call that share a triple publish the error. Give every call sequence of one
+ * secret its own `stream` (or a fresh seed from the operating system's generator), and advance `first` by `count` between calls that
+ * share both. Distinct kinds never collide (the kind is part of the block counter), distinct streams and distinct indices neither.
+ *
+ * The streams (normative): ChaCha20 in counter mode, the 20-round block function of RFC 8439 on the state
+ *   words 0-3 the constants 0x61707865 0x3320646e 0x79622d32 0x6b206574 | words 4-11 seed[0..7] (the caller's 32 bytes as eight
+ *   little-endian u32) | words 12, 13 low and high half of ctr = (kind << 60) | block | words 14, 15 low and high half of `stream`;
+ * output words w[0..15] (rounds + input state), u64 lane t < 8 = w[2t] | w[2t+1] << 32. c = first + local index is the ABSOLUTE
+ * polynomial index, so neither the split of a batch into calls nor anything inside the library changes a word:
+ *   HEXL_SAMPLE_UNIFORM  word j of polynomial (c, limb i): block = ((c 16 + i) n + j) >> 2, t = 2 (j & 3), r = lane[t] + 2^64 lane[t+1],
+ *                        word = r mod q_i -- uniform below q_i up to a bias under 2^-76, and uniform words are a uniform polynomial
+ *                        in NTT form as in coefficient form. The stream depends on i, not on n_limbs: the limbs of a lower level are
+ *                        a prefix of those of a higher one.
+ *   HEXL_SAMPLE_TERNARY  coefficient j of polynomial c, ONE integer polynomial shared by all limbs: block = (c n + j) >> 3,
+ *                        r = lane[j & 7], v = ((r 3) >> 64) - 1 in {-1, 0, 1} (secrets)
+ *   HEXL_SAMPLE_CBD21    the same addressing, v = popcount(r & 0x1FFFFF) - popcount((r >> 21) & 0x1FFFFF): |v| <= 21, sigma = sqrt(10.5)
+ *                        (SEAL's centred binomial error)
+ * A small value v becomes the words NTT_i(v mod q_i), negative v as q_i - |v|: what hexl_rns_from_f64 makes of the double v.
+ *
+ *   hexl_sample         d_out [count][n_limbs][n] WRITTEN with polynomials first ... first + count - 1 of the stream (seed, stream, kind),
+ *                       NTT form, canonical words.
+ *   hexl_rlwe_encrypt   d_out [count][2][n_limbs][n] WRITTEN with (pt + e - a s, a): a = the UNIFORM and e = the CBD21 polynomial
+ *                       first + b of (seed, stream). d_pt NULL (an encryption of zero: a public key, the mask of a key-switching
+ *                       key) or [pt_batch][n_limbs][n] in NTT form (hexl_ckks_encode's output), pt_batch = 1 or count, ignored when d_pt
+ *                       is NULL. d_secret [>= n_limbs][n]: NTT_i(s) in the plan's first n_limbs limbs, one secret for all instances (rows
+ *                       beyond n_limbs are not read: a secret kept at K limbs serves every level). Word for word the composition
+ *                       hexl_sample(UNIFORM), hexl_sample(CBD21), hexl_multiply_plain, hexl_ct_lincomb. Component 1 is a function of
+ *                       the seed: a sender may ship (c0, seed, stream, first) and the receiver expand `a` with hexl_sample.
+ *   hexl_rlwe_decrypt   d_out [count][n_limbs][n] WRITTEN with c0 + c1 s (+ c2 s^2 when n_components = 3) mod q_i, evaluated by
+ *                       Horner; d_ct [count][n_components][n_limbs][n], n_components 2 or 3 (3: a product before relinearisation);
+ *                       d_secret as above. The result is the plaintext plus the noise: hexl_ckks_decode takes it as it is.
+ * Key-shaped output: hexl_rlwe_encrypt with count = L (decomp_modulus_size), n_limbs = K, pt_batch = count writes [L][2][K][n] --
+ * word for word the h_keys layout of hexl_ks_set_keys (key d at d 2 K n, word (k K + i) n + j). With
+ *   pt[d][i] = [i == d] (P mod q_i) s'_i     P = the special prime, the plan's modulus K - 1; s' = the key being switched FROM
+ * (s^2 for relinearisation, s(X^g) for the Galois key of g), the output is a switching key from s' to s: pt is L calls of
+ * hexl_ct_lincomb on NTT(s') with per-limb weights. Download it once and pass the L slices to hexl_ks_set_keys; re-laying a device
+ * buffer into a plan without that round trip is not offered. Public-key encryption is hexl_sample + hexl_multiply_plain +
+ * hexl_ct_lincomb on a public key made here with d_pt = NULL.
+ * Common rules: FP64 plans only (every modulus < 2^52), n = 1024 ... 32768, 1 <= n_limbs <= K (the plan's first n_limbs moduli), no keys
+ * needed. Asynchronous on the context's stream; the seed travels by value in the kernels' arguments, so every host array may be
+ * reused as soon as the call returns. Precondition: every input word is below its modulus. Every output word is canonical.
+ * HEXL_E_BADARG: a null plan, output, seed, secret or (decrypt) ciphertext -- count == 0 does not excuse it --, an unknown kind, a plan
+ * on the integer kernels, n_limbs outside 1 ... K, pt_batch other than 1 or count when d_pt is given, n_components outside {2, 3},
+ * first + count > 2^40 (this keeps every block index below 2^60), a size or a grid that overflows, any overlap of the output with an
+ * input. count == 0 returns 0 after these checks and writes nothing.
+ * Device memory, kept in the plan and grow-only, shared with encode / decode: the small kinds and the error of an encryption pass
+ * through one chunk of real coefficients (n doubles per instance), hexl_rlwe_encrypt also through the chunk's NTT-form error
+ * (n_limbs x n words per instance); a chunk is 256 instances at n = 16384 and the same number of coefficients at every other n.
+ * UNIFORM and hexl_rlwe_decrypt are one launch and keep nothing. */
+#define HEXL_SAMPLE_UNIFORM 1
+#define HEXL_SAMPLE_TERNARY 2
+#define HEXL_SAMPLE_CBD21   3
+int hexl_sample(hexl_ks_plan* plan, uint64_t* d_out, int kind, const uint32_t seed[8], uint64_t stream, uint64_t first,
+                size_t count, uint64_t n_limbs);
+int hexl_rlwe_encrypt(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_pt, size_t pt_batch, const uint64_t* d_secret,
+                      const uint32_t seed[8], uint64_t stream, uint64_t first, size_t count, uint64_t n_limbs);
+int hexl_rlwe_decrypt(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_ct, const uint64_t* d_secret, size_t count,
+                      uint64_t n_components, uint64_t n_limbs);
 /* Arithmetic tier per limb (introspection for logs and tests): tiers[i], i < key_modulus_size, = the forward transforms' range-
  * reduction period modulo q_i on the FP64 path -- 12 / 6 / 3 for q_i <= 2^49 / 2^50 / 2^51 (1 + 2^-7), 0 = every value reduced after
  * every operation (q_i up to 2^52); -1 for every limb of a plan on the integer kernels (a modulus >= 2^52). Every transform runs modulo
