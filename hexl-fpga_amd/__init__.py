@@ -136,6 +136,22 @@ def _check(rc: int, what: str):
         raise HexlError(f"{what} failed with status {rc}")
 
 
+def _check_warn(rc: int, what: str) -> int:
+    """the status of an entry point for which 1 (HEXL_W_RANGE; hexl_ks_plan_tiers: the limbs differ) is an answer, not an error"""
+    if rc != 1:
+        _check(rc, what)
+    return rc
+
+
+def _handles(plans):
+    """ctypes array of plan handles, None entries as NULL"""
+    return (_vp * len(plans))(*[None if p is None else p.h.value for p in plans])
+
+
+def _u64_array(values):
+    return (_u64 * len(values))(*[int(v) for v in values])
+
+
 def ptr_array(arrays):
     """ctypes array of pointers to numpy arrays (host) or torch tensors (device), kept alive by the caller"""
     return (_vp * len(arrays))(*[_ptr(a) for a in arrays])
@@ -239,17 +255,12 @@ class KeySwitchPlan:
 
     def range_check(self) -> bool:
         """True if every keyswitch since the last check saw in-range words (syncs the stream, clears the flag)"""
-        rc = lib().hexl_ks_range_check(self.h)
-        if rc not in (0, 1):                                       # 1 = HEXL_W_RANGE
-            _check(rc, "hexl_ks_range_check")
-        return rc == 0
+        return _check_warn(lib().hexl_ks_range_check(self.h), "hexl_ks_range_check") == 0
 
     def tiers(self):
         """(per-limb forward reduction periods [K] -- 0 = strict, -1 = integer kernels --, True when the limbs in use differ)"""
         out = (_i * self.K)()
-        rc = lib().hexl_ks_plan_tiers(self.h, out)
-        if rc not in (0, 1):
-            _check(rc, "hexl_ks_plan_tiers")
+        rc = _check_warn(lib().hexl_ks_plan_tiers(self.h, out), "hexl_ks_plan_tiers")
         return list(out), rc == 1
 
     def multiply_relinearize(self, out, a, b, batch: int):
@@ -340,10 +351,8 @@ class KeySwitchPlan:
         n = len(results)
         r = (_vp * n)(*[_ptr(a) for a in results])
         t = (_vp * n)(*[_ptr(a) for a in t_targets])
-        rc = lib().hexl_keyswitch_host(self.h, r, t, n)
-        if rc != 1:                                                # 1 = HEXL_W_RANGE: computed, some object had an out-of-range word
-            _check(rc, "hexl_keyswitch_host")
-        return rc == 0
+        # (1 = HEXL_W_RANGE: computed, some object had an out-of-range word)
+        return _check_warn(lib().hexl_keyswitch_host(self.h, r, t, n), "hexl_keyswitch_host") == 0
 
     def time_stages(self, result, t_target, batch: int, iters: int):
         out = (ctypes.c_float * 4)()
@@ -367,10 +376,7 @@ def rotate_hoisted(plans, galois_elts, outs, ct, batch: int):
     (FP64 plans); the scratch is plans[0]'s."""
     if not (len(plans) == len(galois_elts) == len(outs)):
         raise ValueError("rotate_hoisted: one plan, one Galois element and one output per rotation")
-    n_rot = len(plans)
-    hs = (_vp * n_rot)(*[p.h.value for p in plans])
-    gs = (_u64 * n_rot)(*[int(g) for g in galois_elts])
-    _check(lib().hexl_rotate_hoisted(hs, gs, n_rot, ptr_array(outs), _ptr(ct), batch), "hexl_rotate_hoisted")
+    _check(lib().hexl_rotate_hoisted(_handles(plans), _u64_array(galois_elts), len(plans), ptr_array(outs), _ptr(ct), batch), "hexl_rotate_hoisted")
 
 
 def linear_transform(plans, galois_elts, pts, out, ct, batch: int, pt_identity=None):
@@ -382,10 +388,7 @@ def linear_transform(plans, galois_elts, pts, out, ct, batch: int, pt_identity=N
     context, n, L, K and moduli (FP64 plans); the scratch is plans[0]'s."""
     if not (len(plans) == len(galois_elts) == len(pts)):
         raise ValueError("linear_transform: one plan, one Galois element and one plaintext per rotation")
-    n_rot = len(plans)
-    hs = (_vp * n_rot)(*[p.h.value for p in plans])
-    gs = (_u64 * n_rot)(*[int(g) for g in galois_elts])
-    _check(lib().hexl_linear_transform(hs, gs, ptr_array(pts), n_rot, None if pt_identity is None else _ptr(pt_identity), _ptr(out),
+    _check(lib().hexl_linear_transform(_handles(plans), _u64_array(galois_elts), ptr_array(pts), len(plans), None if pt_identity is None else _ptr(pt_identity), _ptr(out),
                                        _ptr(ct), batch), "hexl_linear_transform")
 
 
@@ -406,10 +409,8 @@ def linear_transform_bsgs(baby_plans, baby_elts, giant_plans, giant_elts, pts, o
         raise ValueError("linear_transform_bsgs: one element per plan and n_giant rows of n_baby plaintexts")
     if pt_identity is not None and len(pt_identity) != n_giant:
         raise ValueError("linear_transform_bsgs: one identity plaintext (or None) per giant step")
-    handles = lambda plans: (_vp * len(plans))(*[None if p is None else p.h.value for p in plans])
     flat = [p for row in pts for p in row]
-    _check(lib().hexl_linear_transform_bsgs(handles(baby_plans), (_u64 * n_baby)(*[int(g) for g in baby_elts]), n_baby,
-                                            handles(giant_plans), (_u64 * n_giant)(*[int(g) for g in giant_elts]), n_giant,
+    _check(lib().hexl_linear_transform_bsgs(_handles(baby_plans), _u64_array(baby_elts), n_baby, _handles(giant_plans), _u64_array(giant_elts), n_giant,
                                             _opt_ptrs(flat), None if pt_identity is None else _opt_ptrs(pt_identity), _ptr(out), _ptr(ct),
                                             batch), "hexl_linear_transform_bsgs")
 

@@ -8,28 +8,6 @@
 #include "number_theory.hpp"
 
 // ------------------------------------------------------------------------------- context
-int hx_grow_device(void** p, size_t* cap, size_t need, size_t unit, hexl_ctx* ctx) {
-    if (*cap >= need) return 0;
-    if (*p) {
-        HX_CHECK(ctx ? hipStreamSynchronize(ctx->stream) : hipDeviceSynchronize());
-        HX_CHECK(hipFree(*p));
-        *p = nullptr; *cap = 0;
-    }
-    HX_CHECK(hipMalloc(p, need * unit));
-    *cap = need;
-    return 0;
-}
-int hx_reserve_pinned(hexl_ctx* ctx, void** p, size_t* cur, size_t need, bool coherent) {
-    if (*cur >= need) return 0;
-    if (*p) { HX_CHECK(hipStreamSynchronize(ctx->stream)); HX_CHECK(hipHostFree(*p)); *p = nullptr; *cur = 0; }
-    // coherent (fine-grained) slabs are for the zero-copy lone keyswitch only, whose host side reads result limbs the RUNNING kernel has
-    // just published (host_staging.hip keyswitch_host_lone). The staging pipeline's slabs stay default: with coherent ones its copy-engine transfers ran a
-    // third slower (worksize 128: 13.4 k against 21 k keyswitch/s through the C++ API)
-    HX_CHECK(hipHostMalloc(p, need, coherent ? hipHostMallocCoherent : hipHostMallocDefault));
-    *cur = need;
-    return 0;
-}
-
 // NUMA node the library's own host threads (copy pool, unpack lane) ask for: the node of the devices in use when they all hang off one
 // node, else no preference (host_simd.cpp; round 6: +16 % on the host-pointer KeySwitch at worksize 128). -2 = no context yet.
 int hx_numa_node_of_pci(const char* bdf);
@@ -76,14 +54,6 @@ extern "C" int hexl_ctx_destroy(hexl_ctx* c) {
     if (!c) return 0;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    if (c->d_stage) (void)hipFree(c->d_stage);
-    if (c->d_shared) (void)hipFree(c->d_shared);
-    if (c->d_meta) (void)hipFree(c->d_meta);
-    if (c->d_ntt_tab) (void)hipFree(c->d_ntt_tab);
-    if (c->d_ntt_redo) (void)hipFree(c->d_ntt_redo);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->h_lone) (void)hipHostFree(c->h_lone);
-    if (c->h_ntt_hint) (void)hipHostFree(c->h_ntt_hint);
     if (c->s_up) (void)hipStreamDestroy(c->s_up);
     if (c->s_down) (void)hipStreamDestroy(c->s_down);
     for (int i = 0; i < 2; ++i) {
@@ -93,7 +63,7 @@ extern "C" int hexl_ctx_destroy(hexl_ctx* c) {
     }
     if (c->ev_switch) (void)hipEventDestroy(c->ev_switch);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;                                                     // every HxBuf member releases its memory (the stream was drained above)
     return 0;
 }
 
@@ -289,26 +259,26 @@ extern "C" int hexl_ks_plan_create(hexl_ctx* c, uint64_t n, uint64_t L, uint64_t
             f.fix = (double)mods[i].fix;
             f.half = (double)mods[i].half;
         }
-        HX_CHECK(hipMalloc((void**)&p->d_mods_f64, K * sizeof(KsModF64)));
-        HX_CHECK(hipMalloc((void**)&p->d_tables_f64, ft.size() * sizeof(double)));
-        HX_CHECK(hipMalloc((void**)&p->d_keys_f64, size_t(L) * (L + 1) * 2 * n * sizeof(double)));
-        if (logn >= 10 && logn <= 15) HX_CHECK(hipMalloc((void**)&p->d_keys_x, size_t(L) * (L + 1) * 2 * n * sizeof(double)));
-        if (logn == 14) HX_CHECK(hipMalloc((void**)&p->d_keys_nat, size_t(L) * (L + 1) * 2 * n * sizeof(double)));
-        HX_CHECK(hipMemcpy(p->d_mods_f64, fm.data(), K * sizeof(KsModF64), hipMemcpyHostToDevice));
-        HX_CHECK(hipMemcpy(p->d_tables_f64, ft.data(), ft.size() * sizeof(double), hipMemcpyHostToDevice));
+        const size_t key_words = size_t(L) * (L + 1) * 2 * n;
+        if (int rc = p->d_mods_f64.upload_once(fm.data(), K)) return rc;
+        if (int rc = p->d_tables_f64.upload_once(ft.data(), ft.size())) return rc;
+        if (int rc = p->d_keys_f64.reserve(key_words)) return rc;
+        if (logn >= 10 && logn <= 15)
+            if (int rc = p->d_keys_x.reserve(key_words)) return rc;
+        if (logn == 14)
+            if (int rc = p->d_keys_nat.reserve(key_words)) return rc;
     }
     // input-range flag of the FP64 kernels (hexl_ks_range_check) + its pinned mirror; HEXL_KS_VALIDATE shares them
     // word 0: the kernels' range flag (HEXL_W_RANGE); word 1: HEXL_KS_VALIDATE's own (HEXL_E_RANGE) -- two statuses, two words
     // (word 2: the output gate of the zero-copy lone keyswitch, keyswitch_lat.hip k_ksq_down)
-    HX_CHECK(hipMalloc((void**)&p->d_flag, 4 * sizeof(u32)));
+    if (int rc = p->d_flag.reserve(4)) return rc;
     HX_CHECK(hipMemset(p->d_flag, 0, 4 * sizeof(u32)));
-    HX_CHECK(hipHostMalloc((void**)&p->h_flag, 2 * sizeof(u32), hipHostMallocDefault));
-    HX_CHECK(hipMalloc((void**)&p->d_mods, K * sizeof(KsModulus)));
-    HX_CHECK(hipMalloc((void**)&p->d_tables, tables.size() * sizeof(u64)));
+    if (int rc = p->h_flag.reserve(2)) return rc;
+    if (int rc = p->d_mods.upload_once(mods.data(), K)) return rc;
+    if (int rc = p->d_tables.upload_once(tables.data(), tables.size())) return rc;
     // integer-kernel keys (key words + Shoup factors): only plans that run the integer kernels hold them
-    if (!f64_ok) HX_CHECK(hipMalloc((void**)&p->d_keys, size_t(L) * (L + 1) * 4 * n * sizeof(u64)));
-    HX_CHECK(hipMemcpy(p->d_mods, mods.data(), K * sizeof(KsModulus), hipMemcpyHostToDevice));
-    HX_CHECK(hipMemcpy(p->d_tables, tables.data(), tables.size() * sizeof(u64), hipMemcpyHostToDevice));
+    if (!f64_ok)
+        if (int rc = p->d_keys.reserve(size_t(L) * (L + 1) * 4 * n)) return rc;
     guard.p = nullptr;
     *out = p;
     return 0;
@@ -318,33 +288,12 @@ extern "C" int hexl_ks_plan_destroy(hexl_ks_plan* p) {
     if (!p) return 0;
     (void)hipSetDevice(p->ctx->device);
     (void)hipDeviceSynchronize();
-    if (p->d_mods) (void)hipFree(p->d_mods);
-    if (p->d_tables) (void)hipFree(p->d_tables);
-    if (p->d_keys) (void)hipFree(p->d_keys);
-    if (p->d_scratch) (void)hipFree(p->d_scratch);
     for (int l = 0; l < HX_KS_MAX_LANES; ++l) {
         if (p->aux[l]) (void)hipStreamDestroy(p->aux[l]);
         if (p->ev_done[l]) (void)hipEventDestroy(p->ev_done[l]);
     }
     if (p->ev_start) (void)hipEventDestroy(p->ev_start);
-    if (p->d_mods_f64) (void)hipFree(p->d_mods_f64);
-    if (p->d_tables_f64) (void)hipFree(p->d_tables_f64);
-    if (p->d_keys_f64) (void)hipFree(p->d_keys_f64);
-    if (p->d_keys_x) (void)hipFree(p->d_keys_x);
-    if (p->d_keys_nat) (void)hipFree(p->d_keys_nat);
-    if (p->d_flag) (void)hipFree(p->d_flag);
-    if (p->h_flag) (void)hipHostFree(p->h_flag);
-    if (p->d_rescale) (void)hipFree(p->d_rescale);
-    if (p->d_rs_s) (void)hipFree(p->d_rs_s);
-    if (p->d_rot_t) (void)hipFree(p->d_rot_t);
-    if (p->d_bsgs_b) (void)hipFree(p->d_bsgs_b);
-    if (p->d_bsgs_t) (void)hipFree(p->d_bsgs_t);
-    if (p->d_emb_roots) (void)hipFree(p->d_emb_roots);
-    if (p->d_emb_perm) (void)hipFree(p->d_emb_perm);
-    if (p->d_garner) (void)hipFree(p->d_garner);
-    if (p->d_enc_coeffs) (void)hipFree(p->d_enc_coeffs);
-    if (p->d_enc_words) (void)hipFree(p->d_enc_words);
-    delete p;
+    delete p;                                                     // every HxBuf member releases its memory (the device was drained above)
     return 0;
 }
 
@@ -435,10 +384,7 @@ extern "C" int hexl_multiply_relinearize(hexl_ks_plan* p, uint64_t* d_out, const
     if (!p || !d_out || !d_a || !d_b) return HEXL_E_BADARG;
     // d_out is written while d_a / d_b are still being read (component 0 is stored before component 1's operands are loaded)
     const size_t bytes = batch * 2 * size_t(p->L) * p->n * sizeof(u64);
-    auto overlaps = [&](const uint64_t* x) {
-        return (const char*)d_out < (const char*)x + bytes && (const char*)x < (const char*)d_out + bytes;
-    };
-    if (overlaps(d_a) || overlaps(d_b)) return HEXL_E_BADARG;
+    if (hx_ranges_overlap(d_out, bytes, d_a, bytes) || hx_ranges_overlap(d_out, bytes, d_b, bytes)) return HEXL_E_BADARG;
     HX_CHECK(hipSetDevice(p->ctx->device));
     return hx_launch_multiply_relinearize(p, d_out, d_a, d_b, batch);
 }

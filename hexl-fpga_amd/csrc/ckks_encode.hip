@@ -35,8 +35,6 @@ __device__ __forceinline__ cplx root(const double2* roots, u32 t) {
 constexpr u32 EMB_MAX_LOGB = 13;            // complex points one workgroup holds in LDS: 8192 x 16 bytes = 128 KiB of the CU's 160
 constexpr u32 EMB_MAX_THREADS = 1024;
 constexpr u32 EMB_TOP_THREADS = 256;
-// instances per scratch chunk (hexl_internal.hpp: rlwe.hip fills the same scratch under the same rule)
-static size_t emb_chunk(const hexl_ks_plan* p) { return hx_enc_chunk(p); }
 
 struct EmbArgs {
     const double2* roots;       // [2n]
@@ -195,13 +193,9 @@ static int run_from_f64(hexl_ks_plan* p, const FromF64Args& a) {
     return (int)hipGetLastError();
 }
 
-// the schedule every limb in use admits; LAZY = -1 (per-limb lookup) when they differ, as hx_launch_rns_ntt chooses
 static int launch_from_f64(hexl_ks_plan* p, u64* d_out, const double* d_coeffs, size_t count, u32 n_limbs) {
-    int lazy = p->tier[0];
-    for (u32 i = 1; i < n_limbs; ++i)
-        if (p->tier[i] != p->tier[0]) lazy = -1;
     const FromF64Args a{p->d_mods_f64, p->d_tables_f64, d_coeffs, d_out, p->d_flag, (u32)count, n_limbs, hx_tiermap(p)};
-    return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return run_from_f64<N, E, Z>(p, a); });
+    return hx_with_f64_geom(p->logn, hx_level_tier(p, n_limbs), [&](auto N, auto E, auto Z) { return run_from_f64<N, E, Z>(p, a); });
 }
 
 // ---- coefficient-form limbs -> real coefficients ----
@@ -297,16 +291,8 @@ static int embed_tables(hexl_ks_plan* p) {
         pw = pw * 5 % (2 * u64(n));
     }
     for (u32 q = 0; q < nh; ++q) perm[q] = slot_of_s[hxnt::bitrev(q, logh)];
-    u32* d_perm = nullptr;
-    double* d_roots = nullptr;
-    HX_CHECK(hipMalloc((void**)&d_perm, perm.size() * sizeof(u32)));
-    if (hipError_t e = hipMalloc((void**)&d_roots, roots.size() * sizeof(double)); e != hipSuccess) { (void)hipFree(d_perm); return (int)e; }
-    hipError_t e = hipMemcpy(d_perm, perm.data(), perm.size() * sizeof(u32), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_roots, roots.data(), roots.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d_perm); (void)hipFree(d_roots); return (int)e; }
-    p->d_emb_perm = d_perm;
-    p->d_emb_roots = d_roots;
-    return 0;
+    if (int rc = p->d_emb_perm.upload_once(perm.data(), perm.size())) return rc;
+    return p->d_emb_roots.upload_once(roots.data(), roots.size());     // (the roots last: they are what says "both are there")
 }
 
 // Garner's constants q_j^-1 mod q_i for j < i < K: those of a prefix of the chain are a prefix of these, so one table serves every level
@@ -320,11 +306,7 @@ static int garner_table(hexl_ks_plan* p) {
             g[(size_t(i) * GARNER_MAX + j) * 2] = c;
             g[(size_t(i) * GARNER_MAX + j) * 2 + 1] = c / (double)q;
         }
-    double* d = nullptr;
-    HX_CHECK(hipMalloc((void**)&d, g.size() * sizeof(double)));
-    if (hipError_t e = hipMemcpy(d, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice); e != hipSuccess) { (void)hipFree(d); return (int)e; }
-    p->d_garner = d;
-    return 0;
+    return p->d_garner.upload_once(g.data(), g.size());
 }
 
 // ---- launchers ----
@@ -355,20 +337,18 @@ int hx_launch_encode(hexl_ks_plan* p, u64* d_out, const double* d_coeffs, const 
     const size_t n = p->n;
     if (!d_slots) return launch_from_f64(p, d_out, d_coeffs, count, n_limbs);
     if (int rc = embed_tables(p)) return rc;
-    const size_t chunk = count < emb_chunk(p) ? count : emb_chunk(p);
-    if (int rc = hx_grow_device((void**)&p->d_enc_coeffs, &p->enc_coeffs_cap, chunk, n * sizeof(double), nullptr)) return rc;
+    const size_t chunk = hx_enc_chunk_of(p, count);
+    if (int rc = p->d_enc_coeffs.reserve(chunk * n)) return rc;
     EmbArgs a{};
-    a.roots = reinterpret_cast<const double2*>(p->d_emb_roots);
+    a.roots = reinterpret_cast<const double2*>(p->d_emb_roots.get());
     a.perm = p->d_emb_perm;
     a.coeffs = p->d_enc_coeffs;
     a.factor = scale / (double)(n / 2);
-    for (size_t c0 = 0; c0 < count; c0 += chunk) {
-        const size_t nb = count - c0 < chunk ? count - c0 : chunk;
+    return hx_for_chunks(count, chunk, [&](size_t c0, size_t nb) {
         a.slots_in = d_slots + c0 * n;
         if (int rc = launch_embed(p, a, nb, true)) return rc;
-        if (int rc = launch_from_f64(p, d_out + c0 * n_limbs * n, p->d_enc_coeffs, nb, n_limbs)) return rc;
-    }
-    return 0;
+        return launch_from_f64(p, d_out + c0 * n_limbs * n, p->d_enc_coeffs, nb, n_limbs);
+    });
 }
 
 int hx_launch_decode(hexl_ks_plan* p, double* d_coeffs, double* d_slots, const u64* d_in, size_t count, u32 n_limbs, double scale) {
@@ -377,41 +357,37 @@ int hx_launch_decode(hexl_ks_plan* p, double* d_coeffs, double* d_slots, const u
     const size_t n = p->n;
     if (d_slots)
         if (int rc = embed_tables(p)) return rc;
-    const size_t chunk = count < emb_chunk(p) ? count : emb_chunk(p);
-    if (int rc = hx_grow_device((void**)&p->d_enc_words, &p->enc_words_cap, chunk * n_limbs, n * sizeof(u64), nullptr)) return rc;
+    const size_t chunk = hx_enc_chunk_of(p, count);
+    if (int rc = p->d_enc_words.reserve(chunk * n_limbs * n)) return rc;
     if (d_slots)
-        if (int rc = hx_grow_device((void**)&p->d_enc_coeffs, &p->enc_coeffs_cap, chunk, n * sizeof(double), nullptr)) return rc;
-    CrtArgs ca{p->d_mods_f64, reinterpret_cast<const double2*>(p->d_garner), p->d_enc_words, nullptr, p->logn, n_limbs};
+        if (int rc = p->d_enc_coeffs.reserve(chunk * n)) return rc;
+    CrtArgs ca{p->d_mods_f64, reinterpret_cast<const double2*>(p->d_garner.get()), p->d_enc_words, nullptr, p->logn, n_limbs};
     EmbArgs a{};
     if (d_slots) {
-        a.roots = reinterpret_cast<const double2*>(p->d_emb_roots);
+        a.roots = reinterpret_cast<const double2*>(p->d_emb_roots.get());
         a.perm = p->d_emb_perm;
         a.coeffs = p->d_enc_coeffs;
         a.factor = 1.0 / scale;
     }
-    for (size_t c0 = 0; c0 < count; c0 += chunk) {
-        const size_t nb = count - c0 < chunk ? count - c0 : chunk;
+    return hx_for_chunks(count, chunk, [&](size_t c0, size_t nb) {
         if (int rc = hx_launch_rns_ntt(p, p->d_enc_words, d_in + c0 * n_limbs * n, nb, n_limbs, true)) return rc;
-        ca.out = d_slots ? p->d_enc_coeffs : d_coeffs + c0 * n;
+        ca.out = d_slots ? p->d_enc_coeffs.get() : d_coeffs + c0 * n;
         hipLaunchKernelGGL(k_crt_to_f64, dim3((u32)(nb * n / CRT_THREADS)), dim3(CRT_THREADS), 0, p->ctx->stream, ca);
         if (int rc = (int)hipGetLastError()) return rc;
-        if (d_slots) {
-            a.slots_out = d_slots + c0 * n;
-            if (int rc = launch_embed(p, a, nb, false)) return rc;
-        }
-    }
-    return 0;
+        if (!d_slots) return 0;
+        a.slots_out = d_slots + c0 * n;
+        return launch_embed(p, a, nb, false);
+    });
 }
 
 // ---- entry points of include/hexl_mi355x.h ----
-constexpr size_t ENC_MAX_GRID = 0x7fffffffu;
-// FP64 plan of a ring dimension the transforms are built for, 1 <= n_limbs <= K, sizes that fit, and the [count][n_limbs][n] words
-// apart from the [count][n] doubles (coefficients, or n/2 complex slots)
+// the checks of hexl_internal.hpp for 1 <= n_limbs <= K, and the [count][n_limbs][n] words apart from the [count][n] doubles
+// (coefficients, or n/2 complex slots)
 static bool enc_args_ok(const hexl_ks_plan* p, const void* d_words, const void* d_reals, size_t count, u64 n_limbs) {
-    if (!d_words || !d_reals || !p || !p->use_f64 || p->logn < 10 || p->logn > 15 || n_limbs < 1 || n_limbs > p->K) return false;
-    const size_t per = size_t(n_limbs) * p->n * sizeof(u64);
-    if (count > SIZE_MAX / per || count > ENC_MAX_GRID / n_limbs) return false;
-    return !hx_ranges_overlap(d_words, count * per, d_reals, count * p->n * sizeof(double));
+    if (!d_words || !d_reals || !p || !hx_f64_plan_ok(p, n_limbs, 1, p->K)) return false;
+    size_t bytes;
+    if (!hx_words_bytes(count, 1, n_limbs, p->n, &bytes) || !hx_wg_grid_ok(count, n_limbs)) return false;
+    return !hx_ranges_overlap(d_words, bytes, d_reals, bytes / n_limbs);
 }
 static bool scale_ok(double scale) { return scale > 0.0 && scale < INFINITY; }
 

@@ -195,6 +195,7 @@ struct GaloisPtArgs {
     u32 n_rot, nb, L, logn;
 };
 constexpr u32 GPT_THREADS = 256, GPT_LOG_CHUNK = 9;     // two adjacent words per lane: 512 words of one polynomial per workgroup
+static_assert(GPT_THREADS == HX_WW_THREADS && GPT_THREADS * 2 == 1u << GPT_LOG_CHUNK, "hx_ww_grid(., ., ., GPT_LOG_CHUNK) counts these workgroups");
 
 // One workgroup per (limb, 512-word piece, instance), the instance fastest: the workgroups resident at any time meet the same plaintext
 // words, which are read from HBM once and from L2 afterwards. A lane owns two adjacent output words (16-byte plaintext loads and stores)
@@ -246,7 +247,7 @@ int hx_launch_galois_c0_pt(hexl_ks_plan* p, u64* d_out, const u64* d_ct, const H
                            size_t nb) {
     if (!nb) return 0;
     const GaloisPtArgs a{p->d_mods_f64, d_ct, d_out, d_rots, d_pt_identity, p->d_flag, (u32)n_rot, (u32)nb, p->L, p->logn};
-    const dim3 grid((u32)(nb * p->L * (p->n >> GPT_LOG_CHUNK))), block(GPT_THREADS);
+    const dim3 grid((u32)hx_ww_grid(p, nb, p->L, GPT_LOG_CHUNK)), block(GPT_THREADS);
     if (d_pt_identity) hipLaunchKernelGGL((k_galois_c0_pt<true>), grid, block, 0, p->ctx->stream, a);
     else hipLaunchKernelGGL((k_galois_c0_pt<false>), grid, block, 0, p->ctx->stream, a);
     return (int)hipGetLastError();
@@ -288,7 +289,7 @@ __global__ __launch_bounds__(GPT_THREADS) void k_galois_add(GaloisAddArgs a) {
 int hx_launch_galois_add(hexl_ks_plan* p, u64* d_out, const u64* d_t, size_t nb, u32 g, u32 n_comp) {
     if (!nb) return 0;
     const GaloisAddArgs a{p->d_mods_f64, d_t, d_out, (u32)nb, p->L, p->logn, g};
-    hipLaunchKernelGGL(k_galois_add, dim3((u32)(nb * n_comp * p->L * (p->n >> GPT_LOG_CHUNK))), dim3(GPT_THREADS), 0, p->ctx->stream, a);
+    hipLaunchKernelGGL(k_galois_add, dim3((u32)hx_ww_grid(p, nb * n_comp, p->L, GPT_LOG_CHUNK)), dim3(GPT_THREADS), 0, p->ctx->stream, a);
     return (int)hipGetLastError();
 }
 
@@ -305,10 +306,7 @@ static int run_rescale(hexl_ks_plan* p, const RsArgs& a, u32 nb, u32 ncomp) {
 
 // per-level constants, computed on the host at the first rescale that drops limb l and kept in the plan
 static int rescale_constants(hexl_ks_plan* p, u32 l) {
-    if (!p->d_rescale) {
-        HX_CHECK(hipMalloc((void**)&p->d_rescale, size_t(16) * 16 * sizeof(KsRescaleF64)));
-        p->rescale_levels = 0;
-    }
+    if (int rc = p->d_rescale.reserve(size_t(16) * 16)) return rc;
     if (p->rescale_levels >> l & 1u) return 0;
     const u64 ql = p->moduli[l], half = ql >> 1;
     KsRescaleF64 rm[16];
@@ -333,11 +331,8 @@ int hx_launch_rescale(hexl_ks_plan* p, u64* d_out, const u64* d_in, size_t batch
     const size_t n = p->n;
     const size_t chunk = hx_ks_chunk_of(p, batch);
     // s: one polynomial per (instance, component) of a chunk
-    if (int rc = hx_grow_device((void**)&p->d_rs_s, &p->rs_cap, chunk * ncomp, n * sizeof(double), nullptr)) return rc;
-    // the schedule every limb of the level admits; LAZY = -1 (per-limb lookup) when they differ
-    int lazy = p->tier[0];
-    for (u32 i = 1; i <= l; ++i)
-        if (p->tier[i] != p->tier[0]) lazy = -1;
+    if (int rc = p->d_rs_s.reserve(chunk * ncomp * n)) return rc;
+    const int lazy = hx_level_tier(p, n_limbs);
     RsArgs a;
     a.mods = p->d_mods_f64; a.tables = p->d_tables_f64;
     a.rm = p->d_rescale + size_t(l) * 16;
@@ -345,14 +340,12 @@ int hx_launch_rescale(hexl_ks_plan* p, u64* d_out, const u64* d_in, size_t batch
     a.half = (double)(p->moduli[l] >> 1);
     a.l = l;
     a.tiermap = hx_tiermap(p);
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-        const size_t nb = batch - b0 < chunk ? batch - b0 : chunk;
+    return hx_for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
         a.in = d_in + b0 * ncomp * n_limbs * n;
         a.out = d_out + b0 * ncomp * l * n;
         // (the (LOGN, LOGE) and tier instantiations of run_chunk_f64, keyswitch_f64.hip)
-        if (int rc = hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return run_rescale<N, E, Z>(p, a, (u32)nb, ncomp); })) return rc;
-    }
-    return 0;
+        return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return run_rescale<N, E, Z>(p, a, (u32)nb, ncomp); });
+    });
 }
 
 // ---- rotate ----
@@ -361,24 +354,21 @@ int hx_launch_rotate(hexl_ks_plan* p, u64* d_out, const u64* d_ct, size_t batch,
     if (!p->have_keys) return HEXL_E_NOKEYS;
     const size_t n = p->n, L = p->L;
     const size_t slice = hx_ks_chunk_of(p, batch);
-    if (int rc = hx_grow_device((void**)&p->d_rot_t, &p->rot_cap, slice, L * n * sizeof(u64), nullptr)) return rc;
-    for (size_t b0 = 0; b0 < batch; b0 += slice) {
-        const size_t nb = batch - b0 < slice ? batch - b0 : slice;
+    if (int rc = p->d_rot_t.reserve(slice * L * n)) return rc;
+    return hx_for_chunks(batch, slice, [&](size_t b0, size_t nb) {
         u64* out = d_out + b0 * 2 * L * n;
         GaloisArgs a{d_ct + b0 * 2 * L * n, out, p->d_rot_t, nb * 2 * L, p->logn, g, (u32)L};
         if (int rc = launch_galois(p->ctx, p->ctx->stream, a)) return rc;
         // hx_launch_keyswitch joins its lanes back into the caller's stream before it returns (keyswitch.hip), so the next
         // slice's gather into the same t buffer runs after this keyswitch has read it
-        if (int rc = hx_launch_keyswitch(p, out, p->d_rot_t, nb, 7, nullptr)) return rc;
-    }
-    return 0;
+        return hx_launch_keyswitch(p, out, p->d_rot_t, nb, 7, nullptr);
+    });
 }
 
 // ---- entry points of include/hexl_mi355x.h. They live here rather than in capi.hip: the CPU staging model (tests/cpp) compiles
 // capi.hip and host_staging.hip against stubs of the launchers those two call, and needs none for these. ----
 static bool ring_dimension_ok(u64 n) { return n >= 1024 && n <= 32768 && !(n & (n - 1)); }
 static bool galois_elt_ok(u64 g, u64 n) { return (g & 1) && g < 2 * n; }
-static bool f64_ring_ok(const hexl_ks_plan* p) { return p->use_f64 && p->logn >= 10 && p->logn <= 15; }   // the (b, d)-major FP64 kernels only
 // a plan of a hoisted call works in p0's scratch with p0's geometry: same context, same FP64 ring
 static bool same_ring(const hexl_ks_plan* p, const hexl_ks_plan* p0) {
     return p->ctx == p0->ctx && p->n == p0->n && p->L == p0->L && p->K == p0->K && p->use_f64 && p->moduli == p0->moduli;
@@ -388,16 +378,14 @@ struct CtBytes { size_t row, per, bytes, pt_bytes; };
 static bool ct_bytes(const hexl_ks_plan* p0, size_t batch, CtBytes& s) {
     s.row = size_t(p0->L) * p0->n * sizeof(u64);
     s.per = 2 * s.row;
-    if (batch > SIZE_MAX / s.per) return false;
-    s.bytes = batch * s.per;
     s.pt_bytes = s.row + p0->n * sizeof(u64);
-    return true;
+    return hx_words_bytes(batch, 2, p0->L, p0->n, &s.bytes);
 }
 
 extern "C" int hexl_apply_galois(hexl_ctx* c, uint64_t* d_out, const uint64_t* d_in, size_t count, uint64_t n, uint64_t g) {
     if (!c || !d_out || !d_in || !ring_dimension_ok(n) || !galois_elt_ok(g, n)) return HEXL_E_BADARG;
-    if (count > (SIZE_MAX / sizeof(u64)) / n) return HEXL_E_BADARG;
-    const size_t bytes = count * n * sizeof(u64);
+    size_t bytes;
+    if (!hx_words_bytes(count, 1, 1, n, &bytes)) return HEXL_E_BADARG;
     if (hx_ranges_overlap(d_out, bytes, d_in, bytes)) return HEXL_E_BADARG;    // a permutation cannot run in place
     if (!count) return 0;
     u32 logn = 0;
@@ -408,11 +396,10 @@ extern "C" int hexl_apply_galois(hexl_ctx* c, uint64_t* d_out, const uint64_t* d
 
 extern "C" int hexl_rescale(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_in, size_t batch, uint64_t n_limbs,
                             uint64_t n_components) {
-    if (!p || !d_out || !d_in || !f64_ring_ok(p)) return HEXL_E_BADARG;
-    if (n_limbs < 2 || n_limbs > p->K - 1 || n_components < 1 || n_components > 3) return HEXL_E_BADARG;
-    const size_t per = size_t(n_components) * p->n * sizeof(u64);
-    if (batch > SIZE_MAX / (per * n_limbs)) return HEXL_E_BADARG;
-    if (hx_ranges_overlap(d_out, batch * per * (n_limbs - 1), d_in, batch * per * n_limbs)) return HEXL_E_BADARG;
+    if (!p || !d_out || !d_in || !hx_f64_plan_ok(p, n_limbs, 2, p->K - 1) || !hx_in_range(n_components, 1, 3)) return HEXL_E_BADARG;
+    size_t in_bytes;
+    if (!hx_words_bytes(batch, n_components, n_limbs, p->n, &in_bytes)) return HEXL_E_BADARG;
+    if (hx_ranges_overlap(d_out, in_bytes / n_limbs * (n_limbs - 1), d_in, in_bytes)) return HEXL_E_BADARG;
     HX_CHECK(hipSetDevice(p->ctx->device));
     return hx_launch_rescale(p, d_out, d_in, batch, (u32)n_limbs, (u32)n_components);
 }
@@ -437,7 +424,7 @@ extern "C" int hexl_rotate_hoisted(hexl_ks_plan* const* plans, const uint64_t* g
         if (!plans[r] || !d_outs[r]) return HEXL_E_BADARG;
     const hexl_ks_plan* p0 = plans[0];
     CtBytes s;
-    if (!f64_ring_ok(p0) || !ct_bytes(p0, batch, s)) return HEXL_E_BADARG;
+    if (!hx_f64_plan_ok(p0) || !ct_bytes(p0, batch, s)) return HEXL_E_BADARG;
     for (size_t r = 0; r < n_rot; ++r) {
         if (!same_ring(plans[r], p0) || !galois_elt_ok(galois_elts[r], p0->n)) return HEXL_E_BADARG;
         if (hx_ranges_overlap(d_outs[r], s.bytes, d_ct, s.bytes)) return HEXL_E_BADARG;
@@ -459,7 +446,7 @@ extern "C" int hexl_linear_transform(hexl_ks_plan* const* plans, const uint64_t*
         if (!plans[r] || !d_pts[r]) return HEXL_E_BADARG;
     const hexl_ks_plan* p0 = plans[0];
     CtBytes s;
-    if (!f64_ring_ok(p0) || !ct_bytes(p0, batch, s)) return HEXL_E_BADARG;
+    if (!hx_f64_plan_ok(p0) || !ct_bytes(p0, batch, s)) return HEXL_E_BADARG;
     if (hx_ranges_overlap(d_out, s.bytes, d_ct, s.bytes)) return HEXL_E_BADARG;
     if (d_pt_identity && hx_ranges_overlap(d_out, s.bytes, d_pt_identity, s.row)) return HEXL_E_BADARG;
     for (size_t r = 0; r < n_rot; ++r) {
@@ -485,7 +472,7 @@ extern "C" int hexl_linear_transform_bsgs(hexl_ks_plan* const* baby_plans, const
     for (size_t j = 0; j < n_giant && !p0; ++j) p0 = giant_plans[j];
     if (!p0) return HEXL_E_BADARG;
     CtBytes s;
-    if (!f64_ring_ok(p0) || !ct_bytes(p0, batch, s)) return HEXL_E_BADARG;
+    if (!hx_f64_plan_ok(p0) || !ct_bytes(p0, batch, s)) return HEXL_E_BADARG;
     if (n_baby > HX_LT_BSGS_STORE_BYTES / (2 * s.pt_bytes)) return HEXL_E_BADARG;   // not one instance would fit the baby store
     if (hx_ranges_overlap(d_out, s.bytes, d_ct, s.bytes)) return HEXL_E_BADARG;
     for (size_t i = 0; i < n_baby; ++i)

@@ -129,9 +129,9 @@ int hx_launch_dyadic(hexl_ctx* ctx, u64* d_out, const u64* d_a, const u64* d_b, 
     if (!batch || !n_moduli) return 0;
     if (n == 0 || n > (1u << 24)) return HEXL_E_BADARG;
     const size_t rows = batch * n_moduli;
-    int rc = hx_reserve_device(ctx, &ctx->d_meta, &ctx->d_meta_bytes, rows * sizeof(DyMeta));
+    int rc = ctx->d_meta.reserve(rows * sizeof(DyMeta));
     if (rc) return rc;
-    DyMeta* meta = (DyMeta*)ctx->d_meta;
+    DyMeta* meta = (DyMeta*)ctx->d_meta.get();
     hipLaunchKernelGGL(k_dyadic_meta, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ctx->stream, meta,
                        d_moduli, (u32)rows);
     // 16-byte accesses need every row to start 16-byte aligned: n even and 16-byte aligned base pointers

@@ -62,6 +62,64 @@ inline int hx_knob_ks_pipe() { static const int v = (int)hx_knob("HEXL_KS_PIPE",
 // HEXL_KS_FUSE: bit 0 clear = the (b, d)-major pipeline runs steps 1-2 as one transform per workgroup even for large batches
 inline int hx_knob_ks_fuse() { static const int v = (int)hx_knob("HEXL_KS_FUSE", 1); return v; }
 
+// ---- owned device / pinned memory (DESIGN.md 4.7 "Host scaffold"). HxBuf<T> is one grow-only allocation of `capacity()` elements that
+// releases itself with its owner; HOST_FLAGS < 0: device memory (HxDevBuf), else pinned host memory of those hipHostMalloc flags
+// (HxPinBuf). The drain rule is fixed at construction: before a grown buffer's old memory is released, everything that may still use
+// it has to finish -- the stream of the context given, or the whole device when there is none (a plan's buffers: lanes on the plan's
+// auxiliary streams use them). The destructor does NOT wait: hexl_ctx_destroy / hexl_ks_plan_destroy synchronise first.
+struct hexl_ctx;
+inline int hx_drain(hexl_ctx* ctx);
+template <class T, int HOST_FLAGS = -1>
+class HxBuf {
+public:
+    explicit HxBuf(hexl_ctx* drain = nullptr) : drain_(drain) {}
+    HxBuf(const HxBuf&) = delete;
+    HxBuf& operator=(const HxBuf&) = delete;
+    ~HxBuf() { release(); }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    size_t capacity() const { return cap_; }
+    // room for `count` elements; contents are NOT kept when the buffer grows
+    int reserve(size_t count) {
+        if (cap_ >= count) return 0;
+        if (p_) {
+            if (int rc = hx_drain(drain_)) return rc;
+            HX_CHECK(free_mem(p_));
+            p_ = nullptr; cap_ = 0;
+        }
+        HX_CHECK(alloc_mem((void**)&p_, count * sizeof(T)));
+        cap_ = count;
+        return 0;
+    }
+    // an allocate-once table: `count` elements copied from the host at the first call (later calls do nothing); a failure leaves it empty
+    int upload_once(const T* host, size_t count) {
+        if (p_) return 0;
+        if (int rc = reserve(count)) return rc;
+        const hipError_t e = hipMemcpy(p_, host, count * sizeof(T), hipMemcpyHostToDevice);
+        if (e != hipSuccess) release();
+        return (int)e;
+    }
+    void release() {
+        if (p_) (void)free_mem(p_);
+        p_ = nullptr; cap_ = 0;
+    }
+
+private:
+    static hipError_t alloc_mem(void** p, size_t bytes) {
+        if constexpr (HOST_FLAGS < 0) return hipMalloc(p, bytes);
+        else return hipHostMalloc(p, bytes, (unsigned)HOST_FLAGS);
+    }
+    static hipError_t free_mem(void* p) {
+        if constexpr (HOST_FLAGS < 0) return hipFree(p);
+        else return hipHostFree(p);
+    }
+    T* p_ = nullptr;
+    size_t cap_ = 0;
+    hexl_ctx* drain_;
+};
+template <class T> using HxDevBuf = HxBuf<T>;
+template <class T, int HOST_FLAGS = (int)hipHostMallocDefault> using HxPinBuf = HxBuf<T, HOST_FLAGS>;
+
 struct hexl_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -69,31 +127,33 @@ struct hexl_ctx {
     hipEvent_t ev_switch = nullptr;    // orders a new stream behind the previous one (capi.hip switch_stream; created at the first switch)
     int num_cu = 0;
     // grow-only device scratch + pinned staging used by the *_host entry points
-    void* d_stage = nullptr;  size_t d_stage_bytes = 0;
-    void* d_shared = nullptr; size_t d_shared_bytes = 0;   // small shared arrays of device-resident callers
-    void* h_stage = nullptr;  size_t h_stage_bytes = 0;
-    void* h_lone = nullptr;   size_t h_lone_bytes = 0;    // COHERENT pinned slabs of the zero-copy lone keyswitch (host_staging.hip keyswitch_host_lone)
+    HxDevBuf<char> d_stage{this};
+    HxDevBuf<char> d_shared{this};                          // small shared arrays of device-resident callers
+    HxPinBuf<char> h_stage{this};
+    // COHERENT (fine-grained) pinned slabs of the zero-copy lone keyswitch, whose host side reads result limbs the RUNNING kernel has just
+    // published (host_staging.hip keyswitch_host_lone). The staging pipeline's slabs stay default: with coherent ones its copy-engine
+    // transfers ran a third slower (worksize 128: 13.4 k against 21 k keyswitch/s through the C++ API)
+    HxPinBuf<char, (int)hipHostMallocCoherent> h_lone{this};
     uint32_t lone_epoch = 0;                                // zero-copy lone keyswitches so far (their completion words carry it)
     // host-pointer pipeline: copy streams + events (created lazily), see run_pipeline() in host_staging.hip
     hipStream_t s_up = nullptr, s_down = nullptr;
     hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_down[2] = {nullptr, nullptr};
-    void* d_meta = nullptr;   size_t d_meta_bytes = 0;     // dyadic per-(item,modulus) constants
-    void* d_ntt_redo = nullptr; size_t d_ntt_redo_bytes = 0; // N = 32768 standalone NTT: polynomials left to the integer butterflies (ntt.hip k_ntt_redo_*)
-    void* d_ntt_tab = nullptr; size_t d_ntt_tab_bytes = 0;  // standalone NTT fast path: violation counters + derived double tables
+    HxDevBuf<char> d_meta{this};                            // dyadic per-(item,modulus) constants
+    HxDevBuf<u32> d_ntt_redo{this};                         // N = 32768 standalone NTT: polynomials left to the integer butterflies (ntt.hip k_ntt_redo_*)
+    HxDevBuf<char> d_ntt_tab{this};                         // standalone NTT fast path: violation counters + derived double tables
     uint32_t ntt_seq = 0;                                   // launches so far (selects the violation counter)
     // "these tables are not Shoup tables" hints from the fast-path kernels to the host (ntt.hip NttHint): four pinned words
-    unsigned long long *h_ntt_hint = nullptr, *d_ntt_hint = nullptr;
+    HxPinBuf<unsigned long long, (int)hipHostMallocMapped> h_ntt_hint{this};
+    unsigned long long* d_ntt_hint = nullptr;               // the device's address of h_ntt_hint
     unsigned long long* ntt_hint_word = nullptr; unsigned long long ntt_hint_tag = 0;   // of the launch being set up
     const uint32_t* ntt_clear_viol = nullptr;               // hinted route: the integer kernel clears the hint when this counter is 0
     char name[256] = {0};
 };
 
-// grow-only device buffer of *cap units of `unit` bytes. Before the old buffer is released everything that may still read it has to
-// finish: the context's stream for a context's buffers (ctx given), the whole device for a plan's (ctx == nullptr: lanes on the
-// plan's auxiliary streams use them)
-int hx_grow_device(void** p, size_t* cap, size_t need, size_t unit, hexl_ctx* ctx);
-inline int hx_reserve_device(hexl_ctx* ctx, void** p, size_t* cur, size_t need) { return hx_grow_device(p, cur, need, 1, ctx); }
-int hx_reserve_pinned(hexl_ctx* ctx, void** p, size_t* cur, size_t need, bool coherent = false);
+inline int hx_drain(hexl_ctx* ctx) {
+    HX_CHECK(ctx ? hipStreamSynchronize(ctx->stream) : hipDeviceSynchronize());
+    return 0;
+}
 void hx_pin_own_thread();    // a host thread of the library (copy pool, unpack lane) asks for the NUMA node of the devices in use (capi.hip)
 // ring dimensions: 1024..16384 as the reference (keyswitch) / 16384 (NTT); 32768 is beyond its envelope
 inline bool hx_supported_ntt_n(u64 n) { return n == 1024 || n == 2048 || n == 4096 || n == 8192 || n == 16384 || n == 32768; }
@@ -136,9 +196,10 @@ struct hexl_ks_plan {
     hexl_ctx* ctx = nullptr;
     u32 n = 0, logn = 0, L = 0, K = 0, rns = 0;
     std::vector<u64> moduli;
-    KsModulus* d_mods = nullptr;      // [K]
-    u64* d_tables = nullptr;          // [K][4][n]: roots, precon, inv_roots(HEXL idx), inv_precon
-    u64* d_keys = nullptr;            // [L][L+1][2][n] in forward-output ("B") order
+    // device memory of the plan: every buffer is an HxDevBuf (the plan-wide drain rule: the whole device) and goes with the plan
+    HxDevBuf<KsModulus> d_mods;       // [K]
+    HxDevBuf<u64> d_tables;           // [K][4][n]: roots, precon, inv_roots(HEXL idx), inv_precon
+    HxDevBuf<u64> d_keys;             // [L][L+1][2][n] in forward-output ("B") order
     u32 int_loge = 5;                 // elements-per-thread exponent of the integer kernels (fixes that B order)
     bool have_keys = false;
     // FP64 path (all moduli < 2^52): same tables / keys as centred doubles
@@ -152,21 +213,21 @@ struct hexl_ks_plan {
     unsigned char tier[16] = {};
     bool mixed = false;
     u32 f64_loge = 4;                 // elements-per-thread exponent of the FP64 kernels (fixes the keys' B order)
-    KsModF64* d_mods_f64 = nullptr;   // [K]
-    double* d_tables_f64 = nullptr;   // [K][4][n]
-    double* d_keys_f64 = nullptr;     // [L][L+1][2][n]
-    double* d_keys_x = nullptr;       // the same keys in the B order of the slot-major pipeline's geometry (keyswitch_x.hip)
+    HxDevBuf<KsModF64> d_mods_f64;    // [K]
+    HxDevBuf<double> d_tables_f64;    // [K][4][n]
+    HxDevBuf<double> d_keys_f64;      // [L][L+1][2][n]
+    HxDevBuf<double> d_keys_x;        // the same keys in the B order of the slot-major pipeline's geometry (keyswitch_x.hip)
     u32 x_loge = 5;                   // ... whose elements-per-thread exponent this is
     // scratch for `cap` keyswitches per lane; two lanes (aux streams) work on alternating chunks so that kernels
     // of different kinds -- FP64-bound transforms and the HBM-bound multiply-accumulate -- share the chip and one
     // chunk's ragged last wave of workgroups is filled by the other's
-    u64* d_scratch = nullptr;         // [lanes][cap * scratch_words * n]
-    size_t cap = 0;
+    HxDevBuf<u64> d_scratch;          // [lanes][cap * scratch_words * n] (grow-only: hx_ks_reserve_scratch)
+    size_t cap = 0;                   // instances per lane d_scratch has room for
     hipStream_t aux[HX_KS_MAX_LANES] = {};
     hipEvent_t ev_start = nullptr, ev_done[HX_KS_MAX_LANES] = {};
-    u32* d_flag = nullptr;            // two device words + their pinned host mirrors: [0] the kernels' input-range flag (HEXL_W_RANGE), [1] HEXL_KS_VALIDATE's (HEXL_E_RANGE)
-    u32* h_flag = nullptr;
-    double* d_keys_nat = nullptr;     // N = 16384 FP64 plans: the keys as centred doubles in NATURAL order (latency path, keyswitch_lat.hip)
+    HxDevBuf<u32> d_flag;             // two device words + their pinned host mirrors: [0] the kernels' input-range flag (HEXL_W_RANGE), [1] HEXL_KS_VALIDATE's (HEXL_E_RANGE)
+    HxPinBuf<u32> h_flag;
+    HxDevBuf<double> d_keys_nat;      // N = 16384 FP64 plans: the keys as centred doubles in NATURAL order (latency path, keyswitch_lat.hip)
     bool x_skip = false;              // slot-major lazy kernels: moduli within LAZY_SKIP_MAX_RATIO of each other -> c_d and s' enter the
                                       // transforms without a range reduction (keyswitch_x.hip SKIP variants; HEXL_KSX_SKIP=0 turns it off)
     bool overwrite_result = false;    // host-pointer path, (b, d)-major FP64 kernels: write `result` instead of accumulating into it
@@ -178,26 +239,20 @@ struct hexl_ks_plan {
     hipStream_t cur = nullptr;        // stream the chunk being launched goes to
     u64* cur_scratch = nullptr;
     // CKKS level operations (ckks_ops.hip), all allocated at first use
-    KsRescaleF64* d_rescale = nullptr;   // [16][16]: row l = constants of the rescale that drops limb l (filled at its first call)
+    HxDevBuf<KsRescaleF64> d_rescale; // [16][16]: row l = constants of the rescale that drops limb l (filled at its first call)
     u32 rescale_levels = 0;           // bit l: row l is filled
-    double* d_rs_s = nullptr;         // rescale scratch: s for rs_cap (instance, component) pairs, n doubles each (grow-only)
-    size_t rs_cap = 0;
-    u64* d_rot_t = nullptr;           // rotate: sigma_g(c1) of one slice of rot_cap instances, [rot_cap][L][n] (grow-only)
-    size_t rot_cap = 0;
+    HxDevBuf<double> d_rs_s;          // rescale scratch: s of every (instance, component) pair of a chunk, n doubles each (grow-only)
+    HxDevBuf<u64> d_rot_t;            // rotate: sigma_g(c1) of one slice of instances, [slice][L][n] (grow-only)
     // baby-step/giant-step linear transform (keyswitch_f64.hip hx_launch_linear_transform_bsgs), both grow-only
-    double* d_bsgs_b = nullptr;       // baby store: [n_baby][chunk][2][L+1][n] multiply-accumulate outputs in B order; bsgs_b_cap counts
-    size_t bsgs_b_cap = 0;            // (baby step, instance) slices of 2 (L + 1) n doubles
-    u64* d_bsgs_t = nullptr;          // one giant step's inner sum t_j: [bsgs_t_cap][2][L][n] canonical words
-    size_t bsgs_t_cap = 0;
+    HxDevBuf<double> d_bsgs_b;        // baby store: [n_baby][chunk][2][L+1][n] multiply-accumulate outputs in B order
+    HxDevBuf<u64> d_bsgs_t;           // one giant step's inner sum t_j: [chunk][2][L][n] canonical words
     // device-side encode / decode (ckks_encode.hip), all allocated at first use
-    double* d_emb_roots = nullptr;    // [2n][2]: zeta^t = exp(i pi t / n) as (re, im), computed in long double and rounded once
-    u32* d_emb_perm = nullptr;        // [n/2]: slot k held by position p of the embedding FFT's bit-reversed side (5^k = 4 bitrev(p) + 1 mod 2n)
-    double* d_garner = nullptr;       // [16][16][2]: row i, column j < i = (q_j^-1 mod q_i centred, fl(./q_i)): Garner's constants for every prefix
-    double* d_enc_coeffs = nullptr;   // real coefficients of enc_coeffs_cap instances, n doubles each (grow-only; rlwe.hip: the small samples)
-    size_t enc_coeffs_cap = 0;
-    u64* d_enc_words = nullptr;       // coefficient-form limbs of enc_words_cap (instance, limb) polynomials, n words each (grow-only; rlwe.hip:
+    HxDevBuf<double> d_emb_roots;     // [2n][2]: zeta^t = exp(i pi t / n) as (re, im), computed in long double and rounded once
+    HxDevBuf<u32> d_emb_perm;         // [n/2]: slot k held by position p of the embedding FFT's bit-reversed side (5^k = 4 bitrev(p) + 1 mod 2n)
+    HxDevBuf<double> d_garner;        // [16][16][2]: row i, column j < i = (q_j^-1 mod q_i centred, fl(./q_i)): Garner's constants for every prefix
+    HxDevBuf<double> d_enc_coeffs;    // real coefficients of a chunk's instances, n doubles each (grow-only; rlwe.hip: the small samples)
+    HxDevBuf<u64> d_enc_words;        // coefficient-form limbs of a chunk's (instance, limb) polynomials, n words each (grow-only; rlwe.hip:
                                       // NTT_i of an encryption's error)
-    size_t enc_words_cap = 0;
 };
 
 // launcher prototypes implemented per translation unit
@@ -264,6 +319,7 @@ int hx_launch_encode(hexl_ks_plan*, u64* d_out, const double* d_coeffs, const do
 int hx_launch_decode(hexl_ks_plan*, double* d_coeffs, double* d_slots, const u64* d_in, size_t count, u32 n_limbs, double scale);
 // instances per chunk of the encode scratch (d_enc_coeffs, d_enc_words): 256 at n = 16384 and the same number of coefficients at every other n
 inline size_t hx_enc_chunk(const hexl_ks_plan* p) { return (size_t(256) << 14) >> p->logn; }
+inline size_t hx_enc_chunk_of(const hexl_ks_plan* p, size_t count) { return count < hx_enc_chunk(p) ? count : hx_enc_chunk(p); }
 // the sampler, symmetric encryption and decryption (rlwe.hip); arguments checked by their entry points (hexl_sample, hexl_rlwe_encrypt,
 // hexl_rlwe_decrypt). The small kinds and the error of an encryption pass through d_enc_coeffs / d_enc_words in chunks of hx_enc_chunk.
 int hx_launch_sample(hexl_ks_plan*, u64* d_out, int kind, const u32* seed, u64 stream, u64 first, size_t count, u32 n_limbs);
@@ -291,6 +347,55 @@ static inline bool hx_ranges_overlap(const void* a, size_t abytes, const void* b
 }
 // instances of a batch that go into one scratch chunk
 static inline size_t hx_ks_chunk_of(const hexl_ks_plan* p, size_t batch) { return batch < hx_ks_chunk(p) ? batch : hx_ks_chunk(p); }
+// the plan's keyswitch scratch for chunks of `chunk` instances on every lane (keyswitch.hip; keeps hexl_ks_plan::cap)
+int hx_ks_reserve_scratch(hexl_ks_plan* p, size_t chunk);
+// f(first, nb) for every chunk of `count` instances, in order; stops at the first status that is not 0
+template <class F>
+static inline int hx_for_chunks(size_t count, size_t chunk, F f) {
+    for (size_t c0 = 0; c0 < count; c0 += chunk)
+        if (int rc = f(c0, count - c0 < chunk ? count - c0 : chunk)) return rc;
+    return 0;
+}
+// the forward reduction period every one of the first n_limbs limbs shares, else -1 (the kernels built with LAZY = -1 look it up per limb)
+static inline int hx_level_tier(const hexl_ks_plan* p, u32 n_limbs) {
+    for (u32 i = 1; i < n_limbs; ++i)
+        if (p->tier[i] != p->tier[0]) return -1;
+    return p->tier[0];
+}
+
+// ---- the argument checks of the plan-level entry points (DESIGN.md 4.7 "Host scaffold"); all of them decide HEXL_E_BADARG ----
+constexpr size_t HX_MAX_GRID = 0x7fffffffu;      // workgroups of one launch (x dimension)
+static inline bool hx_in_range(u64 v, u64 lo, u64 hi) { return v >= lo && v <= hi; }
+// FP64 plan of a ring dimension the workgroup transforms exist for (1024 ... 32768) ...
+static inline bool hx_f64_plan_ok(const hexl_ks_plan* p) { return p && p->use_f64 && p->logn >= 10 && p->logn <= 15; }
+// ... and lo <= n_limbs <= hi
+static inline bool hx_f64_plan_ok(const hexl_ks_plan* p, u64 n_limbs, u64 lo, u64 hi) { return hx_f64_plan_ok(p) && hx_in_range(n_limbs, lo, hi); }
+// *bytes = the size of [count][comps][limbs][n] 64-bit words (or doubles); false when it does not fit a size_t
+static inline bool hx_words_bytes(size_t count, u64 comps, u64 limbs, u64 n, size_t* bytes) {
+    const size_t per = size_t(comps) * limbs * n * sizeof(u64);
+    if (per && count > SIZE_MAX / per) return false;
+    *bytes = count * per;
+    return true;
+}
+// one workgroup per (instance, limb) -- the workgroup transforms: the launch fits
+static inline bool hx_wg_grid_ok(size_t count, u64 limbs) { return count <= HX_MAX_GRID / limbs; }
+// The word-wise kernels (k_pt_mul, k_ct_lincomb, the rlwe.hip kernels; with 512-word pieces the k_galois_c0_pt family): HX_WW_THREADS
+// lanes and one workgroup per (instance, limb, piece of 2^log_chunk words). The kernels read constants of their own, tied to these
+// by a static_assert beside each.
+constexpr u32 HX_WW_THREADS = 256, HX_WW_LOG_CHUNK = 10;
+static inline size_t hx_ww_grid(const hexl_ks_plan* p, size_t count, u64 limbs, u32 log_chunk = HX_WW_LOG_CHUNK) {
+    return count * limbs * (p->n >> log_chunk);
+}
+static inline bool hx_ww_grid_ok(const hexl_ks_plan* p, size_t count, u64 limbs) { return count <= HX_MAX_GRID / hx_ww_grid(p, 1, limbs); }
+// The plaintext operand of a batched call: one for all instances (pt_batch == 1) or one per instance (pt_batch == batch); anything else
+// is refused. stride: 1 per instance, 0 shared; bytes: what the call reads of it (per_bytes each; nothing for an empty batch).
+struct HxPtBatch { u32 stride = 0; size_t bytes = 0; };
+static inline bool hx_pt_batch(size_t pt_batch, size_t batch, size_t per_bytes, HxPtBatch* pb) {
+    if (pt_batch != 1 && pt_batch != batch) return false;
+    pb->stride = pt_batch == batch ? 1u : 0u;
+    pb->bytes = (batch ? pt_batch : 0) * per_bytes;
+    return true;
+}
 
 // The <LOGN, LOGE, LAZY> instantiations of the FP64 (b, d)-major kernels and of the kernels built on their geometry (rescale):
 // f(<LOGN>, <LOGE>, <LAZY>) for ring dimension 2^logn and forward reduction period `lazy` (f64_arith.hpp: 0 = strict, < 0 = looked up

@@ -208,8 +208,8 @@ static int run_pipeline(hexl_ctx* c, size_t batch, const PipeShape& sh,
     constexpr size_t HOUT = 4;
     const size_t out_slab = (S * (sh.in_place ? sh.in1 : sh.out1) + 255) & ~size_t(255);
     const size_t dset = in_slab + (sh.in_place ? 0 : out_slab);
-    rc = hx_reserve_device(c, &c->d_stage, &c->d_stage_bytes, 2 * dset);
-    if (!rc) rc = hx_reserve_pinned(c, &c->h_stage, &c->h_stage_bytes, 2 * in_slab + HOUT * out_slab);
+    rc = c->d_stage.reserve(2 * dset);
+    if (!rc) rc = c->h_stage.reserve(2 * in_slab + HOUT * out_slab);
     if (rc) return rc;
     // Sub-batch sizes: S each, but from 64 objects up the window OPENS with S/4 and S/2 and CLOSES with S/2 and S/4: the first upload +
     // kernels + download and the last unpack are exposed (nothing to overlap with), and they shrink with their sub-batch -- in steady
@@ -226,9 +226,9 @@ static int run_pipeline(hexl_ctx* c, size_t batch, const PipeShape& sh,
         for (size_t t : tail) { sub_first.push_back(at); sub_cnt.push_back(t); at += t; }
     }
     const size_t nsub = sub_first.size();
-    auto h_in = [&](size_t k) { return (char*)c->h_stage + (k & 1) * in_slab; };
-    auto d_in = [&](size_t k) { return (char*)c->d_stage + (k & 1) * dset; };
-    auto h_out = [&](size_t k) { return (char*)c->h_stage + 2 * in_slab + (k % HOUT) * out_slab; };
+    auto h_in = [&](size_t k) { return c->h_stage + (k & 1) * in_slab; };
+    auto d_in = [&](size_t k) { return c->d_stage + (k & 1) * dset; };
+    auto h_out = [&](size_t k) { return c->h_stage + 2 * in_slab + (k % HOUT) * out_slab; };
     auto d_out = [&](size_t k) { return sh.in_place ? d_in(k) + sh.shared : d_in(k) + in_slab; };
     if (nsub == 1) {
         // one sub-batch: nothing to overlap with -- one stream, one synchronisation, the unpack on the calling thread
@@ -312,9 +312,9 @@ static int payload_kind(std::initializer_list<std::pair<const void* const*, size
 static int shared_to_device(hexl_ctx* c, const void* src, size_t bytes, int slot, const void** out) {
     if (on_device(src)) { *out = src; return 0; }
     const size_t quarter = (bytes + 255) & ~size_t(255);
-    int rc = hx_reserve_device(c, &c->d_shared, &c->d_shared_bytes, 4 * quarter);
+    int rc = c->d_shared.reserve(4 * quarter);
     if (rc) return rc;
-    char* dst = (char*)c->d_shared + slot * quarter;
+    char* dst = c->d_shared + slot * quarter;
     HX_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
     *out = dst;
     return 0;
@@ -389,7 +389,7 @@ extern "C" int hexl_dyadic_multiply_host(hexl_ctx* c, uint64_t* const* h_out, co
             } else {
                 std::vector<u64> mods(cnt * n_moduli);
                 for (size_t k = 0; k < cnt; ++k) memcpy(&mods[k * n_moduli], h_moduli[i + k], mod1);
-                if (int rc = hx_reserve_device(c, &c->d_shared, &c->d_shared_bytes, mods.size() * 8)) return rc;
+                if (int rc = c->d_shared.reserve(mods.size() * 8)) return rc;
                 HX_CHECK(hipMemcpy(c->d_shared, mods.data(), mods.size() * 8, hipMemcpyHostToDevice));
                 dm = c->d_shared;
             }
@@ -443,9 +443,9 @@ static int keyswitch_host_lone(hexl_ks_plan* p, uint64_t* const* h_results, cons
     auto stamp = [&](const char* what) { trace(what, -1); };
     const size_t in_bytes = (batch * tt + 255) & ~size_t(255), out_bytes = (batch * rs + 255) & ~size_t(255);
     const size_t nflag = batch * 2 * L * 4;                                   // one word per quarter limb
-    int rc = hx_reserve_pinned(c, &c->h_lone, &c->h_lone_bytes, in_bytes + out_bytes + 256 + nflag * sizeof(u32), true);
+    int rc = c->h_lone.reserve(in_bytes + out_bytes + 256 + nflag * sizeof(u32));
     if (rc) return rc;
-    char* h_in = (char*)c->h_lone;
+    char* h_in = c->h_lone;
     char* h_out = h_in + in_bytes;
     u32* flag = (u32*)(h_out + out_bytes);
     u32* done = flag + 64;

@@ -414,8 +414,11 @@ int hx_ks_lanes() {
 static size_t lane_bytes(const hexl_ks_plan* p) { return size_t(hx_ks_lanes()) * scratch_words(p) * p->n * sizeof(u64); }   // per instance of a chunk, every lane
 size_t hexl_ks_scratch_bytes(const hexl_ks_plan* p, size_t batch) { return hx_ks_chunk_of(p, batch) * lane_bytes(p); }
 // the plan's scratch for chunks of `chunk` instances (grow-only; lanes of earlier launches may still work in the old one)
-static int reserve_scratch(hexl_ks_plan* p, size_t chunk) {
-    return hx_grow_device((void**)&p->d_scratch, &p->cap, chunk, lane_bytes(p), nullptr);
+int hx_ks_reserve_scratch(hexl_ks_plan* p, size_t chunk) {
+    const size_t lane_words = lane_bytes(p) / sizeof(u64);
+    const int rc = p->d_scratch.reserve(chunk * lane_words);
+    p->cap = p->d_scratch.capacity() / lane_words;                // (0 after a failed allocation)
+    return rc;
 }
 
 // HEXL_KS_VALIDATE=1: the keyswitch precondition (every t_target / result word below its modulus), checked on the device
@@ -475,7 +478,7 @@ int hx_launch_keyswitch(hexl_ks_plan* p, u64* d_result, const u64* d_t_target, s
     const bool one_lane = lane_env != HX_KNOB_UNSET ? lane_env == 1 : (p->use_f64 && !hx_ks_x_applies(p, chunk));
     const bool two_lanes = !ev && batch >= 64 && !one_lane && !(p->use_f64 && batch <= chunk);
     if (two_lanes && batch <= chunk) chunk = (batch + 1) / 2;
-    if (int rc = reserve_scratch(p, chunk)) return rc;
+    if (int rc = hx_ks_reserve_scratch(p, chunk)) return rc;
     if (!p->aux[0]) {
         for (int l = 0; l < hx_ks_lanes(); ++l) {
             HX_CHECK(hipStreamCreateWithFlags(&p->aux[l], hipStreamNonBlocking));
@@ -550,16 +553,13 @@ int hx_launch_mulrelin_x(hexl_ks_plan* p, u64* d_out, const u64* d_a, const u64*
 int hx_launch_multiply_relinearize(hexl_ks_plan* p, u64* d_out, const u64* d_a, const u64* d_b, size_t batch) {
     if (!batch) return 0;
     if (!p->have_keys) return HEXL_E_NOKEYS;
-    if (!p->use_f64 || p->logn < 10 || p->logn > 15) return HEXL_E_BADARG;   // see hx_launch_mulrelin_x
+    if (!hx_f64_plan_ok(p)) return HEXL_E_BADARG;                            // see hx_launch_mulrelin_x
     const size_t chunk = hx_ks_chunk_of(p, batch);
-    if (int rc = reserve_scratch(p, chunk)) return rc;
+    if (int rc = hx_ks_reserve_scratch(p, chunk)) return rc;
     p->cur = p->ctx->stream;
     p->cur_scratch = p->d_scratch;
     const size_t per = 2 * p->L * p->n;
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-        const size_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-        int rc = hx_launch_mulrelin_x(p, d_out + b0 * per, d_a + b0 * per, d_b + b0 * per, nb);
-        if (rc) return rc;
-    }
-    return 0;
+    return hx_for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
+        return hx_launch_mulrelin_x(p, d_out + b0 * per, d_a + b0 * per, d_b + b0 * per, nb);
+    });
 }

@@ -762,18 +762,11 @@ struct HoistRun {
     size_t chunk, per;                                             // instances per chunk; words of one ciphertext, 2 L n
 
     HoistRun(hexl_ks_plan* p, size_t chunk_) : p0(p), c(p->ctx), chunk(chunk_), per(2 * size_t(p->L) * p->n) {}
-    // p0's keyswitch scratch, grown as hx_launch_keyswitch grows it (hexl_ks_scratch_bytes(p, 1): one instance of a chunk, every lane)
+    // p0's keyswitch scratch, grown as hx_launch_keyswitch grows it
     int reserve() {
-        if (int rc = hx_grow_device((void**)&p0->d_scratch, &p0->cap, chunk, hexl_ks_scratch_bytes(p0, 1), nullptr)) return rc;
+        if (int rc = hx_ks_reserve_scratch(p0, chunk)) return rc;
         p0->cur = c->stream;
         p0->cur_scratch = p0->d_scratch;
-        return 0;
-    }
-    // f(b0, nb) for every chunk of `batch` instances
-    template <class F>
-    int chunks(size_t batch, F f) const {
-        for (size_t b0 = 0; b0 < batch; b0 += chunk)
-            if (int rc = f(b0, batch - b0 < chunk ? batch - b0 : chunk)) return rc;
         return 0;
     }
     // steps 1-2 on d_c1 = component 1 of nb ciphertexts [nb][2][L][n], read in place, into u
@@ -809,7 +802,7 @@ int hx_launch_rotate_hoisted(hexl_ks_plan* const* plans, const u64* galois_elts,
     HoistRun run(p0, hx_ks_chunk_of(p0, batch));
     if (int rc = run.reserve()) return rc;
     const size_t half = run.per / 2;
-    return run.chunks(batch, [&](size_t b0, size_t nb) {
+    return hx_for_chunks(batch, run.chunk, [&](size_t b0, size_t nb) {
         const u64* ct = d_ct + b0 * run.per;
         if (int rc = run.up(ct + half, nb)) return rc;
         for (size_t r = 0; r < n_rot; ++r) {
@@ -836,14 +829,14 @@ int hx_launch_linear_transform(hexl_ks_plan* const* plans, const u64* galois_elt
     // the stream orders it behind the previous call's kernels that read the table
     std::vector<HxLtRot> table(n_rot);
     for (size_t r = 0; r < n_rot; ++r) table[r] = HxLtRot{d_pts[r], galois_elts[r]};
-    if (int rc = hx_reserve_device(c, &c->d_shared, &c->d_shared_bytes, n_rot * sizeof(HxLtRot))) return rc;
+    if (int rc = c->d_shared.reserve(n_rot * sizeof(HxLtRot))) return rc;
     HX_CHECK(hipMemcpyAsync(c->d_shared, table.data(), n_rot * sizeof(HxLtRot), hipMemcpyHostToDevice, c->stream));
     const size_t half = run.per / 2;
-    return run.chunks(batch, [&](size_t b0, size_t nb) {
+    return hx_for_chunks(batch, run.chunk, [&](size_t b0, size_t nb) {
         const u64* ct = d_ct + b0 * run.per;
         u64* out = d_out + b0 * run.per;
         if (int rc = run.up(ct + half, nb)) return rc;
-        if (int rc = hx_launch_galois_c0_pt(p0, out, ct, (const HxLtRot*)c->d_shared, n_rot, d_pt_identity, nb)) return rc;
+        if (int rc = hx_launch_galois_c0_pt(p0, out, ct, (const HxLtRot*)c->d_shared.get(), n_rot, d_pt_identity, nb)) return rc;
         for (size_t r = 0; r < n_rot; ++r)
             if (int rc = run.mac(plans[r], (u32)galois_elts[r], r ? KSF_MAC_PT_ACC : KSF_MAC_PT_FIRST, d_pts[r], nullptr, nb)) return rc;
         return run.down(p0, out, nb);
@@ -884,8 +877,8 @@ int hx_launch_linear_transform_bsgs(hexl_ks_plan* p0, hexl_ks_plan* const* baby_
     hexl_ctx* c = run.c;
     const size_t chunk = run.chunk, half = run.per / 2, slice = 2 * (size_t(p0->L) + 1) * p0->n;
     if (n_baby)
-        if (int rc = hx_grow_device((void**)&p0->d_bsgs_b, &p0->bsgs_b_cap, n_baby * chunk, slice * sizeof(double), nullptr)) return rc;
-    if (int rc = hx_grow_device((void**)&p0->d_bsgs_t, &p0->bsgs_t_cap, chunk, run.per * sizeof(u64), nullptr)) return rc;
+        if (int rc = p0->d_bsgs_b.reserve(n_baby * chunk * slice)) return rc;
+    if (int rc = p0->d_bsgs_t.reserve(chunk * run.per)) return rc;
     // the per-call tables, row after row: what the c0 kernel walks (plaintext, Galois element) and what the sum kernel walks (plaintext,
     // baby slice). Pageable sources, stream-ordered behind the previous call's readers, as hx_launch_linear_transform's table
     std::vector<HxLtRot> rots;
@@ -904,13 +897,13 @@ int hx_launch_linear_transform_bsgs(hexl_ks_plan* p0, hexl_ks_plan* const* baby_
     const size_t total = off[n_giant] = rots.size();
     static_assert(sizeof(HxLtRot) == 16 && sizeof(HxBsgsTerm) == 16, "the two tables share one 16-byte-aligned reservation");
     if (total) {
-        if (int rc = hx_reserve_device(c, &c->d_shared, &c->d_shared_bytes, total * (sizeof(HxLtRot) + sizeof(HxBsgsTerm)))) return rc;
+        if (int rc = c->d_shared.reserve(total * (sizeof(HxLtRot) + sizeof(HxBsgsTerm)))) return rc;
         HX_CHECK(hipMemcpyAsync(c->d_shared, rots.data(), total * sizeof(HxLtRot), hipMemcpyHostToDevice, c->stream));
-        HX_CHECK(hipMemcpyAsync((HxLtRot*)c->d_shared + total, terms.data(), total * sizeof(HxBsgsTerm), hipMemcpyHostToDevice, c->stream));
+        HX_CHECK(hipMemcpyAsync((HxLtRot*)c->d_shared.get() + total, terms.data(), total * sizeof(HxBsgsTerm), hipMemcpyHostToDevice, c->stream));
     }
-    const HxLtRot* d_rots = (const HxLtRot*)c->d_shared;
+    const HxLtRot* d_rots = (const HxLtRot*)c->d_shared.get();
     const HxBsgsTerm* d_terms = (const HxBsgsTerm*)(d_rots + total);
-    return run.chunks(batch, [&](size_t b0, size_t nb) {
+    return hx_for_chunks(batch, run.chunk, [&](size_t b0, size_t nb) {
         const u64* ct = d_ct + b0 * run.per;
         u64* out = d_out + b0 * run.per;
         if (total) {

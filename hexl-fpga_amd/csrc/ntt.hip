@@ -653,7 +653,7 @@ static bool fast_path_enabled() {
 
 static int ensure_ntt_hint(hexl_ctx* ctx) {                        // NttHint: four pinned, device-visible words
     if (!ctx->h_ntt_hint) {
-        HX_CHECK(hipHostMalloc((void**)&ctx->h_ntt_hint, 4 * sizeof(unsigned long long), hipHostMallocMapped));
+        if (int rc = ctx->h_ntt_hint.reserve(4)) return rc;
         memset(ctx->h_ntt_hint, 0, 4 * sizeof(unsigned long long));
         HX_CHECK(hipHostGetDevicePointer((void**)&ctx->d_ntt_hint, ctx->h_ntt_hint, 0));
     }
@@ -665,11 +665,11 @@ static int reserve_tables(hexl_ctx* ctx, u64 n, NttPrep* pr) {
     constexpr size_t HEAD = 256;                                                        // 64 violation counters
     const size_t bytes = HEAD + 2 * n * sizeof(double);
     const void* before = ctx->d_ntt_tab;
-    int rc = hx_reserve_device(ctx, &ctx->d_ntt_tab, &ctx->d_ntt_tab_bytes, bytes);
+    int rc = ctx->d_ntt_tab.reserve(bytes);
     if (rc) return rc;
     if (ctx->d_ntt_tab != before) HX_CHECK(hipMemsetAsync(ctx->d_ntt_tab, 0, HEAD, ctx->stream));
-    u32* counters = (u32*)ctx->d_ntt_tab;
-    pr->w = (double*)((char*)ctx->d_ntt_tab + HEAD);
+    u32* counters = (u32*)ctx->d_ntt_tab.get();
+    pr->w = (double*)(ctx->d_ntt_tab + HEAD);
     pr->wp = pr->w + n;
     if (int rch = ensure_ntt_hint(ctx)) return rch;
     const u32 seq = ctx->ntt_seq++;
@@ -684,8 +684,8 @@ static int reserve_tables(hexl_ctx* ctx, u64 n, NttPrep* pr) {
 // dedicated integer kernels
 static unsigned redo_grid(unsigned fast_grid) { return fast_grid < 32u ? fast_grid : 32u; }
 static int reserve_redo(hexl_ctx* ctx, size_t batch, NttPrep* pr) {
-    int rc = hx_reserve_device(ctx, &ctx->d_ntt_redo, &ctx->d_ntt_redo_bytes, (batch + 1) * sizeof(u32));
-    pr->redo = (u32*)ctx->d_ntt_redo;
+    int rc = ctx->d_ntt_redo.reserve(batch + 1);
+    pr->redo = ctx->d_ntt_redo;
     return rc;
 }
 // the preparation as a launch of its own, in front of a transform kernel that does not do it itself

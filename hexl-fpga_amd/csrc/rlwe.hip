@@ -17,6 +17,7 @@ using hxf::Mod;
 
 constexpr u32 RL_THREADS = 256, RL_LOG_CHUNK = 10;      // 1024 words of one polynomial per workgroup, four per lane
 static_assert(RL_THREADS * 4 == 1u << RL_LOG_CHUNK, "a workgroup covers its chunk exactly");
+static_assert(RL_THREADS == HX_WW_THREADS && RL_LOG_CHUNK == HX_WW_LOG_CHUNK, "hx_ww_grid counts these workgroups");
 typedef unsigned long long rl_u2 __attribute__((ext_vector_type(2)));
 
 struct SampleArgs {
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(RL_THREADS) void k_rlwe_decrypt(DecryptArgs a) {
 }
 
 // ---- launchers ----
-static dim3 rl_grid(const hexl_ks_plan* p, size_t count, u32 n_limbs) { return dim3((u32)(count * n_limbs * (p->n >> RL_LOG_CHUNK))); }
+static dim3 rl_grid(const hexl_ks_plan* p, size_t count, u32 n_limbs) { return dim3((u32)hx_ww_grid(p, count, n_limbs)); }
 
 // the small values of instances first ... first + nb - 1 into the plan's d_enc_coeffs (grown by the caller), as doubles
 static int launch_small(hexl_ks_plan* p, int kind, const hxs::Seed& seed, u64 stream, u64 first, size_t nb) {
@@ -170,22 +171,20 @@ int hx_launch_sample(hexl_ks_plan* p, u64* d_out, int kind, const u32* seed, u64
         hipLaunchKernelGGL(k_sample_uniform, rl_grid(p, count, n_limbs), dim3(RL_THREADS), 0, p->ctx->stream, a);
         return (int)hipGetLastError();
     }
-    const size_t n = p->n, chunk = count < hx_enc_chunk(p) ? count : hx_enc_chunk(p);
-    if (int rc = hx_grow_device((void**)&p->d_enc_coeffs, &p->enc_coeffs_cap, chunk, n * sizeof(double), nullptr)) return rc;
-    for (size_t c0 = 0; c0 < count; c0 += chunk) {
-        const size_t nb = count - c0 < chunk ? count - c0 : chunk;
+    const size_t n = p->n, chunk = hx_enc_chunk_of(p, count);
+    if (int rc = p->d_enc_coeffs.reserve(chunk * n)) return rc;
+    return hx_for_chunks(count, chunk, [&](size_t c0, size_t nb) {
         if (int rc = launch_small(p, kind, sd, stream, first + c0, nb)) return rc;
-        if (int rc = hx_launch_encode(p, d_out + c0 * n_limbs * n, p->d_enc_coeffs, nullptr, nb, n_limbs, 1.0)) return rc;
-    }
-    return 0;
+        return hx_launch_encode(p, d_out + c0 * n_limbs * n, p->d_enc_coeffs, nullptr, nb, n_limbs, 1.0);
+    });
 }
 
 int hx_launch_rlwe_encrypt(hexl_ks_plan* p, u64* d_out, const u64* d_pt, bool per_instance, const u64* d_secret, const u32* seed,
                            u64 stream, u64 first, size_t count, u32 n_limbs) {
     if (!count) return 0;
-    const size_t n = p->n, chunk = count < hx_enc_chunk(p) ? count : hx_enc_chunk(p), per = size_t(n_limbs) * n;
-    if (int rc = hx_grow_device((void**)&p->d_enc_coeffs, &p->enc_coeffs_cap, chunk, n * sizeof(double), nullptr)) return rc;
-    if (int rc = hx_grow_device((void**)&p->d_enc_words, &p->enc_words_cap, chunk * n_limbs, n * sizeof(u64), nullptr)) return rc;
+    const size_t n = p->n, chunk = hx_enc_chunk_of(p, count), per = size_t(n_limbs) * n;
+    if (int rc = p->d_enc_coeffs.reserve(chunk * n)) return rc;
+    if (int rc = p->d_enc_words.reserve(chunk * per)) return rc;
     EncryptArgs a{};
     a.mods = p->d_mods_f64;
     a.e = p->d_enc_words;
@@ -195,17 +194,15 @@ int hx_launch_rlwe_encrypt(hexl_ks_plan* p, u64* d_out, const u64* d_pt, bool pe
     a.logn = p->logn;
     a.L = n_limbs;
     a.pt_stride = per_instance ? 1u : 0u;
-    for (size_t c0 = 0; c0 < count; c0 += chunk) {
-        const size_t nb = count - c0 < chunk ? count - c0 : chunk;
+    return hx_for_chunks(count, chunk, [&](size_t c0, size_t nb) {
         if (int rc = launch_small(p, hxs::KIND_CBD21, a.seed, stream, first + c0, nb)) return rc;
         if (int rc = hx_launch_encode(p, p->d_enc_words, p->d_enc_coeffs, nullptr, nb, n_limbs, 1.0)) return rc;
         a.out = d_out + c0 * 2 * per;
         a.pt = d_pt ? d_pt + (per_instance ? c0 * per : 0) : nullptr;
         a.first = first + c0;
         hipLaunchKernelGGL(k_rlwe_encrypt, rl_grid(p, nb, n_limbs), dim3(RL_THREADS), 0, p->ctx->stream, a);
-        if (int rc = (int)hipGetLastError()) return rc;
-    }
-    return 0;
+        return (int)hipGetLastError();
+    });
 }
 
 int hx_launch_rlwe_decrypt(hexl_ks_plan* p, u64* d_out, const u64* d_ct, const u64* d_secret, size_t count, u32 n_components, u32 n_limbs) {
@@ -218,19 +215,16 @@ int hx_launch_rlwe_decrypt(hexl_ks_plan* p, u64* d_out, const u64* d_ct, const u
 }
 
 // ---- entry points of include/hexl_mi355x.h ----
-constexpr size_t RL_MAX_GRID = 0x7fffffffu;      // workgroups of one launch (x dimension)
-// FP64 plan of a ring dimension the transforms are built for, 1 <= n_limbs <= K, and `count` instances of `comps` components whose
-// bytes and workgroups fit
-static bool rl_plan_ok(const hexl_ks_plan* p, size_t count, u64 comps, u64 n_limbs) {
-    if (!p || !p->use_f64 || p->logn < 10 || p->logn > 15 || n_limbs < 1 || n_limbs > p->K) return false;
-    const size_t per = size_t(n_limbs) * p->n * sizeof(u64) * comps;
-    return count <= SIZE_MAX / per && count <= RL_MAX_GRID / (n_limbs * (p->n >> RL_LOG_CHUNK));
+// the checks of hexl_internal.hpp for 1 <= n_limbs <= K; *bytes = those of `count` instances of `comps` components, whose workgroups fit
+static bool rl_plan_ok(const hexl_ks_plan* p, size_t count, u64 comps, u64 n_limbs, size_t* bytes) {
+    return p && hx_f64_plan_ok(p, n_limbs, 1, p->K) && hx_words_bytes(count, comps, n_limbs, p->n, bytes) && hx_ww_grid_ok(p, count, n_limbs);
 }
 static bool rl_index_ok(u64 first, size_t count) { return first <= hxs::MAX_INDEX && count <= hxs::MAX_INDEX - first; }
 
 extern "C" int hexl_sample(hexl_ks_plan* p, uint64_t* d_out, int kind, const uint32_t seed[8], uint64_t stream, uint64_t first,
                            size_t count, uint64_t n_limbs) {
-    if (!d_out || !seed || !rl_plan_ok(p, count, 1, n_limbs) || !rl_index_ok(first, count)) return HEXL_E_BADARG;
+    size_t bytes;
+    if (!d_out || !seed || !rl_plan_ok(p, count, 1, n_limbs, &bytes) || !rl_index_ok(first, count)) return HEXL_E_BADARG;
     if (kind != HEXL_SAMPLE_UNIFORM && kind != HEXL_SAMPLE_TERNARY && kind != HEXL_SAMPLE_CBD21) return HEXL_E_BADARG;
     HX_CHECK(hipSetDevice(p->ctx->device));
     return hx_launch_sample(p, d_out, kind, seed, stream, first, count, (u32)n_limbs);
@@ -238,22 +232,24 @@ extern "C" int hexl_sample(hexl_ks_plan* p, uint64_t* d_out, int kind, const uin
 
 extern "C" int hexl_rlwe_encrypt(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_pt, size_t pt_batch, const uint64_t* d_secret,
                                  const uint32_t seed[8], uint64_t stream, uint64_t first, size_t count, uint64_t n_limbs) {
-    if (!d_out || !d_secret || !seed || !rl_plan_ok(p, count, 2, n_limbs) || !rl_index_ok(first, count)) return HEXL_E_BADARG;
-    if (d_pt && pt_batch != 1 && pt_batch != count) return HEXL_E_BADARG;
-    const size_t per = size_t(n_limbs) * p->n * sizeof(u64), bytes = count * 2 * per;
+    size_t bytes;
+    if (!d_out || !d_secret || !seed || !rl_plan_ok(p, count, 2, n_limbs, &bytes) || !rl_index_ok(first, count)) return HEXL_E_BADARG;
+    const size_t per = size_t(n_limbs) * p->n * sizeof(u64);
+    HxPtBatch pt;
+    if (d_pt && !hx_pt_batch(pt_batch, count, per, &pt)) return HEXL_E_BADARG;
     if (hx_ranges_overlap(d_out, bytes, d_secret, per)) return HEXL_E_BADARG;
-    if (d_pt && hx_ranges_overlap(d_out, bytes, d_pt, (count ? pt_batch : 0) * per)) return HEXL_E_BADARG;
+    if (d_pt && hx_ranges_overlap(d_out, bytes, d_pt, pt.bytes)) return HEXL_E_BADARG;
     HX_CHECK(hipSetDevice(p->ctx->device));
-    return hx_launch_rlwe_encrypt(p, d_out, d_pt, d_pt && pt_batch == count, d_secret, seed, stream, first, count, (u32)n_limbs);
+    return hx_launch_rlwe_encrypt(p, d_out, d_pt, pt.stride != 0, d_secret, seed, stream, first, count, (u32)n_limbs);
 }
 
 extern "C" int hexl_rlwe_decrypt(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_ct, const uint64_t* d_secret, size_t count,
                                  uint64_t n_components, uint64_t n_limbs) {
-    if (!d_out || !d_ct || !d_secret || (n_components != 2 && n_components != 3)) return HEXL_E_BADARG;
-    if (!rl_plan_ok(p, count, n_components, n_limbs)) return HEXL_E_BADARG;
-    const size_t per = size_t(n_limbs) * p->n * sizeof(u64);
-    if (hx_ranges_overlap(d_out, count * per, d_ct, count * n_components * per) || hx_ranges_overlap(d_out, count * per, d_secret, per))
-        return HEXL_E_BADARG;
+    if (!d_out || !d_ct || !d_secret || !hx_in_range(n_components, 2, 3)) return HEXL_E_BADARG;
+    size_t ct_bytes;
+    if (!rl_plan_ok(p, count, n_components, n_limbs, &ct_bytes)) return HEXL_E_BADARG;
+    const size_t per = size_t(n_limbs) * p->n * sizeof(u64), bytes = ct_bytes / n_components;
+    if (hx_ranges_overlap(d_out, bytes, d_ct, ct_bytes) || hx_ranges_overlap(d_out, bytes, d_secret, per)) return HEXL_E_BADARG;
     HX_CHECK(hipSetDevice(p->ctx->device));
     return hx_launch_rlwe_decrypt(p, d_out, d_ct, d_secret, count, (u32)n_components, (u32)n_limbs);
 }

@@ -88,18 +88,15 @@ static int run_rns_ntt(hexl_ks_plan* p, const RnsNttArgs& a, bool inverse) {
 
 int hx_launch_rns_ntt(hexl_ks_plan* p, u64* d_out, const u64* d_in, size_t count, u32 n_limbs, bool inverse) {
     if (!count) return 0;
-    // the schedule every limb in use admits; LAZY = -1 (per-limb lookup) when they differ, as hx_launch_rescale chooses
-    int lazy = p->tier[0];
-    for (u32 i = 1; i < n_limbs; ++i)
-        if (p->tier[i] != p->tier[0]) lazy = -1;
     const RnsNttArgs a{p->d_mods_f64, p->d_tables_f64, d_in, d_out, (u32)count, n_limbs, hx_tiermap(p)};
-    return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return run_rns_ntt<N, E, Z>(p, a, inverse); });
+    return hx_with_f64_geom(p->logn, hx_level_tier(p, n_limbs), [&](auto N, auto E, auto Z) { return run_rns_ntt<N, E, Z>(p, a, inverse); });
 }
 
 // ---- plaintext multiply ----
 constexpr u32 PT_THREADS = 256, PT_VECS = 2;
 constexpr u32 PT_LOG_CHUNK = 10;    // 1024 words of one polynomial per workgroup (the smallest ring): PT_VECS 16-byte vectors per lane
 static_assert(PT_THREADS * PT_VECS * 2 == 1u << PT_LOG_CHUNK, "a workgroup covers its chunk exactly");
+static_assert(PT_THREADS == HX_WW_THREADS && PT_LOG_CHUNK == HX_WW_LOG_CHUNK, "hx_ww_grid counts these workgroups");
 
 struct PtMulArgs {
     const KsModF64* mods;       // [K]
@@ -150,14 +147,11 @@ __global__ __launch_bounds__(PT_THREADS) void k_pt_mul(PtMulArgs a) {
     }
 }
 
-// workgroups of one hexl_multiply_plain launch
-static size_t pt_mul_grid(const hexl_ks_plan* p, size_t batch, u64 n_limbs) { return batch * n_limbs * (p->n >> PT_LOG_CHUNK); }
-
 int hx_launch_multiply_plain(hexl_ks_plan* p, u64* d_out, const u64* d_ct, const u64* d_pt, size_t batch, u32 n_components, u32 n_limbs,
                              bool per_instance, bool accumulate) {
     if (!batch) return 0;
     const PtMulArgs a{p->d_mods_f64, d_ct, d_pt, d_out, p->logn, n_limbs, per_instance ? 1u : 0u};
-    const dim3 grid((u32)pt_mul_grid(p, batch, n_limbs)), block(PT_THREADS);
+    const dim3 grid((u32)hx_ww_grid(p, batch, n_limbs)), block(PT_THREADS);
     auto launch = [&](auto NC) {
         constexpr int NCOMP = decltype(NC)::value;
         if (accumulate) hipLaunchKernelGGL((k_pt_mul<NCOMP, true>), grid, block, 0, p->ctx->stream, a);
@@ -273,7 +267,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_ct_lincomb(LcArgs a) {
 
 static int hx_launch_ct_lincomb(hexl_ks_plan* p, const LcArgs& a, size_t batch, u32 n_terms, u32 n_components) {
     if (!batch) return 0;
-    const dim3 grid((u32)pt_mul_grid(p, batch, a.L)), block(PT_THREADS);
+    const dim3 grid((u32)hx_ww_grid(p, batch, a.L)), block(PT_THREADS);
     auto comps = [&](auto NT) {
         constexpr int T = decltype(NT)::value;
         if (n_components == 1) hipLaunchKernelGGL((k_ct_lincomb<T, 1>), grid, block, 0, p->ctx->stream, a);
@@ -294,17 +288,12 @@ static int hx_launch_ct_lincomb(hexl_ks_plan* p, const LcArgs& a, size_t batch, 
 }
 
 // ---- entry points of include/hexl_mi355x.h (beside their launchers, as in ckks_ops.hip: the CPU staging model needs no stubs for them) ----
-// FP64 plan of a ring dimension the transforms are built for, 1 <= n_limbs <= K (the special prime included)
-static bool rns_plan_ok(const hexl_ks_plan* p, u64 n_limbs) {
-    return p && p->use_f64 && p->logn >= 10 && p->logn <= 15 && n_limbs >= 1 && n_limbs <= p->K;
-}
-constexpr size_t RNS_MAX_GRID = 0x7fffffffu;     // workgroups of one launch (x dimension)
-
+// The checks are hexl_internal.hpp's; every limb count here may reach K (the special prime included).
 static int rns_ntt(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_in, size_t count, uint64_t n_limbs, bool inverse) {
-    if (!d_out || !d_in || !rns_plan_ok(p, n_limbs)) return HEXL_E_BADARG;
-    const size_t per = size_t(n_limbs) * p->n * sizeof(u64);
-    if (count > SIZE_MAX / per || count > RNS_MAX_GRID / n_limbs) return HEXL_E_BADARG;
-    if (d_out != d_in && hx_ranges_overlap(d_out, count * per, d_in, count * per)) return HEXL_E_BADARG;   // in place, or apart
+    if (!p || !d_out || !d_in || !hx_f64_plan_ok(p, n_limbs, 1, p->K)) return HEXL_E_BADARG;
+    size_t bytes;
+    if (!hx_words_bytes(count, 1, n_limbs, p->n, &bytes) || !hx_wg_grid_ok(count, n_limbs)) return HEXL_E_BADARG;
+    if (d_out != d_in && hx_ranges_overlap(d_out, bytes, d_in, bytes)) return HEXL_E_BADARG;   // in place, or apart
     HX_CHECK(hipSetDevice(p->ctx->device));
     return hx_launch_rns_ntt(p, d_out, d_in, count, (u32)n_limbs, inverse);
 }
@@ -319,30 +308,31 @@ extern "C" int hexl_rns_ntt_inv(hexl_ks_plan* p, uint64_t* d_out, const uint64_t
 
 extern "C" int hexl_multiply_plain(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_ct, const uint64_t* d_pt, size_t batch,
                                    uint64_t n_components, uint64_t n_limbs, size_t pt_batch, int accumulate) {
-    if (!d_out || !d_ct || !d_pt || !rns_plan_ok(p, n_limbs)) return HEXL_E_BADARG;
-    if (n_components < 1 || n_components > 3) return HEXL_E_BADARG;
-    if (pt_batch != 1 && pt_batch != batch) return HEXL_E_BADARG;
-    const size_t pt_per = size_t(n_limbs) * p->n * sizeof(u64), per = pt_per * n_components;
-    if (batch > SIZE_MAX / per || batch > RNS_MAX_GRID / (n_limbs * (p->n >> PT_LOG_CHUNK))) return HEXL_E_BADARG;
-    const size_t bytes = batch * per, pt_bytes = (batch ? pt_batch : 0) * pt_per;
-    if (hx_ranges_overlap(d_out, bytes, d_pt, pt_bytes)) return HEXL_E_BADARG;
+    if (!p || !d_out || !d_ct || !d_pt || !hx_f64_plan_ok(p, n_limbs, 1, p->K) || !hx_in_range(n_components, 1, 3)) return HEXL_E_BADARG;
+    size_t bytes;
+    HxPtBatch pt;
+    if (!hx_pt_batch(pt_batch, batch, size_t(n_limbs) * p->n * sizeof(u64), &pt)) return HEXL_E_BADARG;
+    if (!hx_words_bytes(batch, n_components, n_limbs, p->n, &bytes) || !hx_ww_grid_ok(p, batch, n_limbs)) return HEXL_E_BADARG;
+    if (hx_ranges_overlap(d_out, bytes, d_pt, pt.bytes)) return HEXL_E_BADARG;
     // in place over the ciphertext only when the output is written, not accumulated into (d_out would be both addend and factor)
     if ((d_out != d_ct || accumulate) && hx_ranges_overlap(d_out, bytes, d_ct, bytes)) return HEXL_E_BADARG;
     HX_CHECK(hipSetDevice(p->ctx->device));
-    return hx_launch_multiply_plain(p, d_out, d_ct, d_pt, batch, (u32)n_components, (u32)n_limbs, pt_batch == batch,
-                                    accumulate != 0);
+    return hx_launch_multiply_plain(p, d_out, d_ct, d_pt, batch, (u32)n_components, (u32)n_limbs, pt.stride != 0, accumulate != 0);
 }
 
 extern "C" int hexl_ct_lincomb(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* const* d_cts, const uint64_t* in_limbs,
                                const uint64_t* h_weights, size_t n_terms, const uint64_t* d_pt, size_t pt_batch, const uint64_t* h_const,
                                size_t batch, uint64_t n_components, uint64_t n_limbs) {
-    if (!d_out || !d_cts || n_terms < 1 || n_terms > LC_MAX_TERMS || !rns_plan_ok(p, n_limbs) || n_limbs > LC_MAX_LIMBS) return HEXL_E_BADARG;
-    if (n_components < 1 || n_components > 3) return HEXL_E_BADARG;
-    if (d_pt && pt_batch != 1 && pt_batch != batch) return HEXL_E_BADARG;
-    const size_t poly = size_t(p->n) * sizeof(u64), pt_per = size_t(n_limbs) * poly;
+    if (!p || !d_out || !d_cts || !hx_in_range(n_terms, 1, LC_MAX_TERMS) || !hx_f64_plan_ok(p, n_limbs, 1, p->K) || n_limbs > LC_MAX_LIMBS)
+        return HEXL_E_BADARG;
+    if (!hx_in_range(n_components, 1, 3)) return HEXL_E_BADARG;
+    const size_t poly = size_t(p->n) * sizeof(u64);
+    HxPtBatch pt;
+    if (d_pt && !hx_pt_batch(pt_batch, batch, size_t(n_limbs) * poly, &pt)) return HEXL_E_BADARG;
     // the largest term has K limbs: if that size fits, every other one does
-    if (batch > SIZE_MAX / (size_t(p->K) * poly * n_components) || batch > RNS_MAX_GRID / (n_limbs * (p->n >> PT_LOG_CHUNK))) return HEXL_E_BADARG;
-    const size_t bytes = batch * n_components * pt_per;
+    size_t bytes;
+    if (!hx_words_bytes(batch, n_components, p->K, p->n, &bytes) || !hx_ww_grid_ok(p, batch, n_limbs)) return HEXL_E_BADARG;
+    bytes = bytes / p->K * n_limbs;
     LcArgs a{};
     for (size_t t = 0; t < n_terms; ++t) {
         const u64 lt = in_limbs ? in_limbs[t] : n_limbs;
@@ -353,7 +343,7 @@ extern "C" int hexl_ct_lincomb(hexl_ks_plan* p, uint64_t* d_out, const uint64_t*
         a.ct[t] = d_cts[t];
         a.in_limbs[t] = (u32)lt;
     }
-    if (d_pt && hx_ranges_overlap(d_out, bytes, d_pt, (batch ? pt_batch : 0) * pt_per)) return HEXL_E_BADARG;
+    if (d_pt && hx_ranges_overlap(d_out, bytes, d_pt, pt.bytes)) return HEXL_E_BADARG;
     for (u64 i = 0; i < n_limbs; ++i) {
         const u64 q = p->moduli[i];
         for (size_t t = 0; t < n_terms; ++t) {
@@ -372,7 +362,7 @@ extern "C" int hexl_ct_lincomb(hexl_ks_plan* p, uint64_t* d_out, const uint64_t*
     a.out = d_out;
     a.logn = p->logn;
     a.L = (u32)n_limbs;
-    a.pt_stride = d_pt && pt_batch == batch ? 1u : 0u;
+    a.pt_stride = pt.stride;
     a.has_cst = h_const ? 1u : 0u;
     HX_CHECK(hipSetDevice(p->ctx->device));
     return hx_launch_ct_lincomb(p, a, batch, (u32)n_terms, (u32)n_components);
