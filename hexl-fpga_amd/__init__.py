@@ -71,6 +71,8 @@ C_ABI = {
     "hexl_sample": [_vp, _vp, _i, _vp, _u64, _u64, _sz, _u64],
     "hexl_rlwe_encrypt": [_vp, _vp, _vp, _sz, _vp, _vp, _u64, _u64, _sz, _u64],
     "hexl_rlwe_decrypt": [_vp, _vp, _vp, _vp, _sz, _u64, _u64],
+    "hexl_ks_set_keys_device": [_vp, _vp],
+    "hexl_ks_gen_keys": [_vp, _vp, _i, _u64, _vp, _vp, _u64, _u64],
     "hexl_ks_scratch_bytes": [_vp, _sz],
     "hexl_ntt_fwd_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64],
     "hexl_ntt_inv_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64, _u64, _u64],
@@ -117,6 +119,7 @@ def lib() -> ctypes.CDLL:
 
 
 SAMPLE_UNIFORM, SAMPLE_TERNARY, SAMPLE_CBD21 = 1, 2, 3            # include/hexl_mi355x.h HEXL_SAMPLE_*
+KEY_FROM_POLY, KEY_FROM_SQUARE, KEY_FROM_GALOIS = 0, 1, 2         # include/hexl_mi355x.h HEXL_KEY_FROM_*
 
 
 def seed_words(seed=None):
@@ -249,6 +252,29 @@ class KeySwitchPlan:
         self._keys = [np.ascontiguousarray(k, dtype=np.uint64) for k in keys]
         arr = (_vp * len(self._keys))(*[k.ctypes.data for k in self._keys])
         _check(lib().hexl_ks_set_keys(self.h, arr), "hexl_ks_set_keys")
+
+    def set_keys_device(self, keys):
+        """keys: device tensor [L][2][K][n] in the layout of set_keys (what a key-shaped rlwe_encrypt writes); one kernel on the context's
+        stream lays it into every copy the plan holds -- no host synchronisation, and a plan in use may be re-keyed"""
+        _check(lib().hexl_ks_set_keys_device(self.h, _ptr(keys)), "hexl_ks_set_keys_device")
+
+    def gen_keys(self, secret, from_kind: int, galois_elt: int = 1, from_poly=None, seed=None, stream: int = 0, first: int = 0) -> bytes:
+        """the switching key from s' to `secret` ([K][n], NTT form at all K limbs) generated into the plan: s' = from_poly [K][n]
+        (KEY_FROM_POLY), secret^2 (KEY_FROM_SQUARE) or secret(X^galois_elt) (KEY_FROM_GALOIS). Word for word rlwe_encrypt(count = L,
+        n_limbs = K, pt[d][i] = [i == d] (P mod q_i) s'_i) -> set_keys; consumes polynomials first ... first + L - 1 of (seed, stream).
+        Returns the seed's bytes (None = os.urandom)."""
+        words, raw = seed_words(seed)
+        _check(lib().hexl_ks_gen_keys(self.h, _ptr(secret), from_kind, galois_elt, None if from_poly is None else _ptr(from_poly), words,
+                                      stream, first), "hexl_ks_gen_keys")
+        return raw
+
+    def gen_relin_keys(self, secret, seed=None, stream: int = 0, first: int = 0) -> bytes:
+        """the relinearisation key of `secret` (multiply_relinearize)"""
+        return self.gen_keys(secret, KEY_FROM_SQUARE, seed=seed, stream=stream, first=first)
+
+    def gen_galois_keys(self, secret, g: int, seed=None, stream: int = 0, first: int = 0) -> bytes:
+        """the key rotate / the hoisted family need for the Galois element g"""
+        return self.gen_keys(secret, KEY_FROM_GALOIS, galois_elt=g, seed=seed, stream=stream, first=first)
 
     def keyswitch(self, result, t_target, batch: int):
         _check(lib().hexl_keyswitch(self.h, _ptr(result), _ptr(t_target), batch), "hexl_keyswitch")
@@ -423,5 +449,5 @@ def lt_bsgs_scratch_bytes(plan, n_baby: int, batch: int) -> int:
 from .host_api import HexlFpga  # noqa: E402  (mirror of host/inc/hexl-fpga.h)
 
 __all__ = ["Context", "KeySwitchPlan", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform",
-           "linear_transform_bsgs", "lt_bsgs_scratch_bytes", "C_ABI", "SAMPLE_UNIFORM", "SAMPLE_TERNARY", "SAMPLE_CBD21", "seed_words",
+           "linear_transform_bsgs", "lt_bsgs_scratch_bytes", "C_ABI", "SAMPLE_UNIFORM", "SAMPLE_TERNARY", "SAMPLE_CBD21", "KEY_FROM_POLY", "KEY_FROM_SQUARE", "KEY_FROM_GALOIS", "seed_words",
            "LIB_PATH", "ROOT"]

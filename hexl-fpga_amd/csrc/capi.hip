@@ -125,19 +125,30 @@ extern "C" int hexl_dyadic_multiply(hexl_ctx* c, uint64_t* out, const uint64_t* 
 // ------------------------------------------------------------------------------- K4 plan
 // elements-per-thread exponent of the keyswitch kernels (must match run_chunk<> / run_chunk_f64<> dispatch)
 static u32 ks_loge(u32 logn, bool f64) { return logn <= 10 ? 4 : (f64 && logn == 14 ? 4 : 5); }
-static u32 ks_idxB(u32 logn, u32 loge, u32 r, u32 tid) {
-    const u32 P = (logn + loge - 1) / loge, KL = logn - (P - 1) * loge;
-    const u32 WB = logn - loge < 6 ? logn - loge : 6;          // mirrors Geom::idxB (ntt_core.hpp)
-    const u32 grp = ((tid >> WB) << (loge - KL + WB)) + ((r >> KL) << WB) + (tid & ((1u << WB) - 1));
-    return (grp << KL) + (r & ((1u << KL) - 1));
-}
-// perm[pos] = natural coefficient index stored at position pos of a "B order" ([r][tid]) limb
-static std::vector<u32> ks_perm(u32 logn, u32 loge) {
-    const u32 n = 1u << logn, E = 1u << loge, T = n >> loge;
-    std::vector<u32> perm(n);
-    for (u32 r = 0; r < E; ++r)
-        for (u32 t = 0; t < T; ++t) perm[r * T + t] = ks_idxB(logn, loge, r, t);
+// perm[pos] = the caller's word index stored at position pos of a limb in that order (key_layout.hpp); empty: natural order
+static std::vector<u32> ks_perm(u32 n, const hxk::Order o) {
+    std::vector<u32> perm(o.loge ? n : 0);
+    for (u32 pos = 0; pos < (u32)perm.size(); ++pos) perm[pos] = hxk::src_of(o, pos);
     return perm;
+}
+
+// The copies of the keys this plan holds, in the order hexl_ks_set_keys has always filled them (hexl_internal.hpp HxKeyCopy):
+//   integer plans   d_keys: B order of the integer kernels' geometry, the word beside its Shoup factor -- FP64 plans never run those
+//                   kernels and hold no integer copy (22 MB of device memory and a host pass per key set for nothing)
+//   FP64 plans      d_keys_f64: centred doubles in the B order of the (b, d)-major kernels
+//   d_keys_x        ... in the B order of the slot-major pipeline's geometry. N = 32768: every transform of that pipeline is two
+//                   16384-point halves (keyswitch_x.hip k_ksh_*), so NTT-domain block h of a key row is kept in the B order of THAT geometry
+//   d_keys_nat      ... in natural order (latency path)
+int hx_ks_key_copies(hexl_ks_plan* p, HxKeyCopy out[HX_KEY_MAX_COPIES]) {
+    int c = 0;
+    if (!p->use_f64) out[c++] = {p->d_keys.get(), {p->logn, p->int_loge}, true};
+    else out[c++] = {p->d_keys_f64.get(), {p->logn, p->f64_loge}, false};
+    if (p->d_keys_x) {
+        p->x_loge = p->logn == 14 ? hx_ks_x_loge() : 4;
+        out[c++] = {p->d_keys_x.get(), {p->logn < 15 ? p->logn : 14, p->logn < 15 ? p->x_loge : 4}, false};
+    }
+    if (p->d_keys_nat) out[c++] = {p->d_keys_nat.get(), {p->logn, 0}, false};
+    return c;
 }
 
 extern "C" int hexl_ks_plan_create(hexl_ctx* c, uint64_t n, uint64_t L, uint64_t K, uint64_t rns, uint64_t kcc,
@@ -322,37 +333,23 @@ extern "C" int hexl_ks_set_keys(hexl_ks_plan* p, const uint64_t* const* h_keys) 
                 }
             }
     };
-    auto upload_centred = [&](double* d_keys, const std::vector<u32>& perm) {
-        std::vector<double> h(words);
-        relayout(perm, [&](size_t base, u64 j, u64 v, u64 q) { h[base + j] = hx_centre(v, q); });
-        HX_CHECK(hipMemcpy(d_keys, h.data(), words * sizeof(double), hipMemcpyHostToDevice));
-        return 0;
-    };
-    // integer kernels: [d][slot][k][0] = key mod q, [..][1] = floor(that * 2^64 / q); FP64 plans never run them and hold
-    // no integer copy (22 MB of device memory and a host pass per key set for nothing)
-    if (!p->use_f64) {
-        std::vector<u64> h(2 * words);
-        relayout(ks_perm(p->logn, p->int_loge), [&](size_t base, u64 j, u64 v, u64 q) {
-            h[2 * base + j] = v;
-            h[2 * base + n + j] = (u64)(((u128)v << 64) / q);
-        });
-        HX_CHECK(hipMemcpy(p->d_keys, h.data(), h.size() * sizeof(u64), hipMemcpyHostToDevice));
-    } else if (int rc = upload_centred(p->d_keys_f64, ks_perm(p->logn, p->f64_loge))) {   // the same limbs as centred doubles
-        return rc;
-    }
-    if (p->d_keys_x) {                                            // ... in the B order of the slot-major pipeline's geometry
-        p->x_loge = p->logn == 14 ? hx_ks_x_loge() : 4;
-        std::vector<u32> permx = ks_perm(p->logn < 15 ? p->logn : 14, p->logn < 15 ? p->x_loge : 4);
-        if (p->logn == 15) {
-            // N = 32768: every transform of the slot-major pipeline is two 16384-point halves (keyswitch_x.hip k_ksh_*); NTT-domain block h
-            // of a key row is kept in the B order of THAT geometry
-            permx.resize(n);
-            for (u32 j = 0; j < (1u << 14); ++j) permx[(1u << 14) + j] = (1u << 14) + permx[j];
+    HxKeyCopy copies[HX_KEY_MAX_COPIES];
+    const int n_copies = hx_ks_key_copies(p, copies);
+    for (int c = 0; c < n_copies; ++c) {
+        const std::vector<u32> perm = ks_perm((u32)n, copies[c].order);
+        if (copies[c].shoup) {                                    // [d][slot][k][0] = key mod q, [..][1] = floor(that * 2^64 / q)
+            std::vector<u64> h(2 * words);
+            relayout(perm, [&](size_t base, u64 j, u64 v, u64 q) {
+                h[2 * base + j] = v;
+                h[2 * base + n + j] = (u64)(((u128)v << 64) / q);
+            });
+            HX_CHECK(hipMemcpy(copies[c].dst, h.data(), h.size() * sizeof(u64), hipMemcpyHostToDevice));
+        } else {                                                  // the same limbs as centred doubles
+            std::vector<double> h(words);
+            relayout(perm, [&](size_t base, u64 j, u64 v, u64 q) { h[base + j] = hx_centre(v, q); });
+            HX_CHECK(hipMemcpy(copies[c].dst, h.data(), words * sizeof(double), hipMemcpyHostToDevice));
         }
-        if (int rc = upload_centred(p->d_keys_x, permx)) return rc;
     }
-    if (p->d_keys_nat)                                            // natural order (latency path)
-        if (int rc = upload_centred(p->d_keys_nat, {})) return rc;
     p->have_keys = true;
     return 0;
 }

@@ -12,6 +12,7 @@
 
 #include "../../include/hexl_mi355x.h"
 #include "f64_arith.hpp"
+#include "key_layout.hpp"
 
 typedef uint64_t u64;
 typedef uint32_t u32;
@@ -326,6 +327,18 @@ int hx_launch_sample(hexl_ks_plan*, u64* d_out, int kind, const u32* seed, u64 s
 int hx_launch_rlwe_encrypt(hexl_ks_plan*, u64* d_out, const u64* d_pt, bool per_instance, const u64* d_secret, const u32* seed, u64 stream,
                            u64 first, size_t count, u32 n_limbs);
 int hx_launch_rlwe_decrypt(hexl_ks_plan*, u64* d_out, const u64* d_ct, const u64* d_secret, size_t count, u32 n_components, u32 n_limbs);
+// the error of nb <= chunk encryptions, NTT_i(CBD21 polynomial first + b) at n_limbs limbs, into d_enc_words (reserved by the caller)
+int hx_launch_rlwe_error(hexl_ks_plan*, const u32* seed, u64 stream, u64 first, size_t nb, u32 n_limbs);
+// switching keys without a host round trip (keygen.hip); arguments checked by their entry points (hexl_ks_set_keys_device,
+// hexl_ks_gen_keys). HxKeyCopy: one copy of the keys a plan holds -- [L][L + 1][2][n] limbs at `dst`, the n words of a limb in `order`
+// (key_layout.hpp), as centred doubles, or (shoup: the integer kernels' copy) as u64 [limb][2][n] = the word and floor(word 2^64 / q).
+// hx_ks_key_copies (capi.hip) is the ONE list of them: hexl_ks_set_keys fills what it names on the host, the kernels of keygen.hip on
+// the device. It fixes hexl_ks_plan::x_loge, as hexl_ks_set_keys always did.
+struct HxKeyCopy { void* dst; hxk::Order order; bool shoup; };
+constexpr int HX_KEY_MAX_COPIES = 3;
+int hx_ks_key_copies(hexl_ks_plan* p, HxKeyCopy out[HX_KEY_MAX_COPIES]);
+int hx_launch_ks_install(hexl_ks_plan*, const u64* d_keys);
+int hx_launch_ks_gen_keys(hexl_ks_plan*, const u64* d_secret, int from_kind, u32 g, const u64* d_from, const u32* seed, u64 stream, u64 first);
 u32 hx_ks_x_loge();
 // index of coefficient held in register r of thread tid after a forward transform ("B layout")
 u32 hx_idxB(u32 logn, u32 r, u32 tid);
@@ -334,7 +347,7 @@ u32 hx_loge_for(u32 logn);
 
 static inline u64 hx_shoup(u64 y, u64 q) { return (u64)(((u128)(y % q) << 64) / q); }
 // residue v < q as the centred double in (-q/2, q/2] the FP64 kernels work on
-static inline double hx_centre(u64 v, u64 q) { return v > q / 2 ? (double)v - (double)q : (double)v; }
+static inline double hx_centre(u64 v, u64 q) { return hxk::centre(v, q); }
 // nibble i = forward reduction period of limb i (the kernels built with LAZY = -1 look their schedule up here)
 static inline unsigned long long hx_tiermap(const hexl_ks_plan* p) {
     unsigned long long m = 0;

@@ -40,10 +40,7 @@ __device__ __forceinline__ RlWhere rl_where(u32 logn, u32 L) {
 }
 // the four UNIFORM words j0 ... j0 + 3 (j0 a multiple of 4: one block) of polynomial (c, limb i), canonical, as doubles
 __device__ __forceinline__ void rl_uniform4(double a[4], const hxs::Seed& seed, u64 stream, u64 c, u32 i, u32 logn, u32 j0, const Mod m) {
-    const hxs::Block blk = hxs::chacha20_block(seed, hxs::counter(hxs::KIND_UNIFORM, hxs::uniform_block(c, i, logn, j0)), stream);
-    const double c32 = hxs::mod_c32(m);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) a[k] = hxs::uniform_word(blk, k, c32, m);
+    hxs::uniform4(a, seed, stream, c, i, logn, j0, m);
 }
 __device__ __forceinline__ void rl_store4(u64* dst, const double v[4]) {
     rl_u2 lo, hi;
@@ -179,6 +176,15 @@ int hx_launch_sample(hexl_ks_plan* p, u64* d_out, int kind, const u32* seed, u64
     });
 }
 
+// d_enc_words[nb][n_limbs][n] = NTT_i of the CBD21 polynomials first ... first + nb - 1 of (seed, stream), through d_enc_coeffs; nb is at
+// most a chunk and both buffers have room for it (the caller's reserve)
+int hx_launch_rlwe_error(hexl_ks_plan* p, const u32* seed, u64 stream, u64 first, size_t nb, u32 n_limbs) {
+    hxs::Seed sd;
+    for (int k = 0; k < 8; ++k) sd.k[k] = seed[k];
+    if (int rc = launch_small(p, hxs::KIND_CBD21, sd, stream, first, nb)) return rc;
+    return hx_launch_encode(p, p->d_enc_words, p->d_enc_coeffs, nullptr, nb, n_limbs, 1.0);
+}
+
 int hx_launch_rlwe_encrypt(hexl_ks_plan* p, u64* d_out, const u64* d_pt, bool per_instance, const u64* d_secret, const u32* seed,
                            u64 stream, u64 first, size_t count, u32 n_limbs) {
     if (!count) return 0;
@@ -195,8 +201,7 @@ int hx_launch_rlwe_encrypt(hexl_ks_plan* p, u64* d_out, const u64* d_pt, bool pe
     a.L = n_limbs;
     a.pt_stride = per_instance ? 1u : 0u;
     return hx_for_chunks(count, chunk, [&](size_t c0, size_t nb) {
-        if (int rc = launch_small(p, hxs::KIND_CBD21, a.seed, stream, first + c0, nb)) return rc;
-        if (int rc = hx_launch_encode(p, p->d_enc_words, p->d_enc_coeffs, nullptr, nb, n_limbs, 1.0)) return rc;
+        if (int rc = hx_launch_rlwe_error(p, seed, stream, first + c0, nb, n_limbs)) return rc;
         a.out = d_out + c0 * 2 * per;
         a.pt = d_pt ? d_pt + (per_instance ? c0 * per : 0) : nullptr;
         a.first = first + c0;

@@ -81,6 +81,15 @@ HX_HD double uniform_word(const Block& b, int k, double c32, const hxf::Mod m) {
     return mod128(b.w[4 * k], b.w[4 * k + 1], b.w[4 * k + 2], b.w[4 * k + 3], c32, m);
 }
 
+// the four UNIFORM words j0 ... j0 + 3 (j0 a multiple of 4: one block, none of it wasted) of polynomial (c, limb i), canonical, as
+// doubles -- what every kernel that draws a mask runs (rlwe.hip k_sample_uniform / k_rlwe_encrypt, keygen.hip k_ks_gen)
+HX_HD void uniform4(double a[4], const Seed& seed, uint64_t stream, uint64_t c, uint32_t i, uint32_t logn, uint32_t j0, const hxf::Mod m) {
+    const Block blk = chacha20_block(seed, counter(KIND_UNIFORM, uniform_block(c, i, logn, j0)), stream);
+    const double c32 = mod_c32(m);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[k] = uniform_word(blk, k, c32, m);
+}
+
 // the two small maps, r one u64 lane
 HX_HD int ternary(uint64_t r) { return (int)(uint64_t)(((unsigned __int128)r * 3u) >> 64) - 1; }
 HX_HD int cbd21(uint64_t r) {

@@ -350,6 +350,8 @@ int hexl_ckks_decode(hexl_ks_plan* plan, double* d_slots, const uint64_t* d_in, 
  * (c0 - c0' = pt - pt'); an encryption and a hexl_sample call that share a triple publish the error. Give every call sequence of one
  * secret its own `stream` (or a fresh seed from the operating system's generator), and advance `first` by `count` between calls that
  * share both. Distinct kinds never collide (the kind is part of the block counter), distinct streams and distinct indices neither.
+ * hexl_ks_gen_keys (below) is such a call: it consumes the UNIFORM and CBD21 polynomials first ... first + L - 1 of its (seed, stream),
+ * exactly as the key-shaped hexl_rlwe_encrypt it replaces -- never give two keys of one secret the same triple.
  *
  * The streams (normative): ChaCha20 in counter mode, the 20-round block function of RFC 8439 on the state
  *   words 0-3 the constants 0x61707865 0x3320646e 0x79622d32 0x6b206574 | words 4-11 seed[0..7] (the caller's 32 bytes as eight
@@ -382,8 +384,9 @@ int hexl_ckks_decode(hexl_ks_plan* plan, double* d_slots, const uint64_t* d_in, 
  * word for word the h_keys layout of hexl_ks_set_keys (key d at d 2 K n, word (k K + i) n + j). With
  *   pt[d][i] = [i == d] (P mod q_i) s'_i     P = the special prime, the plan's modulus K - 1; s' = the key being switched FROM
  * (s^2 for relinearisation, s(X^g) for the Galois key of g), the output is a switching key from s' to s: pt is L calls of
- * hexl_ct_lincomb on NTT(s') with per-limb weights. Download it once and pass the L slices to hexl_ks_set_keys; re-laying a device
- * buffer into a plan without that round trip is not offered. Public-key encryption is hexl_sample + hexl_multiply_plain +
+ * hexl_ct_lincomb on NTT(s') with per-limb weights. hexl_ks_set_keys_device (below) installs such a device buffer into a plan as it
+ * is, and hexl_ks_gen_keys writes that very key straight into the plan without the buffer ever existing: no key has to cross the bus
+ * (a download and hexl_ks_set_keys remain the way to keep a copy on the host). Public-key encryption is hexl_sample + hexl_multiply_plain +
  * hexl_ct_lincomb on a public key made here with d_pt = NULL.
  * Common rules: FP64 plans only (every modulus < 2^52), n = 1024 ... 32768, 1 <= n_limbs <= K (the plan's first n_limbs moduli), no keys
  * needed. Asynchronous on the context's stream; the seed travels by value in the kernels' arguments, so every host array may be
@@ -405,6 +408,51 @@ int hexl_rlwe_encrypt(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_pt,
                       const uint32_t seed[8], uint64_t stream, uint64_t first, size_t count, uint64_t n_limbs);
 int hexl_rlwe_decrypt(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_ct, const uint64_t* d_secret, size_t count,
                       uint64_t n_components, uint64_t n_limbs);
+/* Switching keys without a host round trip. Keys are per plan, and plans are per level and per Galois element: a rotation set keys every
+ * one of its plans with one asynchronous call each, and neither a secret nor a key leaves the device.
+ *
+ * hexl_ks_set_keys_device: hexl_ks_set_keys for keys that are on the device already.
+ *   d_keys: DEVICE [L][2][K][n] in the h_keys layout of hexl_ks_set_keys (key d at d*2*K*n, word (k*K + i)*n + j) -- what a key-shaped
+ *   hexl_rlwe_encrypt writes. Afterwards the plan is word for word the plan hexl_ks_set_keys leaves for the same words.
+ * Runs on every plan hexl_ks_set_keys accepts, integer-kernel plans included. Any 64-bit word is taken and reduced modulo its limb's
+ * modulus, as on the host; only limbs i < L and i = K - 1 are read, as on the host. One kernel on the context's stream reads the
+ * caller's buffer once and writes every copy of the keys the plan holds (centred doubles in the order of each FP64 pipeline; words
+ * beside their Shoup factors for the integer kernels): no host synchronisation, no host staging, no key-sized temporary and no device
+ * memory beyond what hexl_ks_plan_create reserved. d_keys may be reused as soon as the kernel has run (stream order).
+ * Ordering: every keyswitch-family call (hexl_keyswitch, hexl_multiply_relinearize, hexl_rotate, the hoisted and linear-transform calls)
+ * joins the auxiliary lanes it used back into the context's stream before it returns, so this launch is behind every reader of the
+ * old keys queued so far and in front of every reader of the new ones queued later. Re-keying a plan that is in use is therefore
+ * allowed, with no synchronisation: install, launch, install, launch. (hexl_ks_set_keys synchronises the stream instead.)
+ * HEXL_E_BADARG: a null plan or pointer; the plan is left as it was.
+ *
+ * hexl_ks_gen_keys: the switching key from s' to s, generated into the plan. Normative definition: afterwards the plan is word for word
+ * what hexl_ks_set_keys leaves for the output of
+ *   hexl_rlwe_encrypt(count = L, n_limbs = K, pt_batch = L, pt[d][i] = [i == d] (P mod q_i) s'_i, d_secret, seed, stream, first),
+ * P = the plan's modulus K - 1, with
+ *   HEXL_KEY_FROM_POLY     s' = d_from [K][n], NTT form
+ *   HEXL_KEY_FROM_SQUARE   s'_i = s_i . s_i mod q_i: the relinearisation key (hexl_multiply_relinearize)
+ *   HEXL_KEY_FROM_GALOIS   s'_i = the hexl_apply_galois permutation of s_i for galois_elt: the key hexl_rotate and the hoisted family
+ *                          need for that element
+ * d_secret is [K][n]: NTT_i(s) at ALL K limbs (hexl_sample(TERNARY, n_limbs = K)), every word below its modulus. galois_elt and d_from are
+ * ignored where the kind does not use them. The call consumes polynomial indices first ... first + L - 1 of the UNIFORM and CBD21 kinds
+ * of (seed, stream): see the WARNING above. Limbs the plan never reads (L <= i < K - 1 when K > L + 1) are skipped; the streams are
+ * addressed by (polynomial, limb, index), so skipping changes no word.
+ * FP64 plans only (every modulus < 2^52), n = 1024 ... 32768, as hexl_rlwe_encrypt. Asynchronous on the context's stream and ordered
+ * like hexl_ks_set_keys_device; the seed travels by value. Fused: the CBD21 errors of the L keys pass through the plan's encode scratch
+ * as in hexl_rlwe_encrypt, then ONE kernel reads e and s (s' only in the L rows whose plaintext is not zero -- gathered through the
+ * Galois index or squared in registers), draws `a`, forms the canonical c0 = pt + e - a s and stores c0 and `a` as centred doubles at
+ * their place in every copy of the keys. No [L][2][K][n] buffer, no plaintext, no s^2 and no s(X^g) exists in memory.
+ * Device memory, kept in the plan and grow-only, shared with encode / decode / encrypt: L x n doubles and L x K x n words of the encode
+ * scratch (1.9 MiB + 15 MiB at n = 16384, L = 7, K = 8); nothing else is allocated (a first call that grows them waits for the device).
+ * HEXL_E_BADARG: a null plan, secret or seed; d_from null with HEXL_KEY_FROM_POLY; an unknown from_kind; HEXL_KEY_FROM_GALOIS with a
+ * galois_elt that is even or >= 2n; first + L > 2^40; a plan on the integer kernels. A refused call leaves the plan as it was (without
+ * keys, if it had none: HEXL_E_NOKEYS from hexl_keyswitch). */
+int hexl_ks_set_keys_device(hexl_ks_plan* plan, const uint64_t* d_keys);
+#define HEXL_KEY_FROM_POLY   0   /* s' = d_from [K][n], NTT form */
+#define HEXL_KEY_FROM_SQUARE 1   /* s' = s^2: the relinearisation key */
+#define HEXL_KEY_FROM_GALOIS 2   /* s' = s(X^galois_elt): the key hexl_rotate / the hoisted family need for that element */
+int hexl_ks_gen_keys(hexl_ks_plan* plan, const uint64_t* d_secret, int from_kind, uint64_t galois_elt, const uint64_t* d_from,
+                     const uint32_t seed[8], uint64_t stream, uint64_t first);
 /* Arithmetic tier per limb (introspection for logs and tests): tiers[i], i < key_modulus_size, = the forward transforms' range-
  * reduction period modulo q_i on the FP64 path -- 12 / 6 / 3 for q_i <= 2^49 / 2^50 / 2^51 (1 + 2^-7), 0 = every value reduced after
  * every operation (q_i up to 2^52); -1 for every limb of a plan on the integer kernels (a modulus >= 2^52). Every transform runs modulo
