@@ -146,8 +146,6 @@ struct hexl_ctx {
     // "these tables are not Shoup tables" hints from the fast-path kernels to the host (ntt.hip NttHint): four pinned words
     HxPinBuf<unsigned long long, (int)hipHostMallocMapped> h_ntt_hint{this};
     unsigned long long* d_ntt_hint = nullptr;               // the device's address of h_ntt_hint
-    unsigned long long* ntt_hint_word = nullptr; unsigned long long ntt_hint_tag = 0;   // of the launch being set up
-    const uint32_t* ntt_clear_viol = nullptr;               // hinted route: the integer kernel clears the hint when this counter is 0
     char name[256] = {0};
 };
 

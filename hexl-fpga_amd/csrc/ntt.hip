@@ -5,6 +5,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <tuple>
+
 // wave priority by pass of the FP64 forward transforms: the pass in front of the cross-wave barrier at 0, the rest at 1
 // (keyswitch_x.hip has the reasoning; standalone forward NTT +5 % at batch 1024, +3.5 % at batch 4096; the inverse transforms'
 // knob HX_INV_PRIO measured within +-2 % either way and stays off)
@@ -23,6 +25,7 @@
 #include "hexl_internal.hpp"
 #include "ntt_core.hpp"
 #include "ntt_core_f64.hpp"
+#include "ntt_route.hpp"
 
 // (N = 2048 -- 128-thread workgroups of two waves -- measured 3 % slower with the priorities: off there)
 constexpr int ntt_fwd_prio(int logn) { return logn == 11 ? 0 : HX_FWD_PRIO; }
@@ -634,65 +637,6 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ntt_redo_inv(u64* __rest
     }
 }
 
-// HEXL_NTT_HALVES=0: N = 32768 back on the monolithic half-size-exchange kernels (A/B)
-static bool halves_enabled() {
-    static const bool v = hx_knob("HEXL_NTT_HALVES", 1) != 0;
-    return v;
-}
-
-// HEXL_NTT_PERSIST=0: one workgroup per polynomial instead of persistent workgroups with input prefetch
-static bool persist_enabled() {
-    static const bool v = hx_knob("HEXL_NTT_PERSIST", 1) != 0;
-    return v;
-}
-
-static bool fast_path_enabled() {
-    static const bool v = hx_knob("HEXL_NTT_INT", 0) != 1;
-    return v;
-}
-
-static int ensure_ntt_hint(hexl_ctx* ctx) {                        // NttHint: four pinned, device-visible words
-    if (!ctx->h_ntt_hint) {
-        if (int rc = ctx->h_ntt_hint.reserve(4)) return rc;
-        memset(ctx->h_ntt_hint, 0, 4 * sizeof(unsigned long long));
-        HX_CHECK(hipHostGetDevicePointer((void**)&ctx->d_ntt_hint, ctx->h_ntt_hint, 0));
-    }
-    return 0;
-}
-
-// device scratch for the derived tables: a ring of 64 violation counters (one per launch, round robin), then [w | w/p] (n doubles each)
-static int reserve_tables(hexl_ctx* ctx, u64 n, NttPrep* pr) {
-    constexpr size_t HEAD = 256;                                                        // 64 violation counters
-    const size_t bytes = HEAD + 2 * n * sizeof(double);
-    const void* before = ctx->d_ntt_tab;
-    int rc = ctx->d_ntt_tab.reserve(bytes);
-    if (rc) return rc;
-    if (ctx->d_ntt_tab != before) HX_CHECK(hipMemsetAsync(ctx->d_ntt_tab, 0, HEAD, ctx->stream));
-    u32* counters = (u32*)ctx->d_ntt_tab.get();
-    pr->w = (double*)(ctx->d_ntt_tab + HEAD);
-    pr->wp = pr->w + n;
-    if (int rch = ensure_ntt_hint(ctx)) return rch;
-    const u32 seq = ctx->ntt_seq++;
-    pr->viol = counters + (seq & 63);
-    pr->viol_later = counters + ((seq + 32) & 63);
-    pr->n = (u32)n;
-    pr->redo = nullptr;
-    return 0;
-}
-// the launch behind the fast kernel is nearly always EMPTY: 32 workgroups (an empty dispatch of one 141 KiB workgroup per CU measured 4.7 us,
-// 5 % of a 512-polynomial launch); a batch under tables that are not Shoup tables runs there once, then the host hint sends it to the
-// dedicated integer kernels
-static unsigned redo_grid(unsigned fast_grid) { return fast_grid < 32u ? fast_grid : 32u; }
-static int reserve_redo(hexl_ctx* ctx, size_t batch, NttPrep* pr) {
-    int rc = ctx->d_ntt_redo.reserve(batch + 1);
-    pr->redo = ctx->d_ntt_redo;
-    return rc;
-}
-// the preparation as a launch of its own, in front of a transform kernel that does not do it itself
-static int launch_prepare(hexl_ctx* ctx, const u64* roots, const u64* precon, u64 q, const NttPrep& pr) {
-    hipLaunchKernelGGL(k_ntt_prepare, dim3((pr.n + 255) / 256), dim3(256), 0, ctx->stream, roots, precon, q, pr);
-    return (int)hipGetLastError();
-}
 template <int LOGN, int LOGE>
 __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ntt_fwd(u64* __restrict__ x,
                                                                 const u64* __restrict__ roots,
@@ -784,10 +728,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_ntt_inv_ip(u64* __restri
     }
 }
 
-u32 hx_loge_for(u32 logn) {
-    // N = 16384: 16 coefficients per thread x 1024 threads (4 waves/SIMD) measured ~10 % faster than 32 x 512
-    return (logn == 14 || logn <= 10) ? 4 : 5;
-}
+u32 hx_loge_for(u32 logn) { return (u32)ntt_loge((int)logn); }
 
 u32 hx_idxB(u32 logn, u32 r, u32 tid) {
     const u32 loge = hx_loge_for(logn);
@@ -797,155 +738,223 @@ u32 hx_idxB(u32 logn, u32 r, u32 tid) {
     return (grp << KL) + (r & ((1u << KL) - 1));
 }
 
-template <int LOGN, int LOGE>
-static int launch_fwd(hexl_ctx* ctx, u64* x, size_t batch, const u64* roots, const u64* precon, u64 q) {
-    using G = Geom<LOGN, LOGE>;
-    if (int rc = hx_lds_optin<k_ntt_fwd<LOGN, LOGE>>(ctx->device, G::LDS_USED)) return rc;
-    // (a persistent forward integer kernel measured no faster in rounds 2 and 4 -- the integer butterflies are bound by their instruction
-    // count, the prefetch registers cost what the hidden load latency gains -- and is gone)
-    hipLaunchKernelGGL((k_ntt_fwd<LOGN, LOGE>), dim3((unsigned)batch), dim3(G::T), G::LDS_USED, ctx->stream, x,
-                       roots, precon, q, (u32)batch, ctx->ntt_clear_viol, ctx->ntt_clear_viol ? ctx->ntt_hint_word : nullptr);
-    return (int)hipGetLastError();
+// ---------------------------------------------------------------------------------------------
+// Host side. ntt_route.hpp decides what a launch runs -- family, geometry, tier, grids -- from the call's arguments and the four
+// HEXL_NTT_* knobs; everything below executes a route, in this order on the stream: LDS opt-ins, reservations, k_ntt_prepare, the
+// transform, the redo launch.
+// ---------------------------------------------------------------------------------------------
+static const NttKnobs& ntt_knobs() {                               // read once per process
+    static const NttKnobs k{hx_knob("HEXL_NTT_INT", 0), hx_knob("HEXL_NTT_PERSIST", 1), hx_knob("HEXL_NTT_HALVES", 1), (int)hx_knob("HEXL_NTT_E16", -1)};
+    return k;
 }
 
-template <int LOGN, int LOGE>
-static int launch_inv(hexl_ctx* ctx, u64* x, size_t batch, const u64* ir, const u64* ip, u64 q, u64 a, u64 ap,
-                      u64 b, u64 bp) {
-    using G = Geom<LOGN, LOGE>;
-    if (int rc = hx_lds_optin<k_ntt_inv<LOGN, LOGE>>(ctx->device, G::LDS_USED)) return rc;
-    const bool persist = persist_enabled();
-    const size_t slots = size_t(ctx->num_cu) * (G::LDS_USED > 80 * 1024 ? 1 : (160 * 1024) / G::LDS_USED);
-    if constexpr (LOGN == 14 && LOGE == 4) if (persist && batch > slots) {
-        if (int rc = hx_lds_optin<k_ntt_inv_ip<LOGN, LOGE>>(ctx->device, G::LDS_USED)) return rc;
-        hipLaunchKernelGGL((k_ntt_inv_ip<LOGN, LOGE>), dim3((unsigned)slots), dim3(G::T), G::LDS_USED, ctx->stream, x, ir, ip,
-                           q, a, ap, b, bp, (u32)batch, ctx->ntt_clear_viol, ctx->ntt_clear_viol ? ctx->ntt_hint_word : nullptr);
-        return (int)hipGetLastError();
+// What the launches of one call share: a local of launch_ntt. The second line is of this launch alone -- ntt_hinted fills in the tag
+// and the slot, ntt_prepare the rest once the route is known.
+struct NttCall {
+    hexl_ctx* ctx; u64* x; const u64 *roots, *precon; u64 q, n; u32 batch;
+    NttHint hint; u32 hint_slot; NttPrep pr; const u32* clear_viol;     // clear_viol: hinted route, the integer kernel clears the hint when this counter is 0
+    // kernel<<<grid, threads, lds>>>(x, roots, precon, q, rest...) on the context's stream
+    template <class K, class... A>
+    void launch(K kernel, unsigned grid, int threads, size_t lds, const std::tuple<A...>& rest) const {
+        std::apply([&](const A&... a) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, ctx->stream, x, roots, precon, q, a...); }, rest);
     }
-    hipLaunchKernelGGL((k_ntt_inv<LOGN, LOGE>), dim3((unsigned)batch), dim3(G::T), G::LDS_USED, ctx->stream, x, ir,
-                       ip, q, a, ap, b, bp, (u32)batch, ctx->ntt_clear_viol, ctx->ntt_clear_viol ? ctx->ntt_hint_word : nullptr);
-    return (int)hipGetLastError();
-}
+};
 
-template <int LOGN, int LOGE, int LAZY, bool SEMI = false>
-static int launch_fwd_x(hexl_ctx* ctx, u64* x, size_t batch, const u64* roots, const u64* precon, u64 q, NttPrep pr) {
-    using G = Geom<LOGN, LOGE>;
-    if (int rc = hx_lds_optin<k_ntt_fwd_x<LOGN, LOGE, LAZY, SEMI>>(ctx->device, G::LDS_USED)) return rc;
-    // persistent workgroups with input prefetch wherever 2 E more registers fit (not N = 32768: 64 data registers at
-    // 1024 threads) and the batch fills the chip more than once; HEXL_NTT_PERSIST=0 keeps one workgroup per polynomial
-    const bool persist = persist_enabled();
-    const size_t slots = size_t(ctx->num_cu) * (G::LDS_USED > 80 * 1024 ? 1 : (160 * 1024) / G::LDS_USED);
-    if (persist && !G::HALF_ONLY && batch > slots) {
-        if (int rc = hx_lds_optin<k_ntt_fwd_p<LOGN, LOGE, LAZY, SEMI>>(ctx->device, G::LDS_USED + RangeVote::BYTES)) return rc;
-        if (int rc = launch_prepare(ctx, roots, precon, q, pr)) return rc;
-        hipLaunchKernelGGL((k_ntt_fwd_p<LOGN, LOGE, LAZY, SEMI>), dim3((unsigned)slots), dim3(G::T), G::LDS_USED + RangeVote::BYTES, ctx->stream, x,
-                           roots, precon, q, pr, (u32)batch, NttHint{ctx->ntt_hint_word, ctx->ntt_hint_tag});
-        return (int)hipGetLastError();
+// The two directions: the kernel symbols, the scale arguments the inverse kernels take (behind q the four Shoup words of the integer
+// butterflies, behind the tables the FP64 butterflies' InvScale; filled once in hx_launch_ntt_inv), and which persistent FP64 kernels
+// leave their fallback to a k_ntt_redo_* launch.
+struct NttFwd {
+    static constexpr bool INVERSE = false;
+    template <int LOGN, int LOGE> static constexpr auto k_int = k_ntt_fwd<LOGN, LOGE>;
+    template <int LOGN, int LOGE, int LAZY, bool SEMI> static constexpr auto k_one = k_ntt_fwd_x<LOGN, LOGE, LAZY, SEMI>;
+    template <int LOGN, int LOGE, int LAZY, bool SEMI> static constexpr auto k_persistent = k_ntt_fwd_p<LOGN, LOGE, LAZY, SEMI>;
+    template <int LAZY, bool SEMI> static constexpr auto k_halves = k_ntt_fwd_h<LAZY, SEMI>;
+    template <int LOGN, int LOGE> static constexpr auto k_redo = k_ntt_redo_fwd<LOGN, LOGE>;
+    template <int LOGN, int LAZY> static constexpr bool REDO = false;
+    std::tuple<> words() const { return {}; }
+    std::tuple<> scale() const { return {}; }
+};
+struct NttInv {
+    static constexpr bool INVERSE = true;
+    template <int LOGN, int LOGE> static constexpr auto k_int = k_ntt_inv<LOGN, LOGE>;
+    template <int LOGN, int LOGE, int LAZY, bool> static constexpr auto k_one = k_ntt_inv_x<LOGN, LOGE, LAZY>;
+    template <int LOGN, int LOGE, int LAZY, bool> static constexpr auto k_persistent = k_ntt_inv_p<LOGN, LOGE, LAZY>;
+    template <int LAZY, bool> static constexpr auto k_halves = k_ntt_inv_h<LAZY>;
+    template <int LOGN, int LOGE> static constexpr auto k_redo = k_ntt_redo_inv<LOGN, LOGE>;
+    template <int LOGN, int LAZY> static constexpr bool REDO = ntt_inv_redo<LOGN, LAZY>;
+    u64 a, ap, b, bp;                    // n^-1, n^-1 W and their Shoup factors
+    hxf::InvScale sc;                    // the same centred, for a < q and b < q
+    std::tuple<u64, u64, u64, u64> words() const { return {a, ap, b, bp}; }
+    std::tuple<hxf::InvScale> scale() const { return {sc}; }
+};
+
+// The one place where a route's runtime tier and geometry become template arguments (tier first: not every tier has every ring).
+// f(<LAZY>, <SEMI>): the forward periods 12 and 6, then what both directions have -- period 3 and strict -- with the forward
+// transform's semi-strict variant of the latter.
+template <bool INVERSE, class F>
+static int with_ntt_tier(int lazy, bool semi, F f) {
+    if constexpr (!INVERSE) {
+        if (lazy == 12) return f(hx_int<12>{}, std::false_type{});
+        if (lazy == 6) return f(hx_int<6>{}, std::false_type{});
     }
-    if (int rc = launch_prepare(ctx, roots, precon, q, pr)) return rc;
-    hipLaunchKernelGGL((k_ntt_fwd_x<LOGN, LOGE, LAZY, SEMI>), dim3((unsigned)batch), dim3(G::T), G::LDS_USED, ctx->stream, x,
-                       roots, precon, q, (const double*)pr.w, (const double*)pr.wp, (const u32*)pr.viol, (u32)batch, NttHint{ctx->ntt_hint_word, ctx->ntt_hint_tag});
+    if (lazy) return f(hx_int<3>{}, std::false_type{});
+    if constexpr (!INVERSE)
+        if (semi) return f(hx_int<0>{}, std::true_type{});
+    return f(hx_int<0>{}, std::false_type{});
+}
+// f(<LOGN>, <LOGE>) for the rings a kind of kernel exists at: the integer kernels at ntt_loge alone, the FP64 kernels also with 16
+// coefficients per thread at N = 2048 .. 8192, the forward FP64 kernels of the periods 6 and 12 at N = 16384 only
+enum NttRings { NTT_RINGS_INT, NTT_RINGS_F64, NTT_RINGS_N14 };
+template <NttRings RINGS, class F>
+static int with_ntt_geom(int logn, int loge, F f) {
+    auto at = [&](auto N, auto E) {
+        constexpr int LOGN = decltype(N)::value;
+        using G = Geom<LOGN, decltype(E)::value>;
+        static_assert(G::LDS_USED == ntt_lds_used(LOGN) && G::HALF_ONLY == ntt_half_only(LOGN),
+                      "ntt_route.hpp restates Geom's LDS footprint: its grids rest on it");
+        return f(N, E);
+    };
+    auto dflt = [&](auto N) { return at(N, hx_int<ntt_loge(decltype(N)::value)>{}); };
+    auto e16 = [&](auto N) {
+        if constexpr (RINGS == NTT_RINGS_F64) if (loge == 4) return at(N, hx_int<4>{});
+        return dflt(N);
+    };
+    if constexpr (RINGS == NTT_RINGS_N14) return logn == 14 ? dflt(hx_int<14>{}) : (int)HEXL_E_BADARG;
+    else switch (logn) {
+        case 10: return dflt(hx_int<10>{});
+        case 11: return e16(hx_int<11>{});
+        case 12: return e16(hx_int<12>{});
+        case 13: return e16(hx_int<13>{});
+        case 14: return dflt(hx_int<14>{});
+        case 15: return dflt(hx_int<15>{});
+        default: return (int)HEXL_E_BADARG;
+    }
+}
+
+static int ensure_ntt_hint(hexl_ctx* ctx) {                        // NttHint: four pinned, device-visible words
+    if (!ctx->h_ntt_hint) {
+        if (int rc = ctx->h_ntt_hint.reserve(4)) return rc;
+        memset(ctx->h_ntt_hint, 0, 4 * sizeof(unsigned long long));
+        HX_CHECK(hipHostGetDevicePointer((void**)&ctx->d_ntt_hint, ctx->h_ntt_hint, 0));
+    }
+    return 0;
+}
+
+// device scratch for the derived tables: a ring of 64 violation counters (one per launch, round robin), then [w | w/p] (n doubles each)
+static int reserve_tables(hexl_ctx* ctx, u64 n, NttPrep* pr) {
+    constexpr size_t HEAD = 256;                                                        // 64 violation counters
+    const size_t bytes = HEAD + 2 * n * sizeof(double);
+    const void* before = ctx->d_ntt_tab;
+    int rc = ctx->d_ntt_tab.reserve(bytes);
+    if (rc) return rc;
+    if (ctx->d_ntt_tab != before) HX_CHECK(hipMemsetAsync(ctx->d_ntt_tab, 0, HEAD, ctx->stream));
+    u32* counters = (u32*)ctx->d_ntt_tab.get();
+    pr->w = (double*)(ctx->d_ntt_tab + HEAD);
+    pr->wp = pr->w + n;
+    if (int rch = ensure_ntt_hint(ctx)) return rch;
+    const u32 seq = ctx->ntt_seq++;
+    pr->viol = counters + (seq & 63);
+    pr->viol_later = counters + ((seq + 32) & 63);
+    pr->n = (u32)n;
+    pr->redo = nullptr;
+    return 0;
+}
+
+// tag of the call's table set (never 0) and its hint slot; true when a previous launch on this context flagged exactly this set (the
+// hint words exist from the context's first fast-path-eligible call on: nothing can have been flagged before)
+static bool ntt_hinted(NttCall& c, int dir) {
+    u64 z = (u64)(uintptr_t)c.roots * 0x9E3779B97F4A7C15ull ^ (u64)(uintptr_t)c.precon * 0xBF58476D1CE4E5B9ull ^ c.q * 0x94D049BB133111EBull ^ (c.n << 1) ^ (u64)dir;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27;
+    c.hint.tag = z | 1;
+    c.hint_slot = (u32)(z >> 60) & 3;
+    return c.ctx->h_ntt_hint && ((volatile unsigned long long*)c.ctx->h_ntt_hint.get())[c.hint_slot] == c.hint.tag;
+}
+
+// The reservations of a route and k_ntt_prepare (a launch of its own in front of every fast-path-eligible transform; it also zeroes the
+// redo counter). A route without it leaves counter and hint word null: the integer kernel has nothing to clear.
+static int ntt_prepare(NttCall& c, const NttRoute& r) {
+    if (!r.prepare) return 0;
+    if (int rc = reserve_tables(c.ctx, c.n, &c.pr)) return rc;
+    c.hint.word = c.ctx->d_ntt_hint + c.hint_slot;
+    if (r.clear_hint) c.clear_viol = c.pr.viol;
+    if (r.redo) {
+        if (int rc = c.ctx->d_ntt_redo.reserve(size_t(c.batch) + 1)) return rc;
+        c.pr.redo = c.ctx->d_ntt_redo;
+    }
+    hipLaunchKernelGGL(k_ntt_prepare, dim3((c.pr.n + 255) / 256), dim3(256), 0, c.ctx->stream, c.roots, c.precon, c.q, c.pr);
     return (int)hipGetLastError();
 }
 
-template <int LOGN, int LOGE, int LAZY>
-static int launch_inv_x(hexl_ctx* ctx, u64* x, size_t batch, const u64* ir, const u64* ip, u64 q, u64 a, u64 ap, u64 b,
-                        u64 bp, NttPrep pr, hxf::InvScale sc) {
-    using G = Geom<LOGN, LOGE>;
-    if (int rc = hx_lds_optin<k_ntt_inv_x<LOGN, LOGE, LAZY>>(ctx->device, G::LDS_USED)) return rc;
-    const bool persist = persist_enabled();
-    const size_t slots = size_t(ctx->num_cu) * (G::LDS_USED > 80 * 1024 ? 1 : (160 * 1024) / G::LDS_USED);
-    if (persist && !G::HALF_ONLY && batch > slots) {
-        if (int rc = hx_lds_optin<k_ntt_inv_p<LOGN, LOGE, LAZY>>(ctx->device, G::LDS_USED + RangeVote::BYTES)) return rc;
-        if constexpr (ntt_inv_redo<LOGN, LAZY>) {                                // fallback in a launch of its own behind the fast kernel
-            if (int rc = hx_lds_optin<k_ntt_redo_inv<LOGN, LOGE>>(ctx->device, G::LDS_USED)) return rc;
-            if (int rc = reserve_redo(ctx, batch, &pr)) return rc;               // (the preparation zeroes the counter)
+// The integer family: one workgroup per polynomial, but the inverse's persistent kernel at N = 16384 (same arguments).
+template <class Dir>
+static int launch_int(NttCall& c, const NttRoute& r, const Dir& d) {
+    return with_ntt_geom<NTT_RINGS_INT>(r.logn, r.loge, [&](auto N, auto E) {
+        constexpr int LOGN = decltype(N)::value, LOGE = decltype(E)::value;
+        using G = Geom<LOGN, LOGE>;
+        auto kernel = Dir::template k_int<LOGN, LOGE>;
+        if (int rc = hx_lds_optin<Dir::template k_int<LOGN, LOGE>>(c.ctx->device, G::LDS_USED)) return rc;
+        if constexpr (Dir::INVERSE && LOGN == 14) if (r.persistent) {
+            if (int rc = hx_lds_optin<k_ntt_inv_ip<LOGN, LOGE>>(c.ctx->device, G::LDS_USED)) return rc;
+            kernel = k_ntt_inv_ip<LOGN, LOGE>;
         }
-        if (int rc = launch_prepare(ctx, ir, ip, q, pr)) return rc;
-        hipLaunchKernelGGL((k_ntt_inv_p<LOGN, LOGE, LAZY>), dim3((unsigned)slots), dim3(G::T), G::LDS_USED + RangeVote::BYTES, ctx->stream, x,
-                           ir, ip, q, a, ap, b, bp, pr, sc, (u32)batch, NttHint{ctx->ntt_hint_word, ctx->ntt_hint_tag});
-        if constexpr (ntt_inv_redo<LOGN, LAZY>)
-            hipLaunchKernelGGL((k_ntt_redo_inv<LOGN, LOGE>), dim3(redo_grid((unsigned)slots)), dim3(G::T), G::LDS_USED, ctx->stream, x, ir, ip, q, a, ap, b, bp,
-                               pr, (u32)batch);
+        if (int rc = ntt_prepare(c, r)) return rc;
+        c.launch(kernel, r.grid, G::T, G::LDS_USED, std::tuple_cat(d.words(), std::make_tuple(c.batch, c.clear_viol, c.clear_viol ? c.hint.word : nullptr)));
+        return (int)hipGetLastError();
+    });
+}
+
+// The halves family (N = 32768): the transform on the geometry of the N = 16384 kernels, always followed by the redo launch.
+template <class Dir, int LAZY, bool SEMI>
+static int launch_halves_as(NttCall& c, const NttRoute& r, const Dir& d) {
+    using G = Geom<14, 4>;
+    constexpr size_t LDS = G::LDS_USED + RangeVote::BYTES, LDS_INT = Geom<15, 5>::LDS_USED;
+    if (int rc = hx_lds_optin<Dir::template k_halves<LAZY, SEMI>>(c.ctx->device, LDS)) return rc;
+    if (int rc = hx_lds_optin<Dir::template k_redo<15, 5>>(c.ctx->device, LDS_INT)) return rc;
+    if (int rc = ntt_prepare(c, r)) return rc;
+    c.launch(Dir::template k_halves<LAZY, SEMI>, r.grid, G::T, LDS, std::tuple_cat(std::make_tuple(c.pr), d.scale(), std::make_tuple(c.batch, c.hint)));
+    c.launch(Dir::template k_redo<15, 5>, r.redo_grid, G::T, LDS_INT, std::tuple_cat(d.words(), std::make_tuple(c.pr, c.batch)));
+    return (int)hipGetLastError();
+}
+
+// The FP64 family: one workgroup per polynomial (k_ntt_*_x, the derived tables and the counter as plain pointers), or persistent
+// workgroups (k_ntt_*_p, the range vote's flags behind the polynomial in LDS) with, for the kernels that have no fallback of their
+// own, the redo launch behind them.
+template <class Dir, int LOGN, int LOGE, int LAZY, bool SEMI>
+static int launch_f64_as(NttCall& c, const NttRoute& r, const Dir& d) {
+    constexpr bool REDO = Dir::template REDO<LOGN, LAZY>;
+    static_assert(REDO == ntt_f64_redo(Dir::INVERSE, LOGN, LAZY), "ntt_route.hpp restates which persistent kernels note their fallbacks for a redo launch");
+    using G = Geom<LOGN, LOGE>;
+    if constexpr (LOGN == 15)                                       // the two FP64 families of N = 32768: the route names which
+        if (r.family == NTT_HALVES) return launch_halves_as<Dir, LAZY, SEMI>(c, r, d);
+    if (int rc = hx_lds_optin<Dir::template k_one<LOGN, LOGE, LAZY, SEMI>>(c.ctx->device, G::LDS_USED)) return rc;
+    if (!r.persistent) {
+        if (int rc = ntt_prepare(c, r)) return rc;
+        c.launch(Dir::template k_one<LOGN, LOGE, LAZY, SEMI>, r.grid, G::T, G::LDS_USED,
+                 std::tuple_cat(d.words(), std::make_tuple((const double*)c.pr.w, (const double*)c.pr.wp), d.scale(),
+                                std::make_tuple((const u32*)c.pr.viol, c.batch, c.hint)));
         return (int)hipGetLastError();
     }
-    if (int rc = launch_prepare(ctx, ir, ip, q, pr)) return rc;
-    hipLaunchKernelGGL((k_ntt_inv_x<LOGN, LOGE, LAZY>), dim3((unsigned)batch), dim3(G::T), G::LDS_USED, ctx->stream, x,
-                       ir, ip, q, a, ap, b, bp, (const double*)pr.w, (const double*)pr.wp, sc, (const u32*)pr.viol, (u32)batch, NttHint{ctx->ntt_hint_word, ctx->ntt_hint_tag});
+    if (int rc = hx_lds_optin<Dir::template k_persistent<LOGN, LOGE, LAZY, SEMI>>(c.ctx->device, G::LDS_USED + RangeVote::BYTES)) return rc;
+    if constexpr (REDO)
+        if (int rc = hx_lds_optin<Dir::template k_redo<LOGN, LOGE>>(c.ctx->device, G::LDS_USED)) return rc;
+    if (int rc = ntt_prepare(c, r)) return rc;
+    c.launch(Dir::template k_persistent<LOGN, LOGE, LAZY, SEMI>, r.grid, G::T, G::LDS_USED + RangeVote::BYTES,
+             std::tuple_cat(d.words(), std::make_tuple(c.pr), d.scale(), std::make_tuple(c.batch, c.hint)));
+    if constexpr (REDO)
+        c.launch(Dir::template k_redo<LOGN, LOGE>, r.redo_grid, G::T, G::LDS_USED, std::tuple_cat(d.words(), std::make_tuple(c.pr, c.batch)));
     return (int)hipGetLastError();
 }
-
-template <int LAZY, bool SEMI = false>
-static int launch_fwd_h(hexl_ctx* ctx, u64* x, size_t batch, const u64* roots, const u64* precon, u64 q, NttPrep pr) {
-    using G = Geom<14, 4>;
-    constexpr size_t LDS = G::LDS_USED + RangeVote::BYTES, LDS_INT = Geom<15, 5>::LDS_USED;
-    if (int rc = hx_lds_optin<k_ntt_fwd_h<LAZY, SEMI>>(ctx->device, LDS)) return rc;
-    if (int rc = hx_lds_optin<k_ntt_redo_fwd<15, 5>>(ctx->device, LDS_INT)) return rc;
-    if (int rc = reserve_redo(ctx, batch, &pr)) return rc;
-    if (int rc = launch_prepare(ctx, roots, precon, q, pr)) return rc;           // (also zeroes the redo counter)
-    const unsigned grid = (unsigned)(batch < (size_t)ctx->num_cu ? batch : (size_t)ctx->num_cu);
-    hipLaunchKernelGGL((k_ntt_fwd_h<LAZY, SEMI>), dim3(grid), dim3(G::T), LDS, ctx->stream, x, roots, precon, q, pr, (u32)batch,
-                       NttHint{ctx->ntt_hint_word, ctx->ntt_hint_tag});
-    hipLaunchKernelGGL((k_ntt_redo_fwd<15, 5>), dim3(redo_grid(grid)), dim3(G::T), LDS_INT, ctx->stream, x, roots, precon, q, pr, (u32)batch);
-    return (int)hipGetLastError();
-}
-template <int LAZY>
-static int launch_inv_h(hexl_ctx* ctx, u64* x, size_t batch, const u64* ir, const u64* ip, u64 q, u64 a, u64 ap, u64 b, u64 bp, NttPrep pr,
-                        hxf::InvScale sc) {
-    using G = Geom<14, 4>;
-    constexpr size_t LDS = G::LDS_USED + RangeVote::BYTES, LDS_INT = Geom<15, 5>::LDS_USED;
-    if (int rc = hx_lds_optin<k_ntt_inv_h<LAZY>>(ctx->device, LDS)) return rc;
-    if (int rc = hx_lds_optin<k_ntt_redo_inv<15, 5>>(ctx->device, LDS_INT)) return rc;
-    if (int rc = reserve_redo(ctx, batch, &pr)) return rc;
-    if (int rc = launch_prepare(ctx, ir, ip, q, pr)) return rc;
-    const unsigned grid = (unsigned)(batch < (size_t)ctx->num_cu ? batch : (size_t)ctx->num_cu);
-    hipLaunchKernelGGL((k_ntt_inv_h<LAZY>), dim3(grid), dim3(G::T), LDS, ctx->stream, x, ir, ip, q, pr, sc, (u32)batch,
-                       NttHint{ctx->ntt_hint_word, ctx->ntt_hint_tag});
-    hipLaunchKernelGGL((k_ntt_redo_inv<15, 5>), dim3(redo_grid(grid)), dim3(G::T), LDS_INT, ctx->stream, x, ir, ip, q, a, ap, b, bp, pr, (u32)batch);
-    return (int)hipGetLastError();
-}
-
-// FP64 transforms of N = 2048 .. 8192: 16 coefficients per thread where that measured faster than 32 (twice the waves
-// per CU, but a different run length per lane in the B-order access): forward N = 2048 (+17 %) and 8192 (+16 %), inverse
-// N = 2048 (+12 %); N = 4096 lost 16 % both ways, the inverse at 8192 11 % (tools/ntt_n_sweep.py).
-// HEXL_NTT_E16 = bit mask over logn - 11 forces the choice for both directions.
-static bool small_e16(int logn, bool fwd) {
-    static const int mask = (int)hx_knob("HEXL_NTT_E16", -1);
-    const int m = mask >= 0 ? mask : (fwd ? 0b101 : 0b001);
-    return (m >> (logn - 11)) & 1;
-}
-
-template <int LAZY, bool SEMI = false>
-static int dispatch_fwd_x(int logn, hexl_ctx* c, u64* x, size_t batch, const u64* r, const u64* p, u64 q, const NttPrep& pr) {
-    switch (logn) {
-        case 10: return launch_fwd_x<10, 4, LAZY, SEMI>(c, x, batch, r, p, q, pr);
-        case 11: return small_e16(11, true) ? launch_fwd_x<11, 4, LAZY, SEMI>(c, x, batch, r, p, q, pr)
-                                   : launch_fwd_x<11, 5, LAZY, SEMI>(c, x, batch, r, p, q, pr);
-        case 12: return small_e16(12, true) ? launch_fwd_x<12, 4, LAZY, SEMI>(c, x, batch, r, p, q, pr)
-                                   : launch_fwd_x<12, 5, LAZY, SEMI>(c, x, batch, r, p, q, pr);
-        case 13: return small_e16(13, true) ? launch_fwd_x<13, 4, LAZY, SEMI>(c, x, batch, r, p, q, pr)
-                                   : launch_fwd_x<13, 5, LAZY, SEMI>(c, x, batch, r, p, q, pr);
-        case 14: return launch_fwd_x<14, 4, LAZY, SEMI>(c, x, batch, r, p, q, pr);
-        case 15: return halves_enabled() ? launch_fwd_h<LAZY, SEMI>(c, x, batch, r, p, q, pr)       // beyond the reference: two sub-transforms
-                                         : launch_fwd_x<15, 5, LAZY, SEMI>(c, x, batch, r, p, q, pr);   // (half-size exchanges)
-        default: return HEXL_E_BADARG;
-    }
-}
-template <int LAZY>
-static int dispatch_inv_x(int logn, hexl_ctx* c, u64* x, size_t batch, const u64* r, const u64* p, u64 q, u64 a, u64 ap,
-                          u64 b, u64 bp, const NttPrep& pr, hxf::InvScale sc) {
-    switch (logn) {
-        case 10: return launch_inv_x<10, 4, LAZY>(c, x, batch, r, p, q, a, ap, b, bp, pr, sc);
-        case 11: return small_e16(11, false) ? launch_inv_x<11, 4, LAZY>(c, x, batch, r, p, q, a, ap, b, bp, pr, sc)
-                                   : launch_inv_x<11, 5, LAZY>(c, x, batch, r, p, q, a, ap, b, bp, pr, sc);
-        case 12: return small_e16(12, false) ? launch_inv_x<12, 4, LAZY>(c, x, batch, r, p, q, a, ap, b, bp, pr, sc)
-                                   : launch_inv_x<12, 5, LAZY>(c, x, batch, r, p, q, a, ap, b, bp, pr, sc);
-        case 13: return small_e16(13, false) ? launch_inv_x<13, 4, LAZY>(c, x, batch, r, p, q, a, ap, b, bp, pr, sc)
-                                   : launch_inv_x<13, 5, LAZY>(c, x, batch, r, p, q, a, ap, b, bp, pr, sc);
-        case 14: return launch_inv_x<14, 4, LAZY>(c, x, batch, r, p, q, a, ap, b, bp, pr, sc);
-        case 15: return halves_enabled() ? launch_inv_h<LAZY>(c, x, batch, r, p, q, a, ap, b, bp, pr, sc)
-                                         : launch_inv_x<15, 5, LAZY>(c, x, batch, r, p, q, a, ap, b, bp, pr, sc);
-        default: return HEXL_E_BADARG;
-    }
+template <class Dir>
+static int launch_fp(NttCall& c, const NttRoute& r, const Dir& d) {
+    return with_ntt_tier<Dir::INVERSE>(r.lazy, r.semi, [&](auto L, auto S) {
+        constexpr int LAZY = decltype(L)::value;
+        constexpr bool SEMI = decltype(S)::value;
+        return with_ntt_geom<(LAZY > 3 ? NTT_RINGS_N14 : NTT_RINGS_F64)>(r.logn, r.loge, [&](auto N, auto E) {
+            constexpr int LOGN = decltype(N)::value, LOGE = decltype(E)::value;
+            return launch_f64_as<Dir, LOGN, LOGE, LAZY, SEMI>(c, r, d);
+        });
+    });
 }
 
 static int ilog2_exact(u64 n) {
@@ -954,80 +963,31 @@ static int ilog2_exact(u64 n) {
     return -1;
 }
 
-// tag of a table set (never 0) and its hint slot; true when a previous launch on this context flagged exactly this set
-static bool ntt_hinted(hexl_ctx* ctx, const u64* t0, const u64* t1, u64 q, u64 n, int dir) {
-    u64 z = (u64)(uintptr_t)t0 * 0x9E3779B97F4A7C15ull ^ (u64)(uintptr_t)t1 * 0xBF58476D1CE4E5B9ull ^ q * 0x94D049BB133111EBull ^ (n << 1) ^ (u64)dir;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    ctx->ntt_hint_tag = z | 1;
-    const u32 slot = (u32)(z >> 60) & 3;
-    ctx->ntt_hint_word = ctx->d_ntt_hint + slot;
-    return ((volatile unsigned long long*)ctx->h_ntt_hint)[slot] == ctx->ntt_hint_tag;
+template <class Dir>
+static int launch_ntt(hexl_ctx* ctx, u64* x, size_t batch, const u64* roots, const u64* precon, u64 q, u64 n, bool scale_in_range, const Dir& d) {
+    NttCall c{ctx, x, roots, precon, q, n, (u32)batch};
+    const bool hinted = ntt_hinted(c, Dir::INVERSE);
+    const NttRoute r = ntt_route(Dir::INVERSE, ilog2_exact(n), q, scale_in_range, batch, ctx->num_cu, hinted, ntt_knobs());
+    switch (r.family) {
+        case NTT_F64:
+        case NTT_HALVES: return launch_fp(c, r, d);
+        case NTT_INT: return launch_int(c, r, d);
+        case NTT_BADARG: return HEXL_E_BADARG;
+        default: return 0;                                         // empty batch
+    }
 }
 
 int hx_launch_ntt_fwd(hexl_ctx* ctx, u64* x, size_t batch, const u64* roots, const u64* precon, u64 q, u64 n) {
-    if (!batch) return 0;
-    const int logn = ilog2_exact(n);
-    ctx->ntt_clear_viol = nullptr;
-    if (fast_path_enabled() && q >= (1ull << 16) && q < hxf::STRICT_NTT_MAX_Q) {
-        NttPrep pr;
-        // a previous call found these tables not to be Shoup tables: the dedicated integer kernels, which also clear the hint
-        // once the prepare kernel (still run for a hinted set) finds the tables genuine
-        if (int rch = ensure_ntt_hint(ctx)) return rch;
-        const bool hinted = ntt_hinted(ctx, roots, precon, q, n, 0);
-        int rc = reserve_tables(ctx, n, &pr);
-        if (!rc && hinted) rc = launch_prepare(ctx, roots, precon, q, pr);      // (the fast-path launchers below prepare for themselves)
-        if (rc) return rc;
-        if (hinted) ctx->ntt_clear_viol = pr.viol;
-        const int period = hxf::lazy_period_for((double)q);       // fewer range reductions for smaller moduli (N = 16384)
-        if (!hinted) {
-            if (logn == 14 && period == 12) return launch_fwd_x<14, 4, 12>(ctx, x, batch, roots, precon, q, pr);
-            if (logn == 14 && period == 6) return launch_fwd_x<14, 4, 6>(ctx, x, batch, roots, precon, q, pr);
-            if (period) return dispatch_fwd_x<3>(logn, ctx, x, batch, roots, precon, q, pr);
-            // strict tier: semi-strict butterflies (f64_arith.hpp ct_bfly_semi, 11 instead of 14 instructions) in the wave-uniform passes up to
-            // 2^52 (1 + 2^-20) -- SURVEY 8d's q = 2^52 + 393217 included --, the plain strict ones above
-            return (double)q <= hxf::SEMI_MAX_MODULUS ? dispatch_fwd_x<0, true>(logn, ctx, x, batch, roots, precon, q, pr)
-                                                                        : dispatch_fwd_x<0>(logn, ctx, x, batch, roots, precon, q, pr);
-        }
-    }
-    switch (logn) {
-        case 10: return launch_fwd<10, 4>(ctx, x, batch, roots, precon, q);
-        case 11: return launch_fwd<11, 5>(ctx, x, batch, roots, precon, q);
-        case 12: return launch_fwd<12, 5>(ctx, x, batch, roots, precon, q);
-        case 13: return launch_fwd<13, 5>(ctx, x, batch, roots, precon, q);
-        case 14: return launch_fwd<14, 4>(ctx, x, batch, roots, precon, q);
-        case 15: return launch_fwd<15, 5>(ctx, x, batch, roots, precon, q);
-        default: return HEXL_E_BADARG;
-    }
+    return launch_ntt(ctx, x, batch, roots, precon, q, n, true, NttFwd{});
 }
 
 int hx_launch_ntt_inv(hexl_ctx* ctx, u64* x, size_t batch, const u64* ir, const u64* ip, u64 q, u64 a, u64 ap,
                       u64 b, u64 bp, u64 n) {
-    if (!batch) return 0;
-    const int logn = ilog2_exact(n);
-    ctx->ntt_clear_viol = nullptr;
-    if (fast_path_enabled() && q >= (1ull << 16) && q < hxf::STRICT_NTT_MAX_Q && a < q && b < q) {
-        NttPrep pr;
-        if (int rch = ensure_ntt_hint(ctx)) return rch;
-        const bool hinted = ntt_hinted(ctx, ir, ip, q, n, 1);     // see hx_launch_ntt_fwd
-        int rc = reserve_tables(ctx, n, &pr);
-        if (!rc && hinted) rc = launch_prepare(ctx, ir, ip, q, pr);
-        if (rc) return rc;
-        if (hinted) ctx->ntt_clear_viol = pr.viol;
+    NttInv d{a, ap, b, bp, {}};
+    const bool scale_in_range = a < q && b < q;
+    if (scale_in_range) {
         const double pd = (double)q;
-        hxf::InvScale sc;
-        sc.n = hx_centre(a, q); sc.n_p = sc.n / pd; sc.nw = hx_centre(b, q); sc.nw_p = sc.nw / pd;
-        if (!hinted)
-            return pd <= hxf::LAZY_MAX_MODULUS ? dispatch_inv_x<3>(logn, ctx, x, batch, ir, ip, q, a, ap, b, bp, pr, sc)
-                                               : dispatch_inv_x<0>(logn, ctx, x, batch, ir, ip, q, a, ap, b, bp, pr, sc);
+        d.sc.n = hx_centre(a, q); d.sc.n_p = d.sc.n / pd; d.sc.nw = hx_centre(b, q); d.sc.nw_p = d.sc.nw / pd;
     }
-    switch (logn) {
-        case 10: return launch_inv<10, 4>(ctx, x, batch, ir, ip, q, a, ap, b, bp);
-        case 11: return launch_inv<11, 5>(ctx, x, batch, ir, ip, q, a, ap, b, bp);
-        case 12: return launch_inv<12, 5>(ctx, x, batch, ir, ip, q, a, ap, b, bp);
-        case 13: return launch_inv<13, 5>(ctx, x, batch, ir, ip, q, a, ap, b, bp);
-        case 14: return launch_inv<14, 4>(ctx, x, batch, ir, ip, q, a, ap, b, bp);
-        case 15: return launch_inv<15, 5>(ctx, x, batch, ir, ip, q, a, ap, b, bp);
-        default: return HEXL_E_BADARG;
-    }
+    return launch_ntt(ctx, x, batch, ir, ip, q, n, scale_in_range, d);
 }
