@@ -64,6 +64,9 @@ C_ABI = {
     "hexl_rns_ntt_inv": [_vp, _vp, _vp, _sz, _u64],
     "hexl_multiply_plain": [_vp, _vp, _vp, _vp, _sz, _u64, _u64, _sz, _i],
     "hexl_ct_lincomb": [_vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _sz, _vp, _sz, _vp, _sz, _u64, _u64],
+    "hexl_ct_tensor_sum": [_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _sz, _sz, _u64],
+    "hexl_relinearize": [_vp, _vp, _vp, _sz],
+    "hexl_multiply_sum_relinearize": [_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _sz, _sz],
     "hexl_rns_from_f64": [_vp, _vp, _vp, _sz, _u64],
     "hexl_rns_to_f64": [_vp, _vp, _vp, _sz, _u64],
     "hexl_ckks_encode": [_vp, _vp, _vp, _sz, _u64, ctypes.c_double],
@@ -331,6 +334,38 @@ class KeySwitchPlan:
         hp = lambda a: None if a is None else a.ctypes.data
         _check(lib().hexl_ct_lincomb(self.h, _ptr(out), ptr_array(cts), hp(il), hp(w), len(cts), None if pt is None else _ptr(pt), pt_batch,
                                      hp(c), batch, n_components, n_limbs), "hexl_ct_lincomb")
+
+    @staticmethod
+    def _tensor_operands(what, a_s, b_s, in_limbs):
+        """(pointer arrays of the two operand lists, the [n_terms][2] limb counts as a host array or None)"""
+        if len(a_s) != len(b_s):
+            raise ValueError(f"{what}: one b per a")
+        il = None if in_limbs is None else np.ascontiguousarray(np.asarray([int(v) for v in np.asarray(in_limbs, dtype=object).reshape(-1)],
+                                                                            dtype=np.uint64))
+        if il is not None and il.size != 2 * len(a_s):
+            raise ValueError(f"{what}: in_limbs is [n_terms][2]")
+        return ptr_array(a_s), ptr_array(b_s), il
+
+    def ct_tensor_sum(self, out, a_s, b_s, batch: int, n_limbs: int, in_limbs=None):
+        """out[batch][3][n_limbs][n] = sum_t (a0 b0, a0 b1 + a1 b0, a1 b1) of the 1 ... 8 pairs (a_s[t], b_s[t]) mod q_i, word by word in
+        NTT form -- the product before relinearisation, what ct_lincomb, rescale and rlwe_decrypt take with three components. a_s[t] is
+        [batch][2][in_limbs[t][0]][n], b_s[t] [batch][2][in_limbs[t][1]][n], each read through its first n_limbs limbs (in_limbs None: all
+        n_limbs); b_s[t] may be a_s[t]; out must not overlap an operand. No keys needed."""
+        pa, pb, il = self._tensor_operands("ct_tensor_sum", a_s, b_s, in_limbs)
+        _check(lib().hexl_ct_tensor_sum(self.h, _ptr(out), pa, pb, None if il is None else il.ctypes.data, len(a_s), batch, n_limbs),
+               "hexl_ct_tensor_sum")
+
+    def relinearize(self, out, ct3, batch: int):
+        """out[batch][2][L][n] = (c0, c1) + KeySwitch(c2) of ct3[batch][3][L][n]; the plan's keys are the relinearisation key
+        (gen_relin_keys). Every plan keyswitch accepts."""
+        _check(lib().hexl_relinearize(self.h, _ptr(out), _ptr(ct3), batch), "hexl_relinearize")
+
+    def multiply_sum_relinearize(self, out, a_s, b_s, batch: int, in_limbs=None):
+        """out[batch][2][L][n] = relinearize(ct_tensor_sum(a_s, b_s, n_limbs = L)), word for word, with ONE key switch whatever the number
+        of pairs and without the three-component sum ever existing in memory; in_limbs entries in L ... K"""
+        pa, pb, il = self._tensor_operands("multiply_sum_relinearize", a_s, b_s, in_limbs)
+        _check(lib().hexl_multiply_sum_relinearize(self.h, _ptr(out), pa, pb, None if il is None else il.ctypes.data, len(a_s), batch),
+               "hexl_multiply_sum_relinearize")
 
     def rns_from_f64(self, out, coeffs, count: int, n_limbs: int):
         """out[count][n_limbs][n] = NTT_i(rint(coeffs[count][n]) mod q_i): real coefficients (float64, natural order) to NTT-form limbs,

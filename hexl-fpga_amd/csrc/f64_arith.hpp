@@ -137,6 +137,22 @@ HX_HD double lc_add(double acc, double u, const Mod m) { return reduce(acc + u, 
 // the sum after its last addend -> the canonical word (lift takes |x| <= p/2 + 2)
 HX_HD double lc_finish(double acc, const Mod m) { return lift(acc, m); }
 
+// ---- the scalar chains of the ciphertext tensor sum (ct_tensor.hip k_ct_tensor_sum), here so that tests/cpp/tensor_selftest.cpp replays
+// the kernel's own source against 128-bit integers ---------------------------------------------------------------------------------
+// an operand word as the products take it: canonical (0 <= x < p < 2^52, exact as a double) -> centred, |.| <= p/2 + 2, the operand
+// range mul_mod is bounded for. Converted once per word: a0 and b0 meet two products each, a1 and b1 as well.
+HX_HD double ts_operand(double x, const Mod m) { return reduce(x, m); }
+// acc' = (acc + a b) mod p, centred: acc a partial sum as this function leaves it (|acc| <= p/2 + 2; 0 in front of the first term),
+// a and b outputs of ts_operand. The product, by the general bound of the LAZY notes below with a = p 2^-53 < 1/2 and |x| / p =
+// 1/2: the quotient estimate is off by at most 1/2 (rint) + two roundings of h / p <= p/4, each 2^-53 relative (a/4 each), and the
+// split-off low part is |l| <= 2^-53 |h| = a p/4; together |mul_mod| <= (0.5 + 0.75 a) p < 0.875p (mul_mod's own note counts half
+// ulps and no low part: 0.7p). |acc + product| <= 1.375p + 2 < 2^53: the sum is an exact integer inside reduce's domain, and
+// |acc'| <= p/2 + 2 again. EVERY product is followed by a reduce -- the cross term a0 b1 + a1 b0 is two calls, not one sum: two
+// un-reduced products on a centred partial sum could reach 0.5p + 2 + 1.75p = 2.25p > 2^53 at p ~ 2^52 by this bound.
+HX_HD double ts_mac(double acc, double a, double b, const Mod m) { return reduce(acc + mul_mod(a, b, m), m); }
+// the sum after its last term -> the canonical word (lift takes |x| <= p/2 + 2)
+HX_HD double ts_finish(double acc, const Mod m) { return lift(acc, m); }
+
 // ---- the scalar chain of hexl_rns_from_f64 / hexl_ckks_encode (ckks_encode.hip k_rns_from_f64), here so that
 // tests/cpp/from_f64_selftest.cpp replays the kernel's own source against __int128 ------------------------------------------------
 // A real coefficient c -> the centred residue of rint(c) modulo p (|result| <= p/2 + 2), EXACT for every finite c with

@@ -241,7 +241,9 @@ struct hexl_ks_plan {
     HxDevBuf<KsRescaleF64> d_rescale; // [16][16]: row l = constants of the rescale that drops limb l (filled at its first call)
     u32 rescale_levels = 0;           // bit l: row l is filled
     HxDevBuf<double> d_rs_s;          // rescale scratch: s of every (instance, component) pair of a chunk, n doubles each (grow-only)
-    HxDevBuf<u64> d_rot_t;            // rotate: sigma_g(c1) of one slice of instances, [slice][L][n] (grow-only)
+    HxDevBuf<u64> d_rot_t;            // rotate: sigma_g(c1) of one slice of instances, [slice][L][n] (grow-only); relinearize and
+                                      // multiply_sum_relinearize (ct_tensor.hip): component 2 of one slice -- one buffer for all three, as
+                                      // each call's keyswitch has read it before the call returns to the stream
     // baby-step/giant-step linear transform (keyswitch_f64.hip hx_launch_linear_transform_bsgs), both grow-only
     HxDevBuf<double> d_bsgs_b;        // baby store: [n_baby][chunk][2][L+1][n] multiply-accumulate outputs in B order
     HxDevBuf<u64> d_bsgs_t;           // one giant step's inner sum t_j: [chunk][2][L][n] canonical words

@@ -147,7 +147,8 @@ int hexl_rescale(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_in, size
  * automorphism above. The plan's keys must be the switching key from s(X^g) to s (the caller's responsibility). Runs on every plan
  * hexl_keyswitch accepts, integer kernels included. HEXL_E_NOKEYS before hexl_ks_set_keys; HEXL_E_BADARG for a galois_elt that is
  * even or >= 2n, or d_out overlapping d_ct. Device memory kept by the plan, grow-only, beside the keyswitch's scratch:
- * min(batch, chunk) x L x n words (sigma_g(c1) of one slice; 224 MiB at n = 16384, L = 7). */
+ * min(batch, chunk) x L x n words (sigma_g(c1) of one slice; 224 MiB at n = 16384, L = 7), shared with hexl_relinearize and
+ * hexl_multiply_sum_relinearize. */
 int hexl_rotate(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t galois_elt);
 /* Hoisted rotations: n_rot rotations of ONE ciphertext batch (the inner loop of the diagonal method, rotate -> multiply_plain ->
  * accumulate). The keyswitch's steps 1-2 (inverse transforms and mod-up, L + L*L of its L*L + 3L + 2 transforms) depend on c1 alone,
@@ -311,6 +312,53 @@ int hexl_multiply_plain(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_c
 int hexl_ct_lincomb(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* const* d_cts, const uint64_t* in_limbs,
                     const uint64_t* h_weights, size_t n_terms, const uint64_t* d_pt, size_t pt_batch,
                     const uint64_t* h_const, size_t batch, uint64_t n_components, uint64_t n_limbs);
+/* Ciphertext x ciphertext with the relinearisation placed by the caller ("lazy relinearisation"). Relinearisation is linear, so a sum
+ * of products needs ONE key switch -- L*L + 3L + 2 transforms per instance -- where hexl_multiply_relinearize per pair spends one per
+ * term: inner products, ciphertext matrix products, the giant-step sums of a polynomial evaluation, "multiply now, relinearize after
+ * the additions". Everything in NTT form.
+ *
+ * hexl_ct_tensor_sum: the sum of up to eight tensor products, three components out. For b < batch, i < n_limbs, j < n, modulo q_i,
+ * every word canonical:
+ *   out[b][0][i][j] = sum_t a_t[b][0][i][j] . b_t[b][0][i][j]
+ *   out[b][1][i][j] = sum_t ( a_t[b][0][i][j] . b_t[b][1][i][j] + a_t[b][1][i][j] . b_t[b][0][i][j] )
+ *   out[b][2][i][j] = sum_t a_t[b][1][i][j] . b_t[b][1][i][j]
+ *   d_as, d_bs  HOST arrays of n_terms DEVICE pointers, 1 <= n_terms <= 8; a_t is [batch][2][in_limbs[2t]][n] and b_t is
+ *               [batch][2][in_limbs[2t+1]][n], every word below its modulus. d_as[t] == d_bs[t] is allowed (a square); operands may
+ *               overlap each other in any way
+ *   in_limbs    HOST [n_terms][2], n_limbs <= in_limbs[.] <= K, or NULL: every operand has n_limbs. An operand with more limbs than the
+ *               output is read through its first n_limbs limbs only -- the CKKS level drop: the last moduli of the plan's chain are
+ *               discarded, as hexl_rescale and hexl_rns_ntt_* do when they use "the plan's first n_limbs"
+ *   d_out       [batch][3][n_limbs][n], WRITTEN: what hexl_ct_lincomb, hexl_rescale and hexl_rlwe_decrypt take with n_components = 3.
+ *               Sums of more than eight products are chained through hexl_ct_lincomb on three components
+ * 1 <= n_limbs <= K; FP64 plans only, n = 1024 ... 32768, no keys needed, as hexl_ct_lincomb. Every operand is read once and the output
+ * written once: 4 n_terms + 3 polynomial passes per limb.
+ * HEXL_E_BADARG: a null plan, d_out, d_as, d_bs, d_as[t] or d_bs[t] (batch == 0 does not excuse it), n_terms outside 1 ... 8, an
+ * in_limbs entry outside its range, a plan on the integer kernels, d_out overlapping any operand (the layouts differ: there is no
+ * in-place form), a size or a grid that overflows. batch == 0 returns 0 after these checks.
+ * Asynchronous on the context's stream. Pointers and limb counts travel in the kernel's arguments: every host array may be reused as
+ * soon as the call returns, and the call allocates and keeps no device memory. */
+int hexl_ct_tensor_sum(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* const* d_as, const uint64_t* const* d_bs,
+                       const uint64_t* in_limbs, size_t n_terms, size_t batch, uint64_t n_limbs);
+/* Relinearize: d_ct3[batch][3][L][n] -> d_out[batch][2][L][n] WRITTEN with (c0, c1) + KeySwitch(c2), i.e. what
+ * hexl_keyswitch(result = components 0..1, t_target = component 2) leaves. The plan's keys must be the relinearisation key
+ * (hexl_ks_gen_keys with HEXL_KEY_FROM_SQUARE; the caller's responsibility). Runs on every plan hexl_keyswitch accepts, integer kernels
+ * included: the call moves words and runs the key switch, with no arithmetic of its own. Asynchronous on the context's stream.
+ * HEXL_E_BADARG for a null pointer, d_out overlapping d_ct3 or a size that overflows; then HEXL_E_NOKEYS before hexl_ks_set_keys; then
+ * batch == 0 returns 0. Device memory kept by the plan, grow-only, beside the keyswitch's scratch: min(batch, chunk) x L x n words
+ * (component 2 of one slice) -- the very buffer hexl_rotate keeps for sigma_g(c1), shared between the two. */
+int hexl_relinearize(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_ct3, size_t batch);
+/* d_out[batch][2][L][n] WRITTEN with the relinearised sum of up to eight products: word for word
+ *   hexl_ct_tensor_sum(plan, tmp, d_as, d_bs, in_limbs, n_terms, batch, n_limbs = L) followed by hexl_relinearize(plan, d_out, tmp, batch)
+ * (both end in canonical words that depend on exact residues only) -- but the three-component sum never exists in memory: slice by
+ * slice the tensor kernel writes components 0-1 into d_out and component 2 into the key switch's t_target slice. One key switch per
+ * output ciphertext whatever n_terms is: (n_terms - 1) (L*L + 3L + 2) transforms per instance fewer than n_terms calls of
+ * hexl_multiply_relinearize and a hexl_ct_lincomb. With n_terms = 1 the output is word for word hexl_multiply_relinearize's, which
+ * serves one pair better (its product never leaves the chip).
+ * d_as, d_bs, in_limbs, n_terms as for hexl_ct_tensor_sum with n_limbs = L: in_limbs entries in L ... K. FP64 plans only, n = 1024 ...
+ * 32768. HEXL_E_BADARG as for hexl_ct_tensor_sum (d_out must not overlap any operand); then HEXL_E_NOKEYS; then batch == 0 returns 0.
+ * Asynchronous on the context's stream; the host arrays may be reused as soon as the call returns. Device memory: hexl_relinearize's. */
+int hexl_multiply_sum_relinearize(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* const* d_as, const uint64_t* const* d_bs,
+                                  const uint64_t* in_limbs, size_t n_terms, size_t batch);
 /* Encode and decode on the device: the canonical embedding and the change between real coefficients and RNS limbs, so that weights and
  * results can cross the bus as slot vectors (n/2 complex doubles) instead of [n_limbs][n] words. All four are asynchronous on the
  * context's stream and need no keys. FP64 plans only (every modulus < 2^52), n = 1024 ... 32768, 1 <= n_limbs <= K: the moduli are the
