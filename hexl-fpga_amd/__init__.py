@@ -73,6 +73,7 @@ C_ABI = {
     "hexl_ckks_decode": [_vp, _vp, _vp, _sz, _u64, ctypes.c_double],
     "hexl_sample": [_vp, _vp, _i, _vp, _u64, _u64, _sz, _u64],
     "hexl_rlwe_encrypt": [_vp, _vp, _vp, _sz, _vp, _vp, _u64, _u64, _sz, _u64],
+    "hexl_pk_encrypt": [_vp, _vp, _vp, _sz, _vp, _u64, _vp, _u64, _u64, _sz, _u64],
     "hexl_rlwe_decrypt": [_vp, _vp, _vp, _vp, _sz, _u64, _u64],
     "hexl_ks_set_keys_device": [_vp, _vp],
     "hexl_ks_gen_keys": [_vp, _vp, _i, _u64, _vp, _vp, _u64, _u64],
@@ -402,6 +403,24 @@ class KeySwitchPlan:
         words, raw = seed_words(seed)
         _check(lib().hexl_rlwe_encrypt(self.h, _ptr(out), None if pt is None else _ptr(pt), pt_batch, _ptr(secret), words, stream, first,
                                        count, n_limbs), "hexl_rlwe_encrypt")
+        return raw
+
+    def gen_public_key(self, out, secret, n_limbs=None, seed=None, stream: int = 0, first: int = 0) -> bytes:
+        """out[2][n_limbs][n] = (pk0, pk1) = (e - a secret, a): rlwe_encrypt(pt=None, count=1), n_limbs None = K (such a key serves every
+        level through pk_encrypt's pk_limbs). Consumes the UNIFORM and CBD21 polynomial `first` of (seed, stream). Returns the seed's
+        bytes (None = os.urandom)."""
+        return self.rlwe_encrypt(out, secret, 1, self.K if n_limbs is None else n_limbs, seed=seed, stream=stream, first=first)
+
+    def pk_encrypt(self, out, pk, count: int, n_limbs: int, pk_limbs=None, pt=None, pt_batch: int = 1, seed=None, stream: int = 0,
+                   first: int = 0) -> bytes:
+        """out[count][2][n_limbs][n] = (pk0 u + e0 + pt, pk1 u + e1) under the public key pk[2][pk_limbs][n] (gen_public_key; pk_limbs
+        None = n_limbs, only the first n_limbs limbs of each component are read): u = the TERNARY polynomial first + b, e0 / e1 = the
+        CBD21 polynomials 2 (first + b) and 2 (first + b) + 1 of (seed, stream); pt None (an encryption of zero) or
+        [pt_batch][n_limbs][n], pt_batch = 1 or count. Give the call a (seed, stream) of its own and advance `first` by `count`.
+        Returns the seed's bytes (None = os.urandom)."""
+        words, raw = seed_words(seed)
+        _check(lib().hexl_pk_encrypt(self.h, _ptr(out), None if pt is None else _ptr(pt), pt_batch, _ptr(pk),
+                                     n_limbs if pk_limbs is None else pk_limbs, words, stream, first, count, n_limbs), "hexl_pk_encrypt")
         return raw
 
     def rlwe_decrypt(self, out, ct, secret, count: int, n_components: int, n_limbs: int):

@@ -327,6 +327,12 @@ int hx_launch_sample(hexl_ks_plan*, u64* d_out, int kind, const u32* seed, u64 s
 int hx_launch_rlwe_encrypt(hexl_ks_plan*, u64* d_out, const u64* d_pt, bool per_instance, const u64* d_secret, const u32* seed, u64 stream,
                            u64 first, size_t count, u32 n_limbs);
 int hx_launch_rlwe_decrypt(hexl_ks_plan*, u64* d_out, const u64* d_ct, const u64* d_secret, size_t count, u32 n_components, u32 n_limbs);
+// public-key encryption (rlwe.hip; arguments checked by hexl_pk_encrypt): per chunk the mask and the two errors of every instance pass
+// through the encode scratch as 3 rows, so a chunk is a third of encode's -- 85 instances at n = 16384, 1365 at n = 1024
+inline size_t hx_pk_chunk(const hexl_ks_plan* p) { return hx_enc_chunk(p) / 3; }
+inline size_t hx_pk_chunk_of(const hexl_ks_plan* p, size_t count) { return count < hx_pk_chunk(p) ? count : hx_pk_chunk(p); }
+int hx_launch_pk_encrypt(hexl_ks_plan*, u64* d_out, const u64* d_pt, bool per_instance, const u64* d_pk, u32 pk_limbs, const u32* seed,
+                         u64 stream, u64 first, size_t count, u32 n_limbs);
 // the error of nb <= chunk encryptions, NTT_i(CBD21 polynomial first + b) at n_limbs limbs, into d_enc_words (reserved by the caller)
 int hx_launch_rlwe_error(hexl_ks_plan*, const u32* seed, u64 stream, u64 first, size_t nb, u32 n_limbs);
 // switching keys without a host round trip (keygen.hip); arguments checked by their entry points (hexl_ks_set_keys_device,

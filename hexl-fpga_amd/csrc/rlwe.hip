@@ -5,6 +5,8 @@
 //   rlwe_encrypt   out[b] = (pt + e - a s, a), a = UNIFORM and e = CBD21 of polynomial `first + b`       k_sample_small + k_rns_from_f64
 //                                                                                                          + k_rlwe_encrypt
 //   rlwe_decrypt   out[b] = c0 + c1 s (+ c2 s^2), Horner                                                  k_rlwe_decrypt
+//   pk_encrypt     out[b] = (pk0 u + e0 + pt, pk1 u + e1), u = TERNARY polynomial c = first + b, e0 / e1 =      2 k_sample_small + k_rns_from_f64
+//                  CBD21 polynomials 2c / 2c + 1 of (seed, stream)                           + k_pk_encrypt
 // The streams are ChaCha20 in counter mode, addressed per word (sample_core.hpp): a result depends on (seed, stream, absolute
 // polynomial index, limb, coefficient) only. The three word kernels have k_pt_mul's shape (rns_ops.hip): one workgroup per (instance,
 // limb, 1024-word chunk), 256 lanes, the modulus found once per workgroup; a lane owns FOUR CONSECUTIVE words -- 32 contiguous bytes,
@@ -105,6 +107,41 @@ __global__ __launch_bounds__(RL_THREADS) void k_rlwe_encrypt(EncryptArgs a) {
     rl_store4(dst + per, u);
 }
 
+struct PkEncryptArgs {
+    const KsModF64* mods;       // [K]
+    u64* out;                   // [nb][2][L][n]
+    const u64* u;               // [nb][L][n]: NTT_i of the ternary masks (plan scratch)
+    const u64* e;               // [nb][2][L][n]: NTT_i of the two errors of every instance (plan scratch, behind u)
+    const u64* pt;              // nullptr, or [pt_stride ? nb : 1][L][n]
+    const u64* pk;              // [2][pk_limbs][n], rows 0 ... L - 1 of each component read
+    u32 logn, L, pk_limbs, pt_stride;
+};
+
+// k_rlwe_encrypt's shape with the mask and the key read instead of drawn. The six loads (u, e0, e1, pt, pk0, pk1) are issued before
+// the first product; the key's 2 L n words are the same for every instance and come from the cache after the first wave of
+// workgroups, so HBM sees four polynomial reads (u, e0, e1, pt) and two writes per (instance, limb). The chains are sample_core.hpp's.
+__global__ __launch_bounds__(RL_THREADS) void k_pk_encrypt(PkEncryptArgs a) {
+    const RlWhere w = rl_where(a.logn, a.L);
+    const Mod m = a.mods[w.i].m;
+    const size_t within = (size_t(w.i) << a.logn) + w.j0, per = size_t(a.L) << a.logn;
+    double u[4], e0[4], e1[4], p[4] = {0.0, 0.0, 0.0, 0.0}, k0[4], k1[4], c0[4], c1[4];
+    rl_load4(u, a.u + size_t(w.b) * per + within);
+    rl_load4(e0, a.e + size_t(w.b) * 2 * per + within);
+    rl_load4(e1, a.e + (size_t(w.b) * 2 + 1) * per + within);
+    if (a.pt) rl_load4(p, a.pt + size_t(w.b) * a.pt_stride * per + within);
+    rl_load4(k0, a.pk + within);
+    rl_load4(k1, a.pk + (size_t(a.pk_limbs) << a.logn) + within);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double ur = hxs::pk_operand(u[k], m);
+        c0[k] = hxs::pk_c0(hxs::pk_operand(k0[k], m), ur, e0[k], p[k], m);
+        c1[k] = hxs::pk_c1(hxs::pk_operand(k1[k], m), ur, e1[k], m);
+    }
+    u64* dst = a.out + size_t(w.b) * 2 * per + within;
+    rl_store4(dst, c0);
+    rl_store4(dst + per, c1);
+}
+
 struct DecryptArgs {
     const KsModF64* mods;       // [K]
     u64* out;                   // [count][L][n]
@@ -137,10 +174,11 @@ __global__ __launch_bounds__(RL_THREADS) void k_rlwe_decrypt(DecryptArgs a) {
 // ---- launchers ----
 static dim3 rl_grid(const hexl_ks_plan* p, size_t count, u32 n_limbs) { return dim3((u32)hx_ww_grid(p, count, n_limbs)); }
 
-// the small values of instances first ... first + nb - 1 into the plan's d_enc_coeffs (grown by the caller), as doubles
-static int launch_small(hexl_ks_plan* p, int kind, const hxs::Seed& seed, u64 stream, u64 first, size_t nb) {
+// the small values of instances first ... first + nb - 1 into rows row0 ... row0 + nb - 1 of the plan's d_enc_coeffs (grown by the
+// caller), as doubles
+static int launch_small(hexl_ks_plan* p, int kind, const hxs::Seed& seed, u64 stream, u64 first, size_t nb, size_t row0 = 0) {
     SampleArgs a{};
-    a.coeffs = p->d_enc_coeffs;
+    a.coeffs = p->d_enc_coeffs + row0 * p->n;
     a.seed = seed;
     a.stream = stream;
     a.first = first;
@@ -210,6 +248,37 @@ int hx_launch_rlwe_encrypt(hexl_ks_plan* p, u64* d_out, const u64* d_pt, bool pe
     });
 }
 
+// Per chunk of nb instances the encode scratch holds 3 nb rows: the nb masks, then the 2 nb errors in the order [instance][2] -- CBD21
+// polynomials 2 (first + c0) ... are that order already -- and ONE transform launch turns all of them into d_enc_words. A chunk is a
+// third of encode's, so the scratch never grows beyond what a full chunk of hexl_rlwe_encrypt reserves.
+int hx_launch_pk_encrypt(hexl_ks_plan* p, u64* d_out, const u64* d_pt, bool per_instance, const u64* d_pk, u32 pk_limbs, const u32* seed,
+                         u64 stream, u64 first, size_t count, u32 n_limbs) {
+    if (!count) return 0;
+    const size_t n = p->n, chunk = hx_pk_chunk_of(p, count), per = size_t(n_limbs) * n;
+    if (int rc = p->d_enc_coeffs.reserve(3 * chunk * n)) return rc;
+    if (int rc = p->d_enc_words.reserve(3 * chunk * per)) return rc;
+    hxs::Seed sd;
+    for (int k = 0; k < 8; ++k) sd.k[k] = seed[k];
+    PkEncryptArgs a{};
+    a.mods = p->d_mods_f64;
+    a.u = p->d_enc_words;
+    a.pk = d_pk;
+    a.logn = p->logn;
+    a.L = n_limbs;
+    a.pk_limbs = pk_limbs;
+    a.pt_stride = per_instance ? 1u : 0u;
+    return hx_for_chunks(count, chunk, [&](size_t c0, size_t nb) {
+        if (int rc = launch_small(p, hxs::KIND_TERNARY, sd, stream, first + c0, nb)) return rc;
+        if (int rc = launch_small(p, hxs::KIND_CBD21, sd, stream, 2 * (first + c0), 2 * nb, nb)) return rc;
+        if (int rc = hx_launch_encode(p, p->d_enc_words, p->d_enc_coeffs, nullptr, 3 * nb, n_limbs, 1.0)) return rc;
+        a.out = d_out + c0 * 2 * per;
+        a.e = p->d_enc_words + nb * per;
+        a.pt = d_pt ? d_pt + (per_instance ? c0 * per : 0) : nullptr;
+        hipLaunchKernelGGL(k_pk_encrypt, rl_grid(p, nb, n_limbs), dim3(RL_THREADS), 0, p->ctx->stream, a);
+        return (int)hipGetLastError();
+    });
+}
+
 int hx_launch_rlwe_decrypt(hexl_ks_plan* p, u64* d_out, const u64* d_ct, const u64* d_secret, size_t count, u32 n_components, u32 n_limbs) {
     if (!count) return 0;
     const DecryptArgs a{p->d_mods_f64, d_out, d_ct, d_secret, p->logn, n_limbs};
@@ -246,6 +315,23 @@ extern "C" int hexl_rlwe_encrypt(hexl_ks_plan* p, uint64_t* d_out, const uint64_
     if (d_pt && hx_ranges_overlap(d_out, bytes, d_pt, pt.bytes)) return HEXL_E_BADARG;
     HX_CHECK(hipSetDevice(p->ctx->device));
     return hx_launch_rlwe_encrypt(p, d_out, d_pt, pt.stride != 0, d_secret, seed, stream, first, count, (u32)n_limbs);
+}
+
+// TERNARY index c and CBD21 indices 2c, 2c + 1 for c < first + count: first + count <= MAX_INDEX / 2 keeps the latter below MAX_INDEX
+static bool pk_index_ok(u64 first, size_t count) { return first <= hxs::MAX_INDEX / 2 && count <= hxs::MAX_INDEX / 2 - first; }
+
+extern "C" int hexl_pk_encrypt(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_pt, size_t pt_batch, const uint64_t* d_pk,
+                               uint64_t pk_limbs, const uint32_t seed[8], uint64_t stream, uint64_t first, size_t count, uint64_t n_limbs) {
+    size_t bytes;
+    if (!d_out || !d_pk || !seed || !rl_plan_ok(p, count, 2, n_limbs, &bytes) || !pk_index_ok(first, count)) return HEXL_E_BADARG;
+    if (!hx_in_range(pk_limbs, n_limbs, p->K)) return HEXL_E_BADARG;
+    const size_t per = size_t(n_limbs) * p->n * sizeof(u64);
+    HxPtBatch pt;
+    if (d_pt && !hx_pt_batch(pt_batch, count, per, &pt)) return HEXL_E_BADARG;
+    if (hx_ranges_overlap(d_out, bytes, d_pk, size_t(2) * pk_limbs * p->n * sizeof(u64))) return HEXL_E_BADARG;
+    if (d_pt && hx_ranges_overlap(d_out, bytes, d_pt, pt.bytes)) return HEXL_E_BADARG;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    return hx_launch_pk_encrypt(p, d_out, d_pt, pt.stride != 0, d_pk, (u32)pk_limbs, seed, stream, first, count, (u32)n_limbs);
 }
 
 extern "C" int hexl_rlwe_decrypt(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_ct, const uint64_t* d_secret, size_t count,

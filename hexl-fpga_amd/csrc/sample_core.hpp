@@ -1,5 +1,6 @@
-// sample_core.hpp -- the random streams of hexl_sample / hexl_rlwe_encrypt, one source for the kernels (rlwe.hip)
-// and for the host (tests/cpp/sample_selftest.cpp replays it against RFC 8439's vector and unsigned __int128), like f64_arith.hpp.
+// sample_core.hpp -- the random streams of hexl_sample / hexl_rlwe_encrypt / hexl_pk_encrypt, one source for
+// the kernels (rlwe.hip) and for the host (tests/cpp/sample_selftest.cpp and pk_selftest.cpp replay it against RFC 8439's vector and
+// unsigned __int128), like f64_arith.hpp.
 //
 // ChaCha20 in counter mode, the 20-round block function of RFC 8439 on this 16-word state:
 //   words 0-3    0x61707865 0x3320646e 0x79622d32 0x6b206574
@@ -106,6 +107,25 @@ HX_HD double encrypt_c0(double a, double s, double e, double pt, const hxf::Mod 
 // |product| <= 0.7p, reduced, then lc_add's |acc + u| <= 1.5p + 2
 HX_HD double horner(double acc, double sr, double c, const hxf::Mod m) {
     return hxf::lc_add(hxf::reduce(hxf::mul_mod(acc, sr, m), m), c, m);
+}
+
+// ---- the scalar chain of k_pk_encrypt (hexl_pk_encrypt), all operands canonical words as doubles (0 <= . < p);
+// tests/cpp/pk_selftest.cpp replays it against 128-bit integers and asserts every bound named here ----
+// a factor as both products take it: canonical -> centred, |.| <= p/2 + 2, mul_mod's operand range. u is converted ONCE per word and
+// meets pk0 and pk1.
+HX_HD double pk_operand(double x, const hxf::Mod m) { return hxf::reduce(x, m); }
+// (key u) mod p, centred: keyr and ur outputs of pk_operand, so |mul_mod| <= 0.7p (f64_arith.hpp; 0.875p by the coarser count of
+// ts_mac's note), which the reduce brings back to |.| <= p/2 + 2 -- the partial sum lc_add is bounded for
+HX_HD double pk_product(double keyr, double ur, const hxf::Mod m) { return hxf::reduce(hxf::mul_mod(keyr, ur, m), m); }
+// c0 = (pk0 u + e0 + pt) mod p, canonical: each lc_add takes a centred sum (|.| <= p/2 + 2) and a canonical word of [0, p),
+// |sum| <= 1.5p + 2 < 2^53, exact and inside reduce's domain, and leaves |.| <= p/2 + 2 again, which is what lc_finish lifts. pt = 0.0
+// for an encryption of zero: the same chain.
+HX_HD double pk_c0(double pk0r, double ur, double e0, double pt, const hxf::Mod m) {
+    return hxf::lc_finish(hxf::lc_add(hxf::lc_add(pk_product(pk0r, ur, m), e0, m), pt, m), m);
+}
+// c1 = (pk1 u + e1) mod p, canonical: one lc_add on the same bounds
+HX_HD double pk_c1(double pk1r, double ur, double e1, const hxf::Mod m) {
+    return hxf::lc_finish(hxf::lc_add(pk_product(pk1r, ur, m), e1, m), m);
 }
 
 }  // namespace hxs

@@ -400,6 +400,9 @@ int hexl_ckks_decode(hexl_ks_plan* plan, double* d_slots, const uint64_t* d_in, 
  * share both. Distinct kinds never collide (the kind is part of the block counter), distinct streams and distinct indices neither.
  * hexl_ks_gen_keys (below) is such a call: it consumes the UNIFORM and CBD21 polynomials first ... first + L - 1 of its (seed, stream),
  * exactly as the key-shaped hexl_rlwe_encrypt it replaces -- never give two keys of one secret the same triple.
+ * hexl_pk_encrypt is another: for every instance c = first + b it consumes the TERNARY polynomial c and the CBD21 polynomials 2c and
+ * 2c + 1 of its (seed, stream). A (seed, stream) it uses must not be shared with hexl_sample, hexl_rlwe_encrypt or hexl_ks_gen_keys of
+ * the same key material (their CBD21 index c is its index 2c' or 2c' + 1 for some c'), and `first` advances by `count` between calls.
  *
  * The streams (normative): ChaCha20 in counter mode, the 20-round block function of RFC 8439 on the state
  *   words 0-3 the constants 0x61707865 0x3320646e 0x79622d32 0x6b206574 | words 4-11 seed[0..7] (the caller's 32 bytes as eight
@@ -428,25 +431,43 @@ int hexl_ckks_decode(hexl_ks_plan* plan, double* d_slots, const uint64_t* d_in, 
  *   hexl_rlwe_decrypt   d_out [count][n_limbs][n] WRITTEN with c0 + c1 s (+ c2 s^2 when n_components = 3) mod q_i, evaluated by
  *                       Horner; d_ct [count][n_components][n_limbs][n], n_components 2 or 3 (3: a product before relinearisation);
  *                       d_secret as above. The result is the plaintext plus the noise: hexl_ckks_decode takes it as it is.
+ *   hexl_pk_encrypt     encryption under a public key, fused. d_out [count][2][n_limbs][n] WRITTEN: for instance b, c = first + b,
+ *                         out[b][0] = pk0 u_c + e0_c + pt      out[b][1] = pk1 u_c + e1_c      modulo q_i, canonical words,
+ *                       u_c = the TERNARY polynomial c, e0_c and e1_c = the CBD21 polynomials 2c and 2c + 1 of (seed, stream), each
+ *                       entering as NTT_i(v mod q_i) as hexl_sample makes it. d_pk [2][pk_limbs][n] in NTT form, every word below its
+ *                       modulus, n_limbs <= pk_limbs <= K: (pk0, pk1) = (e - a s, a), exactly what hexl_rlwe_encrypt(d_pt = NULL,
+ *                       count = 1, n_limbs = pk_limbs) writes. Only the first n_limbs limbs of each component are read (the component
+ *                       stride is pk_limbs n): a key kept at K limbs serves every level. d_pt NULL (an encryption of zero, for
+ *                       re-randomisation) or [pt_batch][n_limbs][n], pt_batch = 1 or count, as for hexl_rlwe_encrypt. No secret is needed.
+ *                       Normative definition: word for word the composition
+ *                         U = hexl_sample(TERNARY, first, count);  E = hexl_sample(CBD21, 2 first, 2 count) viewed as [count][2][n_limbs][n];
+ *                         T = hexl_multiply_plain(ct = the key's first n_limbs limbs replicated per instance, pt = U, n_components = 2,
+ *                         pt_batch = count);  d_out = hexl_ct_lincomb(terms {T, E}, d_pt, pt_batch)
+ *                       -- four launches and a key-sized replica per instance, which this call replaces by the sampling launches and
+ *                       ONE combine kernel (four polynomial reads and two writes per instance and limb, the key from cache).
  * Key-shaped output: hexl_rlwe_encrypt with count = L (decomp_modulus_size), n_limbs = K, pt_batch = count writes [L][2][K][n] --
  * word for word the h_keys layout of hexl_ks_set_keys (key d at d 2 K n, word (k K + i) n + j). With
  *   pt[d][i] = [i == d] (P mod q_i) s'_i     P = the special prime, the plan's modulus K - 1; s' = the key being switched FROM
  * (s^2 for relinearisation, s(X^g) for the Galois key of g), the output is a switching key from s' to s: pt is L calls of
  * hexl_ct_lincomb on NTT(s') with per-limb weights. hexl_ks_set_keys_device (below) installs such a device buffer into a plan as it
  * is, and hexl_ks_gen_keys writes that very key straight into the plan without the buffer ever existing: no key has to cross the bus
- * (a download and hexl_ks_set_keys remain the way to keep a copy on the host). Public-key encryption is hexl_sample + hexl_multiply_plain +
- * hexl_ct_lincomb on a public key made here with d_pt = NULL.
+ * (a download and hexl_ks_set_keys remain the way to keep a copy on the host). Public-key encryption is hexl_pk_encrypt on a public key
+ * made here with d_pt = NULL and count = 1.
  * Common rules: FP64 plans only (every modulus < 2^52), n = 1024 ... 32768, 1 <= n_limbs <= K (the plan's first n_limbs moduli), no keys
  * needed. Asynchronous on the context's stream; the seed travels by value in the kernels' arguments, so every host array may be
  * reused as soon as the call returns. Precondition: every input word is below its modulus. Every output word is canonical.
  * HEXL_E_BADARG: a null plan, output, seed, secret or (decrypt) ciphertext -- count == 0 does not excuse it --, an unknown kind, a plan
  * on the integer kernels, n_limbs outside 1 ... K, pt_batch other than 1 or count when d_pt is given, n_components outside {2, 3},
  * first + count > 2^40 (this keeps every block index below 2^60), a size or a grid that overflows, any overlap of the output with an
- * input. count == 0 returns 0 after these checks and writes nothing.
+ * input. count == 0 returns 0 after these checks and writes nothing. hexl_pk_encrypt: the same list with the key in the secret's place,
+ * and pk_limbs outside n_limbs ... K, first + count > 2^39 (this keeps the CBD21 indices 2c + 1 below 2^40), any overlap of d_out with
+ * the key's full [2][pk_limbs][n] extent or with d_pt.
  * Device memory, kept in the plan and grow-only, shared with encode / decode: the small kinds and the error of an encryption pass
  * through one chunk of real coefficients (n doubles per instance), hexl_rlwe_encrypt also through the chunk's NTT-form error
  * (n_limbs x n words per instance); a chunk is 256 instances at n = 16384 and the same number of coefficients at every other n.
- * UNIFORM and hexl_rlwe_decrypt are one launch and keep nothing. */
+ * hexl_pk_encrypt passes the mask and the two errors of an instance through the same two buffers (3 n doubles and 3 x n_limbs x n
+ * words per instance) in chunks of a third of that -- 85 instances at n = 16384, 1365 at n = 1024 --, so it never holds more than a full
+ * chunk of hexl_rlwe_encrypt does (32 MiB + n_limbs x 32 MiB). UNIFORM and hexl_rlwe_decrypt are one launch and keep nothing. */
 #define HEXL_SAMPLE_UNIFORM 1
 #define HEXL_SAMPLE_TERNARY 2
 #define HEXL_SAMPLE_CBD21   3
@@ -454,6 +475,8 @@ int hexl_sample(hexl_ks_plan* plan, uint64_t* d_out, int kind, const uint32_t se
                 size_t count, uint64_t n_limbs);
 int hexl_rlwe_encrypt(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_pt, size_t pt_batch, const uint64_t* d_secret,
                       const uint32_t seed[8], uint64_t stream, uint64_t first, size_t count, uint64_t n_limbs);
+int hexl_pk_encrypt(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_pt, size_t pt_batch, const uint64_t* d_pk, uint64_t pk_limbs,
+                    const uint32_t seed[8], uint64_t stream, uint64_t first, size_t count, uint64_t n_limbs);
 int hexl_rlwe_decrypt(hexl_ks_plan* plan, uint64_t* d_out, const uint64_t* d_ct, const uint64_t* d_secret, size_t count,
                       uint64_t n_components, uint64_t n_limbs);
 /* Switching keys without a host round trip. Keys are per plan, and plans are per level and per Galois element: a rotation set keys every
