@@ -78,6 +78,13 @@ C_ABI = {
     "hexl_ks_set_keys_device": [_vp, _vp],
     "hexl_ks_gen_keys": [_vp, _vp, _i, _u64, _vp, _vp, _u64, _u64],
     "hexl_ks_scratch_bytes": [_vp, _sz],
+    "hexl_hks_create": [_vp, _u64, ctypes.POINTER(_vp)],
+    "hexl_hks_destroy": [_vp],
+    "hexl_hks_set_keys_device": [_vp, _vp],
+    "hexl_hks_keyswitch": [_vp, _vp, _vp, _sz, _u64],
+    "hexl_hks_relinearize": [_vp, _vp, _vp, _sz, _u64],
+    "hexl_hks_rotate": [_vp, _vp, _vp, _sz, _u64, _u64],
+    "hexl_hks_scratch_bytes": [_vp, _sz],
     "hexl_ntt_fwd_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64],
     "hexl_ntt_inv_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64, _u64, _u64],
     "hexl_dyadic_multiply_host": [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _sz, _u64,
@@ -118,7 +125,7 @@ def lib() -> ctypes.CDLL:
         for name, args in C_ABI.items():
             fn = getattr(_lib, name)
             fn.argtypes = args
-            fn.restype = _sz if name in ("hexl_ks_scratch_bytes", "hexl_lt_bsgs_scratch_bytes") else _i
+            fn.restype = _sz if name in ("hexl_ks_scratch_bytes", "hexl_lt_bsgs_scratch_bytes", "hexl_hks_scratch_bytes") else _i
     return _lib
 
 
@@ -243,6 +250,7 @@ class KeySwitchPlan:
                  twiddles=None):
         self.ctx, self.n, self.L, self.K = ctx, n, L, K
         mod = np.ascontiguousarray(moduli, dtype=np.uint64)
+        self.moduli = [int(q) for q in mod[:K]]
         msf = np.ascontiguousarray(modswitch, dtype=np.uint64)
         tw = None if twiddles is None else np.ascontiguousarray(twiddles, dtype=np.uint64)
         h = _vp()
@@ -279,6 +287,29 @@ class KeySwitchPlan:
     def gen_galois_keys(self, secret, g: int, seed=None, stream: int = 0, first: int = 0) -> bytes:
         """the key rotate / the hoisted family need for the Galois element g"""
         return self.gen_keys(secret, KEY_FROM_GALOIS, galois_elt=g, seed=seed, stream=stream, first=first)
+
+    def gen_hybrid_key(self, out, secret, digit_limbs: int, from_poly, seed=None, stream: int = 0, first: int = 0) -> bytes:
+        """out[dnum][2][K][n] = the hybrid switching key (HybridKeySwitch.set_keys_device) from s' = from_poly ([K][n], NTT form) to
+        `secret` ([K][n]), dnum = ceil(L / digit_limbs): key d encrypts P [i in G_d] s' modulo q_i (0 modulo the special primes
+        L ... K - 1, whose product is P), G_d = the limbs d digit_limbs ... min((d + 1) digit_limbs, L) - 1. A wrapper, not a C entry
+        point: dnum calls of ct_lincomb on from_poly with per-limb weights, then ONE key-shaped rlwe_encrypt(count = dnum, n_limbs = K,
+        pt_batch = dnum). WARNING (include/hexl_mi355x.h): it consumes the UNIFORM and CBD21 polynomials first ... first + dnum - 1 of
+        (seed, stream) -- never give two keys of one secret the same triple. Returns the seed's bytes (None = os.urandom)."""
+        import torch
+        L, K, n = self.L, self.K, self.n
+        if not 1 <= digit_limbs <= L or K <= L:
+            raise ValueError("gen_hybrid_key: 1 <= digit_limbs <= L < K")
+        dnum = -(-L // digit_limbs)
+        P = 1
+        for q in self.moduli[L:K]:
+            P *= q
+        pt = torch.empty((dnum, K, n), dtype=torch.int64, device=from_poly.device)
+        for d in range(dnum):
+            w = [P % self.moduli[i] if d * digit_limbs <= i < min((d + 1) * digit_limbs, L) else 0 for i in range(K)]
+            self.ct_lincomb(pt[d], [from_poly], 1, 1, K, weights=[w])
+        raw = self.rlwe_encrypt(out, secret, dnum, K, pt=pt, pt_batch=dnum, seed=seed, stream=stream, first=first)
+        self._hybrid_pt = pt          # the launches are asynchronous on the context's stream: the plaintexts outlive this call
+        return raw
 
     def keyswitch(self, result, t_target, batch: int):
         _check(lib().hexl_keyswitch(self.h, _ptr(result), _ptr(t_target), batch), "hexl_keyswitch")
@@ -449,6 +480,44 @@ class KeySwitchPlan:
             self.h = None
 
 
+class HybridKeySwitch:
+    """The hybrid key switch (hexl_hks): digit_limbs = alpha data limbs per digit, the plan's limbs L ... K - 1 as special primes, one
+    installed key for every level n_limbs = 1 ... L. Attached to an FP64 `plan` created with K > L, which it borrows: close() it
+    before the plan. All launches are asynchronous on the context's stream."""
+
+    def __init__(self, plan: KeySwitchPlan, digit_limbs: int):
+        self.plan, self.alpha = plan, digit_limbs
+        self.dnum = -(-plan.L // digit_limbs) if digit_limbs >= 1 else 0
+        h = _vp()
+        _check(lib().hexl_hks_create(plan.h, digit_limbs, ctypes.byref(h)), "hexl_hks_create")
+        self.h = h
+
+    def set_keys_device(self, keys):
+        """keys: device tensor [dnum][2][K][n], key d at d*2*K*n, word (k*K + i)*n + j (KeySwitchPlan.gen_hybrid_key writes it); one
+        kernel on the context's stream, no host synchronisation -- an object in use may be re-keyed"""
+        _check(lib().hexl_hks_set_keys_device(self.h, _ptr(keys)), "hexl_hks_set_keys_device")
+
+    def keyswitch(self, result, t_target, batch: int, n_limbs: int):
+        """result[batch][2][n_limbs][n] += KeySwitch(t_target[batch][n_limbs][n]) mod q_i, as KeySwitchPlan.keyswitch"""
+        _check(lib().hexl_hks_keyswitch(self.h, _ptr(result), _ptr(t_target), batch, n_limbs), "hexl_hks_keyswitch")
+
+    def relinearize(self, out, ct3, batch: int, n_limbs: int):
+        """out[batch][2][n_limbs][n] = (c0, c1) + KeySwitch(c2) of ct3[batch][3][n_limbs][n]"""
+        _check(lib().hexl_hks_relinearize(self.h, _ptr(out), _ptr(ct3), batch, n_limbs), "hexl_hks_relinearize")
+
+    def rotate(self, out, ct, batch: int, n_limbs: int, g: int):
+        """out[batch][2][n_limbs][n] = (sigma_g(c0), 0) + KeySwitch(sigma_g(c1)); the keys switch from s(X^g) to s"""
+        _check(lib().hexl_hks_rotate(self.h, _ptr(out), _ptr(ct), batch, n_limbs, g), "hexl_hks_rotate")
+
+    def scratch_bytes(self, batch: int) -> int:
+        return lib().hexl_hks_scratch_bytes(self.h, batch)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().hexl_hks_destroy(self.h)
+            self.h = None
+
+
 def rotate_hoisted(plans, galois_elts, outs, ct, batch: int):
     """outs[r][batch][2][L][n] = (sigma_g(c0), 0) + ModDown(sum_d sigma_g(u_d) . key_r[d]) for g = galois_elts[r] and the keys of
     plans[r], with the mod-up u of ct's component 1 computed once for all of them (hexl_rotate_hoisted). Decrypts like
@@ -502,6 +571,6 @@ def lt_bsgs_scratch_bytes(plan, n_baby: int, batch: int) -> int:
 
 from .host_api import HexlFpga  # noqa: E402  (mirror of host/inc/hexl-fpga.h)
 
-__all__ = ["Context", "KeySwitchPlan", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform",
+__all__ = ["Context", "KeySwitchPlan", "HybridKeySwitch", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform",
            "linear_transform_bsgs", "lt_bsgs_scratch_bytes", "C_ABI", "SAMPLE_UNIFORM", "SAMPLE_TERNARY", "SAMPLE_CBD21", "KEY_FROM_POLY", "KEY_FROM_SQUARE", "KEY_FROM_GALOIS", "seed_words",
            "LIB_PATH", "ROOT"]

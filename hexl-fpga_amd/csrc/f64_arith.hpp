@@ -173,6 +173,35 @@ HX_HD double f64_to_residue(double c, const Mod m) {
     return reduce(mul_mod(reduce(a, m), reduce(2147483648.0, m), m) + reduce(b, m), m);
 }
 
+// ---- the scalar chains of the hybrid key switch (keyswitch_hybrid.hip k_hks_conv, k_hks_mac, k_hks_intt_sp, k_hks_down), here so that
+// tests/cpp/hks_selftest.cpp replays the kernels' own source against __int128 for every pairing of a source limb with a target limb ----
+// y = a (D / q_i)^-1 mod q_i, canonical: a a canonical word of limb i as a double (0 <= a < q_i < 2^52, exact), (hinv, hinv_p) the
+// inverse centred and fl(./q_i); m = q_i. a is inside mul_shoup's |x| <= 1.5p as it is, |product| <= p: reduce and lift take that.
+HX_HD double hks_digit(double a, double hinv, double hinv_p, const Mod m) { return lift(reduce(mul_shoup(a, hinv, hinv_p, m), m), m); }
+// One term of the fast base conversion into limb j: acc' = (acc + y w) mod q_j, centred. y is a canonical residue of ANOTHER modulus
+// (0 <= y < 2^52): it may exceed q_j many times over (a 52-bit source beside a 27-bit target: the quotient inside reduce has 25 bits)
+// or be far below it, so it is range-reduced into |.| <= q_j/2 + 2 first -- inside mul_shoup's 1.5p. (w, wp) = (D / q_i) mod q_j centred
+// and fl(./q_j); m = q_j. |product| <= (0.5 + 0.25 + 1/p) p, acc a partial sum as this function leaves it (|acc| <= p/2 + 2; 0 in front
+// of the first term): |acc + product| <= 1.25p + 4 < 2^53, an exact integer inside reduce's domain, and |acc'| <= p/2 + 2 again.
+HX_HD double hks_conv_term(double acc, double y, double w, double wp, const Mod m) {
+    return reduce(acc + mul_shoup(reduce(y, m), w, wp, m), m);
+}
+// the sum after its last term, plus fix, canonical: fix = 0 (mod-up) or q_j - (floor(P/2) mod q_j) in [1, q_j] (mod-down);
+// |acc + fix| <= 1.5p + 2 < 2^53.
+HX_HD double hks_conv_finish(double acc, double fix, const Mod m) { return lift(reduce(acc + fix, m), m); }
+// acc' = (acc + u key) mod p, centred: u a range-reduced transform output or a range-reduced input word, key a centred key word, acc as
+// this function leaves it -- all |.| <= p/2 + 2, mul_mod's operand range: |product| <= 0.875p (ts_mac's count), |sum| <= 1.375p + 2 < 2^53.
+HX_HD double hks_mac_term(double acc, double u, double key, const Mod m) { return reduce(acc + mul_mod(u, key, m), m); }
+// b = (v + half) mod q_s, canonical: v a range-reduced output of INTT_s (|v| <= q_s/2 + 2), half = floor(P/2) mod q_s in [0, q_s) -- a
+// RESIDUE here, where rs_round's is floor(q_l/2) itself; m = q_s. lift(v) + half < 2 q_s < 2^53.
+HX_HD double hks_round(double v, double half, const Mod m) { return lift(reduce(lift(v, m) + half, m), m); }
+// out = (old + (acc - w) P^-1) mod q_i, canonical: acc an output of hks_mac_term, w the range-reduced output of NTT_i (both
+// |.| <= q_i/2 + 2: |acc - w| <= p + 4, inside mul_shoup's 1.5p, |product| <= p), old the canonical word already there (0 <= old < p),
+// (pinv, pinv_p) = P^-1 mod q_i centred and fl(./q_i); m = q_i. |old + product| <= 2p < 2^53: exact and inside reduce's domain.
+HX_HD double hks_down(double old, double acc, double w, double pinv, double pinv_p, const Mod m) {
+    return lift(reduce(old + mul_shoup(acc - w, pinv, pinv_p, m), m), m);
+}
+
 // The STRICT butterflies (every value reduced after every operation) leave room above 2^52: the largest intermediate is the
 // inverse butterfly's |h - k p| <= (1.31 + 0.22) p for |d| = |X - Y| <= p + 4 (quotient from the product: three roundings of a
 // value near p/2, ulp 1/2), the forward's |X + t| <= 1.4 p, all below 2^53 up to p ~ 2^52.39. The standalone _NTT / _INTT fast

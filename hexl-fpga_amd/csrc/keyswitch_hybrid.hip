@@ -1,0 +1,567 @@
+// keyswitch_hybrid.hip -- the hybrid key switch: alpha data limbs per digit, n_p = K - L special primes, ONE installed
+// key for every level. A pipeline of its own beside the per-limb gadget of keyswitch_f64.hip / keyswitch_x.hip, attached to an FP64 plan
+// (hexl_hks borrows the plan's context, stream, moduli, constants and tables, and owns its keys, conversion constants and scratch).
+// Per chunk of instances at level l (T_l = {0 .. l-1} + S, S = {L .. K-1}, dl = ceil(l / alpha) digits), every line modulo its limb:
+//   1   a_i = INTT_i(t[i]), canonical words; ext_d[i] = t[i] for the digit d that holds i                              k_hks_intt
+//   2a  y_i = a_i (D/q_i)^-1;  x_d[j] = sum_{i in G_d} y_i (D/q_i mod q_j)  for every j in T_l outside the digit       k_hks_conv<false>
+//   2b  ext_d[j] = NTT_j(x_d[j]), in place                                                                             k_hks_fwd
+//   3   acc[k][j] = sum_d ext_d[j] key[d][k][j]                                                                        k_hks_mac
+//   4a  b_s = (INTT_s(acc[k][s]) + floor(P/2)) mod q_s for s in S, in place                                            k_hks_intt_sp
+//   4b  w_i = sum_s b_s (P/q_s)^-1 (P/q_s mod q_i) + fix_i  for i < l                                                  k_hks_conv<true>
+//   4c  result[k][i] += (acc[k][i] - NTT_i(w_i)) P^-1                                                                   k_hks_down
+// The transforms are one workgroup per polynomial on WgNttF64, limb-major, as k_rns_fwd / k_rns_inv (rns_ops.hip) and k_rs_intt /
+// k_rs_down (ckks_ops.hip); every intermediate lies at its LOGICAL index (coefficients in natural order, NTT form in the transforms'
+// output order), so the word-wise kernels between them need no index map and the keys keep the caller's order. The scalar chains
+// are f64_arith.hpp's hks_* functions (tests/cpp/hks_selftest.cpp replays them against __int128).
+#include "hexl_internal.hpp"
+#include "ntt_core_f64.hpp"
+#include "number_theory.hpp"
+
+using namespace hx;
+
+constexpr u32 HKS_MAX_LIMBS = 16;                                 // hexl_ks_plan::tier has 16 limbs
+constexpr u32 HKS_DOWN_ROW = 16;                                  // row of the conversion tables that holds the mod-down (S -> data limbs)
+struct HksSrc { double hinv, hinv_p; };                           // (D / q_i)^-1 mod q_i centred, and fl(. / q_i)
+struct HksWt { double w, wp; };                                   // (D / q_i) mod q_j centred, and fl(. / q_j)
+struct HksDown {                                                  // per plan limb
+    double pinv, pinv_p;     // i < L: P^-1 mod q_i centred, fl(. / q_i)
+    double fix;              // i < L: q_i - (floor(P/2) mod q_i), in [1, q_i]
+    double half;             // s in S: floor(P/2) mod q_s
+};
+
+struct hexl_hks {
+    hexl_ks_plan* plan = nullptr;
+    u32 alpha = 0, dnum = 0, np = 0;
+    bool have_keys = false;
+    HxDevBuf<double> d_keys;          // [dnum][2][K][n] centred, the caller's order
+    HxDevBuf<HksSrc> d_src;           // [17][16]: row l - 1 = level l (source limb i of its digit), row 16 = the mod-down (source s in S)
+    HxDevBuf<HksWt> d_wt;             // [17][16][16]: (row, source limb, target limb)
+    HxDevBuf<HksDown> d_down;         // [K]
+    // scratch of one chunk, grow-only (the stream drain rule of the context: everything runs on its stream)
+    HxDevBuf<u64> d_coef;             // [chunk][L][n]        a_i, canonical, natural order; after step 3: w of component 0 (doubles)
+    HxDevBuf<double> d_ext;           // [chunk][dnum][K][n]  x_d, then ext_d; after step 3 its first l rows per instance: w of component 1
+    HxDevBuf<double> d_acc;           // [chunk][2][K][n]     acc; rows of S: b_s after step 4a
+    HxDevBuf<u64> d_slice;            // rotate / relinearize: the key switch's input of one slice, [slice][L][n]
+    explicit hexl_hks(hexl_ks_plan* p)
+        : plan(p), d_keys(p->ctx), d_src(p->ctx), d_wt(p->ctx), d_down(p->ctx), d_coef(p->ctx), d_ext(p->ctx), d_acc(p->ctx), d_slice(p->ctx) {}
+};
+
+struct HksArgs {
+    const KsModF64* mods;       // [K]
+    const double* tables;       // [K][4][n] (keyswitch_f64.hip KsArgsF)
+    const HksSrc* src;          // [16]: the level's row (k_hks_conv<true>: the mod-down row)
+    const HksWt* wt;            // [16][16]
+    const HksDown* down;        // [K]
+    const double* keys;         // [dnum][2][K][n]
+    const u64* t;               // [nb][l][n]
+    u64* result;                // [nb][2][l][n]
+    u64* coef;                  // [nb][l][n]
+    double* ext;                // [nb][dl][T][n]
+    double* acc;                // [nb][2][T][n]
+    u32 L, K, l, T, dl, alpha, nb, logn;
+    unsigned long long limbmap; // nibble jT = plan limb of row jT of T_l (T_l is not a prefix of the plan's limbs when l < L)
+    unsigned long long tiermap; // LAZY = -1: nibble i = reduction period of limb i (keyswitch_f64.hip)
+};
+__device__ __forceinline__ u32 hks_limb(const HksArgs& a, u32 jT) { return u32(a.limbmap >> (4 * jT)) & 15u; }
+// w of (instance b, component k, limb i): component 0 in the coefficient buffer, component 1 in the first rows of the instance's ext block
+// (both are dead once step 3 has run, and dl * T >= l)
+__device__ __forceinline__ double* hks_w(const HksArgs& a, u32 b, u32 k, u32 i, size_t n) {
+    return k == 0 ? reinterpret_cast<double*>(a.coef) + (size_t(b) * a.l + i) * n : a.ext + (size_t(b) * a.dl * a.T + i) * n;
+}
+
+struct HksFwdOpt : NttOpt { static constexpr int XSD = 0; };      // centred inputs, FINAL's range reduction behind the tail (rns_ops.hip RnsFwdOpt)
+
+// step 1, one workgroup per (limb i < l, instance): k_rns_inv with the digit's own row of ext written on the way in
+template <int LOGN, int LOGE, int LAZY>
+__global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_intt(HksArgs a) {
+    using G = Geom<LOGN, LOGE>;
+    extern __shared__ __attribute__((aligned(16))) double ldsd[];
+    const int tid = threadIdx.x;
+    const u32 i = blockIdx.x / a.nb, b = blockIdx.x - i * a.nb;
+    const KsModF64 md = a.mods[i];
+    const Mod m = md.m;
+    const double* tb = a.tables + size_t(i) * 4 * G::N;
+    const u64* src = a.t + (size_t(b) * a.l + i) * G::N;
+    const u32 tB = u32(G::idxB(0, tid));
+    double v[G::E];
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) v[r] = hxf::reduce(hxf::to_f64((src + G::idxB(r, 0))[tB]), m);
+    // ext_d[i] = t[i] for the digit that holds i: NTT_i(x_d mod q_i) = t[i], no transform
+    double* own = a.ext + ((size_t(b) * a.dl + i / a.alpha) * a.T + i) * G::N;
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) (own + G::idxB(r, 0))[tB] = v[r];
+    with_tier<LAZY, LOGN == 14>(a.tiermap, i, [&](auto T) {
+        WgNttF64<LOGN, LOGE, decltype(T)::value, InvNoWpOpt<true>>::template inverse<true>(
+            v, ldsd, tid, tb + 2 * G::N, tb + 3 * G::N, m, md.sc);
+    });
+    u64* dst = a.coef + (size_t(b) * a.l + i) * G::N;
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) (dst + G::idxA(r, 0))[u32(tid)] = hxf::from_f64(hxf::lift(v[r], m));
+}
+
+// step 2b, one workgroup per (row jT of T_l, digit d, instance), in place: a workgroup holds its whole polynomial before it stores
+// (the re-deals' barriers lie between the last load and the first store). Rows inside their own digit were written by k_hks_intt.
+template <int LOGN, int LOGE, int LAZY>
+__global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_fwd(HksArgs a) {
+    using G = Geom<LOGN, LOGE>;
+    extern __shared__ __attribute__((aligned(16))) double ldsd[];
+    const int tid = threadIdx.x;
+    const u32 per = a.dl * a.nb;
+    const u32 jT = blockIdx.x / per, rem = blockIdx.x - jT * per;
+    const u32 d = rem / a.nb, b = rem - d * a.nb;
+    if (jT < a.l && jT / a.alpha == d) return;                   // (uniform)
+    const u32 j = hks_limb(a, jT);
+    const Mod m = a.mods[j].m;
+    const double* tb = a.tables + size_t(j) * 4 * G::N;
+    double* row = a.ext + ((size_t(b) * a.dl + d) * a.T + jT) * G::N;
+    double v[G::E];
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) v[r] = hxf::reduce((row + G::idxA(r, 0))[u32(tid)], m);
+    with_tier<LAZY, LOGN == 14>(a.tiermap, j, [&](auto T) {
+        WgNttF64<LOGN, LOGE, decltype(T)::value, HksFwdOpt>::template forward<true, true>(v, ldsd, tid, tb, tb + G::N, m);
+    });
+    const u32 tB = u32(G::idxB(0, tid));
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) (row + G::idxB(r, 0))[tB] = v[r];
+}
+
+// step 4a, one workgroup per (s in S, instance, component), in place: b_s = (INTT_s(acc[k][s]) + floor(P/2)) mod q_s, canonical
+template <int LOGN, int LOGE, int LAZY>
+__global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_intt_sp(HksArgs a) {
+    using G = Geom<LOGN, LOGE>;
+    extern __shared__ __attribute__((aligned(16))) double ldsd[];
+    const int tid = threadIdx.x;
+    const u32 si = blockIdx.x / (2 * a.nb), bk = blockIdx.x - si * 2 * a.nb;
+    const u32 s = a.L + si;
+    const KsModF64 md = a.mods[s];
+    const Mod m = md.m;
+    const double half = a.down[s].half;
+    const double* tb = a.tables + size_t(s) * 4 * G::N;
+    double* row = a.acc + (size_t(bk) * a.T + a.l + si) * G::N;
+    const u32 tB = u32(G::idxB(0, tid));
+    double v[G::E];
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) v[r] = (row + G::idxB(r, 0))[tB];               // an hks_mac_term output: |v| <= q_s/2 + 2
+    with_tier<LAZY, LOGN == 14>(a.tiermap, s, [&](auto T) {
+        WgNttF64<LOGN, LOGE, decltype(T)::value, InvNoWpOpt<true>>::template inverse<true>(
+            v, ldsd, tid, tb + 2 * G::N, tb + 3 * G::N, m, md.sc);
+    });
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) (row + G::idxA(r, 0))[u32(tid)] = hxf::hks_round(v[r], half, m);
+}
+
+// step 4c, one workgroup per (limb i < l, instance, component): k_rs_down's shape -- the transform of w, then the subtract-multiply-
+// accumulate epilogue on acc and the word `result` holds. acc and result are requested behind the transform (k_rs_down's LAZY < 0 form).
+template <int LOGN, int LOGE, int LAZY>
+__global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_down(HksArgs a) {
+    using G = Geom<LOGN, LOGE>;
+    extern __shared__ __attribute__((aligned(16))) double ldsd[];
+    const int tid = threadIdx.x;
+    const u32 i = blockIdx.x / (2 * a.nb), bk = blockIdx.x - i * 2 * a.nb;
+    const u32 b = bk >> 1, k = bk & 1;
+    const Mod m = a.mods[i].m;
+    const HksDown dn = a.down[i];
+    const double* tb = a.tables + size_t(i) * 4 * G::N;
+    const double* w = hks_w(a, b, k, i, G::N);
+    double v[G::E];
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) v[r] = hxf::reduce((w + G::idxA(r, 0))[u32(tid)], m);
+    with_tier<LAZY, LOGN == 14>(a.tiermap, i, [&](auto T) {
+        WgNttF64<LOGN, LOGE, decltype(T)::value, HksFwdOpt>::template forward<true, true>(v, ldsd, tid, tb, tb + G::N, m);
+    });
+    const double* pk = a.acc + (size_t(bk) * a.T + i) * G::N;
+    u64* res = a.result + (size_t(bk) * a.l + i) * G::N;
+    const u32 tB = u32(G::idxB(0, tid));
+    // in groups of eight registers: beside the 2^LOGE words of w, all of acc and result do not fit the registers of N = 32768
+    constexpr int GRP = G::E < 8 ? G::E : 8;
+#pragma unroll
+    for (int r0 = 0; r0 < G::E; r0 += GRP) {
+        double pv[GRP];
+        u64 old[GRP];
+#pragma unroll
+        for (int r = 0; r < GRP; ++r) { pv[r] = (pk + G::idxB(r0 + r, 0))[tB]; old[r] = (res + G::idxB(r0 + r, 0))[tB]; }
+#pragma unroll
+        for (int r = 0; r < GRP; ++r)
+            (res + G::idxB(r0 + r, 0))[tB] = hxf::from_f64(hxf::hks_down(hxf::to_f64(old[r]), pv[r], v[r0 + r], dn.pinv, dn.pinv_p, m));
+    }
+}
+
+// ---- the word-wise kernels: 256 lanes, a lane owns two adjacent indices (16-byte accesses), a workgroup 512 of them ----
+constexpr u32 HKS_THREADS = 256, HKS_LOG_PIECE = 9;
+static_assert(HKS_THREADS * 2 == 1u << HKS_LOG_PIECE, "a workgroup covers its piece exactly");
+static_assert(HKS_THREADS == HX_WW_THREADS, "hx_ww_grid(., ., ., HKS_LOG_PIECE) counts these workgroups");
+
+// steps 2a and 4b: the fast base conversion, no correction term. One workgroup per (instance, group, piece): group = digit d < dl
+// (mod-up: sources the words a_i of G_d, targets every row of T_l outside the digit) or component k (DOWN: sources b_s, s in S, targets
+// the data limbs i < l, fix_i added). Per coefficient the <= MAXS source words are loaded and y formed ONCE; every target limb reduces y
+// into its own range before the products (hks_conv_term). Moduli and weights of a target are wave-uniform: scalar loads.
+template <bool DOWN, int MAXS>
+__global__ __launch_bounds__(HKS_THREADS) void k_hks_conv(HksArgs a) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
+    const u32 lp = a.logn - HKS_LOG_PIECE;
+    const u32 grp = blockIdx.x >> lp, piece = blockIdx.x - (grp << lp);
+    const u32 ng = DOWN ? 2u : a.dl;
+    const u32 b = grp / ng, g = grp - b * ng;
+    const size_t n = size_t(1) << a.logn, c = (size_t(piece) << HKS_LOG_PIECE) + 2 * threadIdx.x;
+    const u32 s0 = DOWN ? a.L : g * a.alpha;                      // first source limb (plan index)
+    const u32 ns = DOWN ? a.K - a.L : (a.l - s0 < a.alpha ? a.l - s0 : a.alpha);
+    double y[MAXS][2];
+#pragma unroll
+    for (int si = 0; si < MAXS; ++si)
+        if (si < (int)ns) {
+            const u32 i = s0 + si;
+            const Mod m = a.mods[i].m;
+            const HksSrc hs = a.src[i];
+            double v[2];
+            if constexpr (DOWN) {
+                const d2 t = *reinterpret_cast<const d2*>(a.acc + ((size_t(b) * 2 + g) * a.T + a.l + si) * n + c);
+                v[0] = t.x; v[1] = t.y;
+            } else {
+                const u2 t = *reinterpret_cast<const u2*>(a.coef + (size_t(b) * a.l + i) * n + c);
+                v[0] = hxf::to_f64(t.x); v[1] = hxf::to_f64(t.y);
+            }
+            y[si][0] = hxf::hks_digit(v[0], hs.hinv, hs.hinv_p, m);
+            y[si][1] = hxf::hks_digit(v[1], hs.hinv, hs.hinv_p, m);
+        }
+    const u32 nt = DOWN ? a.l : a.T;
+    for (u32 jT = 0; jT < nt; ++jT) {
+        const u32 j = hks_limb(a, jT);
+        if (!DOWN && j >= s0 && j < s0 + ns) continue;            // inside the digit: k_hks_intt wrote the row
+        const Mod m = a.mods[j].m;
+        double acc0 = 0.0, acc1 = 0.0;
+#pragma unroll
+        for (int si = 0; si < MAXS; ++si)
+            if (si < (int)ns) {
+                const HksWt wt = a.wt[(s0 + si) * HKS_MAX_LIMBS + j];
+                acc0 = hxf::hks_conv_term(acc0, y[si][0], wt.w, wt.wp, m);
+                acc1 = hxf::hks_conv_term(acc1, y[si][1], wt.w, wt.wp, m);
+            }
+        const double fix = DOWN ? a.down[j].fix : 0.0;
+        const d2 o = {hxf::hks_conv_finish(acc0, fix, m), hxf::hks_conv_finish(acc1, fix, m)};
+        double* dst = DOWN ? hks_w(a, b, g, jT, n) : a.ext + ((size_t(b) * a.dl + g) * a.T + jT) * n;
+        *reinterpret_cast<d2*>(dst + c) = o;
+    }
+}
+
+// step 3: acc[b][k][jT] = sum_d ext[b][d][jT] . key[d][k][limb of jT], k_ksf_mac's structure with dl terms: a lane keeps the 2 dl key
+// vectors of its two indices in registers and walks the batch, so the keys are read once per launch and ext / acc exactly once.
+template <int MAXD>
+__global__ __launch_bounds__(HKS_THREADS) void k_hks_mac(HksArgs a) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    const u32 n = 1u << a.logn, pairs = n >> 1;
+    const u32 gid = blockIdx.x * blockDim.x + threadIdx.x;        // (row of T_l, pair)
+    const u32 jT = gid / pairs;
+    if (jT >= a.T) return;
+    const u32 c = (gid - jT * pairs) * 2;
+    const u32 j = hks_limb(a, jT);
+    const Mod m = a.mods[j].m;
+    d2 key[MAXD][2];
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d)
+        if (d < (int)a.dl) {
+            key[d][0] = *reinterpret_cast<const d2*>(a.keys + ((size_t(d) * 2 + 0) * a.K + j) * n + c);
+            key[d][1] = *reinterpret_cast<const d2*>(a.keys + ((size_t(d) * 2 + 1) * a.K + j) * n + c);
+        }
+    for (u32 b = blockIdx.y; b < a.nb; b += gridDim.y) {
+        const double* ub = a.ext + (size_t(b) * a.dl * a.T + jT) * n + c;
+        d2 acc0 = {0.0, 0.0}, acc1 = {0.0, 0.0};
+#pragma unroll
+        for (int d = 0; d < MAXD; ++d)
+            if (d < (int)a.dl) {
+                const d2 u = *reinterpret_cast<const d2*>(ub + size_t(d) * a.T * n);
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    acc0[e] = hxf::hks_mac_term(acc0[e], u[e], key[d][0][e], m);
+                    acc1[e] = hxf::hks_mac_term(acc1[e], u[e], key[d][1][e], m);
+                }
+            }
+        *reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 0) * a.T + jT) * n + c) = acc0;
+        *reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 1) * a.T + jT) * n + c) = acc1;
+    }
+}
+
+// the key install: the caller's [dnum][2][K][n] canonical words as centred doubles at the same place, one workgroup per (row, piece)
+struct HksInstallArgs { const KsModF64* mods; const u64* in; double* out; u32 K, logn; };
+__global__ __launch_bounds__(HKS_THREADS) void k_hks_install(HksInstallArgs a) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
+    const u32 lp = a.logn - HKS_LOG_PIECE;
+    const u32 row = blockIdx.x >> lp, piece = blockIdx.x - (row << lp);       // row = (d 2 + k) K + i
+    const u64 q = (u64)a.mods[row % a.K].m.p;
+    const size_t at = (size_t(row) << a.logn) + (size_t(piece) << HKS_LOG_PIECE) + 2 * threadIdx.x;
+    const u2 v = *reinterpret_cast<const u2*>(a.in + at);
+    const d2 o = {hxk::centre(v.x % q, q), hxk::centre(v.y % q, q)};
+    *reinterpret_cast<d2*>(a.out + at) = o;
+}
+
+// relinearize: ct3[nb][3][l][n] -> out[nb][2][l][n] (components 0-1) and t[nb][l][n] (component 2); words are moved, never interpreted
+struct HksMoveArgs { const u64* in; u64* out; u64* t; u32 l, logn; };
+__global__ __launch_bounds__(HKS_THREADS) void k_hks_split3(HksMoveArgs a) {
+    typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
+    const u32 lp = a.logn - HKS_LOG_PIECE;
+    const u32 br = blockIdx.x >> lp, piece = blockIdx.x - (br << lp);
+    const u32 b = br / (3 * a.l), r = br - b * 3 * a.l;           // r = k l + i
+    const size_t n = size_t(1) << a.logn, c = (size_t(piece) << HKS_LOG_PIECE) + 2 * threadIdx.x;
+    u64* row = r < 2 * a.l ? a.out + (size_t(b) * 2 * a.l + r) * n : a.t + (size_t(b) * a.l + (r - 2 * a.l)) * n;
+    *reinterpret_cast<u2*>(row + c) = *reinterpret_cast<const u2*>(a.in + (size_t(b) * 3 * a.l + r) * n + c);
+}
+// rotate, behind hx_launch_galois(out <- ct): component 1 of out[nb][2][l][n] moves to t[nb][l][n] and is zeroed
+__global__ __launch_bounds__(HKS_THREADS) void k_hks_take_c1(HksMoveArgs a) {
+    typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
+    const u32 lp = a.logn - HKS_LOG_PIECE;
+    const u32 bi = blockIdx.x >> lp, piece = blockIdx.x - (bi << lp);
+    const u32 b = bi / a.l, i = bi - b * a.l;
+    const size_t n = size_t(1) << a.logn, c = (size_t(piece) << HKS_LOG_PIECE) + 2 * threadIdx.x;
+    u64* c1 = a.out + ((size_t(b) * 2 + 1) * a.l + i) * n + c;
+    *reinterpret_cast<u2*>(a.t + (size_t(b) * a.l + i) * n + c) = *reinterpret_cast<const u2*>(c1);
+    const u2 zero = {0, 0};
+    *reinterpret_cast<u2*>(c1) = zero;
+}
+
+// ---- host side ----
+// the forward reduction period every limb of T_l shares, else -1 (hx_level_tier for a basis that is not a prefix)
+static int hks_level_tier(const hexl_ks_plan* p, u32 l) {
+    for (u32 i = 1; i < l; ++i)
+        if (p->tier[i] != p->tier[0]) return -1;
+    for (u32 s = p->L; s < p->K; ++s)
+        if (p->tier[s] != p->tier[0]) return -1;
+    return p->tier[0];
+}
+
+template <class F>
+static void hks_with_max(u32 count, F f) {                        // register room for 1, 2, 4, 8 or 16 sources / digits
+    if (count <= 1) f(hx_int<1>{});
+    else if (count <= 2) f(hx_int<2>{});
+    else if (count <= 4) f(hx_int<4>{});
+    else if (count <= 8) f(hx_int<8>{});
+    else f(hx_int<16>{});
+}
+static u32 hks_piece_grid(const hexl_ks_plan* p, size_t rows) { return (u32)(rows << (p->logn - HKS_LOG_PIECE)); }
+
+template <int LOGN, int LOGE, int LAZY>
+static int hks_run_chunk(hexl_hks* h, const HksArgs& a) {
+    using G = Geom<LOGN, LOGE>;
+    hexl_ks_plan* p = h->plan;
+    if (int rc = hx_lds_optin<k_hks_intt<LOGN, LOGE, LAZY>, k_hks_fwd<LOGN, LOGE, LAZY>, k_hks_intt_sp<LOGN, LOGE, LAZY>,
+                              k_hks_down<LOGN, LOGE, LAZY>>(p->ctx->device, G::LDS_USED)) return rc;
+    hipStream_t st = p->ctx->stream;
+    const dim3 wg(G::T), ww(HKS_THREADS);
+    const u32 nb = a.nb, np = a.K - a.L;
+    hipLaunchKernelGGL((k_hks_intt<LOGN, LOGE, LAZY>), dim3(a.l * nb), wg, G::LDS_USED, st, a);
+    hks_with_max(a.alpha < a.l ? a.alpha : a.l, [&](auto M) {
+        hipLaunchKernelGGL((k_hks_conv<false, decltype(M)::value>), dim3(hks_piece_grid(p, size_t(nb) * a.dl)), ww, 0, st, a);
+    });
+    hipLaunchKernelGGL((k_hks_fwd<LOGN, LOGE, LAZY>), dim3(a.T * a.dl * nb), wg, G::LDS_USED, st, a);
+    hks_with_max(a.dl, [&](auto M) {
+        const dim3 grid(a.T * (G::N / 2) / HKS_THREADS, nb < 8 ? nb : 8);
+        hipLaunchKernelGGL((k_hks_mac<decltype(M)::value>), grid, ww, 0, st, a);
+    });
+    hipLaunchKernelGGL((k_hks_intt_sp<LOGN, LOGE, LAZY>), dim3(np * 2 * nb), wg, G::LDS_USED, st, a);
+    HksArgs dn = a;
+    dn.src = h->d_src + size_t(HKS_DOWN_ROW) * HKS_MAX_LIMBS;
+    dn.wt = h->d_wt + size_t(HKS_DOWN_ROW) * HKS_MAX_LIMBS * HKS_MAX_LIMBS;
+    hks_with_max(np, [&](auto M) {
+        hipLaunchKernelGGL((k_hks_conv<true, decltype(M)::value>), dim3(hks_piece_grid(p, size_t(nb) * 2)), ww, 0, st, dn);
+    });
+    hipLaunchKernelGGL((k_hks_down<LOGN, LOGE, LAZY>), dim3(a.l * 2 * nb), wg, G::LDS_USED, st, a);
+    return (int)hipGetLastError();
+}
+
+static size_t hks_chunk_of(const hexl_hks* h, size_t batch) { return hx_ks_chunk_of(h->plan, batch); }
+static size_t hks_words_per_instance(const hexl_hks* h) {         // in units of n 64-bit words, at the full level
+    return size_t(h->plan->L) + size_t(h->dnum) * h->plan->K + 2 * size_t(h->plan->K);
+}
+
+// the key switch of `batch` instances at level l: d_result[batch][2][l][n] += KS(d_t[batch][l][n]), chunk by chunk on the context's stream
+static int hks_launch(hexl_hks* h, u64* d_result, const u64* d_t, size_t batch, u32 l) {
+    hexl_ks_plan* p = h->plan;
+    const size_t n = p->n, L = p->L, K = p->K;
+    const size_t chunk = hks_chunk_of(h, batch);
+    if (int rc = h->d_coef.reserve(chunk * L * n)) return rc;
+    if (int rc = h->d_ext.reserve(chunk * h->dnum * K * n)) return rc;
+    if (int rc = h->d_acc.reserve(chunk * 2 * K * n)) return rc;
+    HksArgs a{};
+    a.mods = p->d_mods_f64; a.tables = p->d_tables_f64;
+    a.src = h->d_src + size_t(l - 1) * HKS_MAX_LIMBS;
+    a.wt = h->d_wt + size_t(l - 1) * HKS_MAX_LIMBS * HKS_MAX_LIMBS;
+    a.down = h->d_down;
+    a.keys = h->d_keys;
+    a.coef = h->d_coef; a.ext = h->d_ext; a.acc = h->d_acc;
+    a.L = (u32)L; a.K = (u32)K; a.l = l; a.T = l + h->np;
+    a.dl = (l + h->alpha - 1) / h->alpha;
+    a.alpha = h->alpha; a.logn = p->logn;
+    for (u32 jT = 0; jT < a.T; ++jT) a.limbmap |= (unsigned long long)(jT < l ? jT : L + (jT - l)) << (4 * jT);
+    a.tiermap = hx_tiermap(p);
+    const int lazy = hks_level_tier(p, l);
+    return hx_for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
+        a.t = d_t + b0 * l * n;
+        a.result = d_result + b0 * 2 * l * n;
+        a.nb = (u32)nb;
+        return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return hks_run_chunk<N, E, Z>(h, a); });
+    });
+}
+
+// conversion constants for every level, exact integer work: per (level, digit, limb) the two weights, and the mod-down's
+static int hks_constants(hexl_hks* h) {
+    const hexl_ks_plan* p = h->plan;
+    const u32 L = p->L, K = p->K, alpha = h->alpha;
+    const std::vector<u64>& q = p->moduli;
+    std::vector<HksSrc> src(size_t(HKS_DOWN_ROW + 1) * HKS_MAX_LIMBS, HksSrc{0.0, 0.0});
+    std::vector<HksWt> wt(size_t(HKS_DOWN_ROW + 1) * HKS_MAX_LIMBS * HKS_MAX_LIMBS, HksWt{0.0, 0.0});
+    // the sources lo ... hi - 1 convert into the targets of `targets`: (D / q_i)^-1 mod q_i and (D / q_i) mod q_j, D their product
+    auto fill = [&](u32 row, u32 lo, u32 hi, const std::vector<u32>& targets) {
+        for (u32 i = lo; i < hi; ++i) {
+            auto hat_mod = [&](u64 m) {
+                u64 r = 1 % m;
+                for (u32 o = lo; o < hi; ++o)
+                    if (o != i) r = hxnt::mulmod(r, q[o] % m, m);
+                return r;
+            };
+            const double hinv = hx_centre(hxnt::invmod(hat_mod(q[i]), q[i]), q[i]);
+            src[size_t(row) * HKS_MAX_LIMBS + i] = HksSrc{hinv, hinv / (double)q[i]};
+            for (u32 j : targets) {
+                if (j >= lo && j < hi) continue;
+                const double w = hx_centre(hat_mod(q[j]), q[j]);
+                wt[(size_t(row) * HKS_MAX_LIMBS + i) * HKS_MAX_LIMBS + j] = HksWt{w, w / (double)q[j]};
+            }
+        }
+    };
+    for (u32 l = 1; l <= L; ++l) {
+        std::vector<u32> basis;
+        for (u32 j = 0; j < l; ++j) basis.push_back(j);
+        for (u32 s = L; s < K; ++s) basis.push_back(s);
+        for (u32 lo = 0; lo < l; lo += alpha) fill(l - 1, lo, lo + alpha < l ? lo + alpha : l, basis);
+    }
+    std::vector<u32> data;
+    for (u32 i = 0; i < L; ++i) data.push_back(i);
+    fill(HKS_DOWN_ROW, L, K, data);
+    std::vector<HksDown> down(K, HksDown{0.0, 0.0, 0.0, 0.0});
+    for (u32 i = 0; i < K; ++i) {
+        u64 P = 1 % q[i];
+        for (u32 s = L; s < K; ++s) P = hxnt::mulmod(P, q[s] % q[i], q[i]);
+        // floor(P / 2) = (P - 1) / 2 for an odd P: ((P mod q) - 1) (q + 1) / 2 mod q
+        const u64 half = hxnt::mulmod((P + q[i] - 1) % q[i], (q[i] + 1) / 2, q[i]);
+        if (i < L) {
+            const double pinv = hx_centre(hxnt::invmod(P, q[i]), q[i]);
+            down[i] = HksDown{pinv, pinv / (double)q[i], (double)(q[i] - half), 0.0};
+        } else {
+            down[i].half = (double)half;
+        }
+    }
+    if (int rc = h->d_src.upload_once(src.data(), src.size())) return rc;
+    if (int rc = h->d_wt.upload_once(wt.data(), wt.size())) return rc;
+    return h->d_down.upload_once(down.data(), down.size());
+}
+
+// ---- entry points of include/hexl_mi355x.h ----
+static bool hks_galois_elt_ok(u64 g, u64 n) { return (g & 1) && g < 2 * n; }
+// the checks the three launching entry points share: handle, plan, level; *bytes = the size of [batch][comps][n_limbs][n] words
+static bool hks_call_ok(const hexl_hks* h, size_t batch, u64 n_limbs, u64 comps, size_t* bytes) {
+    if (!h || !hx_f64_plan_ok(h->plan, n_limbs, 1, h->plan->L)) return false;
+    const hexl_ks_plan* p = h->plan;
+    if (!hx_words_bytes(batch, comps, n_limbs, p->n, bytes)) return false;
+    const size_t chunk = hks_chunk_of(h, batch);
+    size_t scratch;
+    if (!hx_words_bytes(chunk, 1, hks_words_per_instance(h), p->n, &scratch)) return false;
+    // the largest grids of a chunk: one workgroup per (row of T_l, digit, instance), one per (instance, 3 l rows, piece)
+    return hx_wg_grid_ok(chunk, u64(p->K) * h->dnum) && chunk <= HX_MAX_GRID / (size_t(3 * p->L) << (p->logn - HKS_LOG_PIECE));
+}
+
+extern "C" int hexl_hks_create(hexl_ks_plan* p, uint64_t digit_limbs, hexl_hks** out) {
+    if (!out) return HEXL_E_BADARG;
+    *out = nullptr;
+    if (!hx_f64_plan_ok(p) || p->K <= p->L || p->K > HKS_MAX_LIMBS || !hx_in_range(digit_limbs, 1, p->L)) return HEXL_E_BADARG;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    hexl_hks* h = new hexl_hks(p);
+    h->alpha = (u32)digit_limbs;
+    h->dnum = (p->L + h->alpha - 1) / h->alpha;
+    h->np = p->K - p->L;
+    int rc = hks_constants(h);
+    if (!rc) rc = h->d_keys.reserve(size_t(h->dnum) * 2 * p->K * p->n);
+    if (rc) { delete h; return rc; }
+    *out = h;
+    return 0;
+}
+
+extern "C" int hexl_hks_destroy(hexl_hks* h) {
+    if (!h) return HEXL_E_BADARG;
+    (void)hipSetDevice(h->plan->ctx->device);
+    (void)hipStreamSynchronize(h->plan->ctx->stream);             // the buffers go with the object: nothing may still use them
+    delete h;
+    return 0;
+}
+
+extern "C" int hexl_hks_set_keys_device(hexl_hks* h, const uint64_t* d_keys) {
+    if (!h || !d_keys) return HEXL_E_BADARG;
+    const hexl_ks_plan* p = h->plan;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    const HksInstallArgs a{p->d_mods_f64, d_keys, h->d_keys, p->K, p->logn};
+    hipLaunchKernelGGL(k_hks_install, dim3(hks_piece_grid(p, size_t(h->dnum) * 2 * p->K)), dim3(HKS_THREADS), 0, p->ctx->stream, a);
+    if (int rc = (int)hipGetLastError()) return rc;
+    h->have_keys = true;
+    return 0;
+}
+
+extern "C" int hexl_hks_keyswitch(hexl_hks* h, uint64_t* d_result, const uint64_t* d_t_target, size_t batch, uint64_t n_limbs) {
+    size_t t_bytes;
+    if (!d_result || !d_t_target || !hks_call_ok(h, batch, n_limbs, 1, &t_bytes)) return HEXL_E_BADARG;
+    if (hx_ranges_overlap(d_result, 2 * t_bytes, d_t_target, t_bytes)) return HEXL_E_BADARG;
+    if (!h->have_keys) return HEXL_E_NOKEYS;
+    if (!batch) return 0;
+    HX_CHECK(hipSetDevice(h->plan->ctx->device));
+    return hks_launch(h, d_result, d_t_target, batch, (u32)n_limbs);
+}
+
+// The slice loop of hexl_rotate / hexl_relinearize: fill(b0, nb, out, t) writes what the key switch adds into to `out` and its input to
+// the slice buffer; everything runs on the context's stream, so the next slice's fill is behind this slice's key switch.
+template <class F>
+static int hks_slices(hexl_hks* h, u64* d_out, size_t batch, u32 l, F fill) {
+    const size_t n = h->plan->n;
+    const size_t slice = hks_chunk_of(h, batch);
+    if (int rc = h->d_slice.reserve(slice * h->plan->L * n)) return rc;
+    return hx_for_chunks(batch, slice, [&](size_t b0, size_t nb) {
+        u64* out = d_out + b0 * 2 * l * n;
+        if (int rc = fill(b0, nb, out, (u64*)h->d_slice)) return rc;
+        return hks_launch(h, out, h->d_slice, nb, l);
+    });
+}
+
+extern "C" int hexl_hks_relinearize(hexl_hks* h, uint64_t* d_out, const uint64_t* d_ct3, size_t batch, uint64_t n_limbs) {
+    size_t in_bytes;
+    if (!d_out || !d_ct3 || !hks_call_ok(h, batch, n_limbs, 3, &in_bytes)) return HEXL_E_BADARG;
+    if (hx_ranges_overlap(d_out, in_bytes / 3 * 2, d_ct3, in_bytes)) return HEXL_E_BADARG;
+    if (!h->have_keys) return HEXL_E_NOKEYS;
+    if (!batch) return 0;
+    hexl_ks_plan* p = h->plan;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    const size_t n = p->n, l = n_limbs;
+    return hks_slices(h, d_out, batch, (u32)l, [&](size_t b0, size_t nb, u64* out, u64* t) {
+        const HksMoveArgs a{d_ct3 + b0 * 3 * l * n, out, t, (u32)l, p->logn};
+        hipLaunchKernelGGL(k_hks_split3, dim3(hks_piece_grid(p, nb * 3 * l)), dim3(HKS_THREADS), 0, p->ctx->stream, a);
+        return (int)hipGetLastError();
+    });
+}
+
+extern "C" int hexl_hks_rotate(hexl_hks* h, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t n_limbs, uint64_t galois_elt) {
+    size_t bytes;
+    if (!d_out || !d_ct || !hks_call_ok(h, batch, n_limbs, 2, &bytes) || !hks_galois_elt_ok(galois_elt, h->plan->n)) return HEXL_E_BADARG;
+    if (hx_ranges_overlap(d_out, bytes, d_ct, bytes)) return HEXL_E_BADARG;      // a permutation cannot run in place
+    if (!h->have_keys) return HEXL_E_NOKEYS;
+    if (!batch) return 0;
+    hexl_ks_plan* p = h->plan;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    const size_t n = p->n, l = n_limbs;
+    return hks_slices(h, d_out, batch, (u32)l, [&](size_t b0, size_t nb, u64* out, u64* t) {
+        // out = (sigma_g(c0), sigma_g(c1)), then component 1 moves to the slice buffer and is zeroed
+        if (int rc = hx_launch_galois(p->ctx, out, d_ct + b0 * 2 * l * n, nb * 2 * l, p->logn, (u32)galois_elt)) return rc;
+        const HksMoveArgs a{nullptr, out, t, (u32)l, p->logn};
+        hipLaunchKernelGGL(k_hks_take_c1, dim3(hks_piece_grid(p, nb * l)), dim3(HKS_THREADS), 0, p->ctx->stream, a);
+        return (int)hipGetLastError();
+    });
+}
+
+extern "C" size_t hexl_hks_scratch_bytes(const hexl_hks* h, size_t batch) {
+    if (!h) return 0;
+    return hks_chunk_of(h, batch) * hks_words_per_instance(h) * h->plan->n * sizeof(u64);
+}

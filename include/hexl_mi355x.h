@@ -524,6 +524,65 @@ int hexl_ks_set_keys_device(hexl_ks_plan* plan, const uint64_t* d_keys);
 #define HEXL_KEY_FROM_GALOIS 2   /* s' = s(X^galois_elt): the key hexl_rotate / the hoisted family need for that element */
 int hexl_ks_gen_keys(hexl_ks_plan* plan, const uint64_t* d_secret, int from_kind, uint64_t galois_elt, const uint64_t* d_from,
                      const uint32_t seed[8], uint64_t stream, uint64_t first);
+/* Hybrid key switching: digit groups and several special primes. Every key switch above is the per-limb gadget: each
+ * of the L data limbs is a digit of its own and the plan's modulus K - 1 is the one special prime -- L*L + 3L + 2 transforms per
+ * instance, L*2*(L + 1)*n key words per key, and a second plan with a second key for every lower level. The hybrid gadget groups alpha
+ * limbs into one digit, uses n_p = K - L special primes and switches through ONE installed key at every level:
+ *   L + sum_d (L + n_p - |G_d|) + 2 n_p + 2L transforms at the full level (L = 12, alpha = 4, n_p = 4: 80 against 182), dnum*2*K*n key
+ *   words per key (96 n against 312 n).
+ *
+ * hexl_hks is attached to an FP64 plan (every modulus < 2^52, n = 1024 ... 32768) created with decomp_modulus_size = L data limbs and
+ * key_modulus_size = K > L: limbs L ... K - 1 are the special primes S, P their product. It borrows the plan's context, stream, moduli
+ * and tables -- destroy it BEFORE the plan -- and owns its keys, conversion constants and scratch. The plan itself is not changed:
+ * hexl_keyswitch and every other entry point run on it as before, with the plan's own keys.
+ *   digit_limbs = alpha, 1 <= alpha <= L; dnum = ceil(L / alpha); digit d covers the limbs G_d = {d alpha ... min((d + 1) alpha, L) - 1}
+ *   d_keys      DEVICE [dnum][2][K][n]: key d at d*2*K*n, word (k*K + i)*n + j -- the h_keys layout of hexl_ks_set_keys with dnum in
+ *               place of L. ALL K limbs are read. Precondition: NTT form, every word below its modulus. The plaintext of key d is
+ *               P [i in G_d] s' modulo q_i and 0 modulo the special primes, whatever the level: one key serves every level.
+ *               The install is one kernel on the context's stream, no host synchronisation, ordered like hexl_ks_set_keys_device:
+ *               install, launch, install, launch re-keys an object in use. d_keys may be reused once the kernel has run (stream order).
+ *   n_limbs = l, 1 <= l <= L: the level. d_t_target [batch][l][n]; d_result, d_out, d_ct [batch][2][l][n]; d_ct3 [batch][3][l][n]. At
+ *               level l the digits are G_d restricted to the limbs below l, d < ceil(l / alpha) (the last one may be partial), and the
+ *               basis is T_l = {0 ... l - 1} and S.
+ * Per instance, every line modulo its limb's modulus and every stored word canonical (normative):
+ *   1  a_i = INTT_i(t[i]) for i < l, in [0, q_i)
+ *   2  mod-up by fast base conversion, no correction term. For digit d, D = the product of q_i over the digit's limbs at level l:
+ *        y_i = a_i . ((D / q_i)^-1 mod q_i)
+ *        x_d[j] = sum_i y_i . ((D / q_i) mod q_j),  ext_d[j] = NTT_j(x_d[j])   for every j of T_l outside the digit
+ *        ext_d[j] = t[j]                                                          for j inside it
+ *      (x_d is a lift of the digit in [0, |G_d| D))
+ *   3  acc[k][j] = sum_d ext_d[j] . key[d][k][j]   for k in {0, 1}, j in T_l
+ *   4  mod-down with rounding: for s in S   b_s = (INTT_s(acc[k][s]) + (floor(P / 2) mod q_s)),  z_s = b_s . ((P / q_s)^-1 mod q_s);
+ *      for i < l   w_i = sum_s z_s . ((P / q_s) mod q_i)  and
+ *        out[k][i] = result[k][i] + (acc[k][i] - NTT_i((w_i + fix_i) mod q_i)) . (P^-1 mod q_i),  fix_i = q_i - (floor(P / 2) mod q_i)
+ * With alpha = 1 and K = L + 1 this is, term for term, the key switch of hexl_rotate_hoisted's description above, and d_keys is the
+ * hexl_ks_set_keys_device layout: hexl_hks_keyswitch at n_limbs = L then equals hexl_keyswitch on the same plan and the same device key
+ * buffer word for word (for a plan whose h_modswitch[i] is P^-1 mod q_i).
+ *   hexl_hks_keyswitch    adds the key switch of d_t_target into d_result modulo q_i, exactly as hexl_keyswitch does
+ *   hexl_hks_relinearize  d_out WRITTEN with (c0, c1) + KS(c2)
+ *   hexl_hks_rotate       d_out WRITTEN with (sigma_g(c0), 0) + KS(sigma_g(c1)), sigma_g the permutation of hexl_apply_galois
+ * All three are asynchronous on the context's stream, on one lane: the stream contract of hexl_ctx_set_stream holds as for any single
+ * launch. Precondition: every input word is below its modulus. This version does NOT raise the input-range flag (hexl_ks_range_check):
+ * the output words of an instance with an out-of-range word are unspecified and nothing reports it.
+ * Noise: the switched ciphertext decrypts to t . s' plus an error of infinity norm at most
+ *   21 n sum_d |G_d| D_d / P + (n_p + 1/2)(n + 1)     for CBD21 key errors and a ternary secret.
+ * P >= max_d D_d keeps the first term near 21 n alpha dnum; that choice of special primes is the caller's and is NOT checked.
+ * HEXL_E_BADARG: a null handle or pointer (batch == 0 does not excuse it), a plan on the integer kernels or with K = L, alpha outside
+ * 1 ... L, n_limbs outside 1 ... L, a galois_elt that is even or >= 2n, an output that overlaps an input, a size or a grid that
+ * overflows; then HEXL_E_NOKEYS before hexl_hks_set_keys_device; then batch == 0 returns 0.
+ * Device memory, owned by the object: the keys (dnum*2*K*n doubles), 74 KiB of constants for all levels (computed at create time), and
+ * grow-only scratch for one chunk of min(batch, chunk) instances, chunk as for hexl_keyswitch (256 at n = 16384, the same number of
+ * coefficients at other n; HEXL_KS_CHUNK): per instance L*n coefficient words, dnum*K*n extended doubles and 2*K*n accumulator doubles.
+ * hexl_hks_scratch_bytes(hks, batch) is that sum at the full level (a lower level uses less of it). hexl_hks_relinearize and
+ * hexl_hks_rotate keep one more grow-only buffer, the key switch's input of one slice: min(batch, chunk) x L x n words. */
+typedef struct hexl_hks hexl_hks;
+int hexl_hks_create(hexl_ks_plan* plan, uint64_t digit_limbs /* alpha */, hexl_hks** out);
+int hexl_hks_destroy(hexl_hks* hks);                 /* before the plan it borrows */
+int hexl_hks_set_keys_device(hexl_hks* hks, const uint64_t* d_keys);   /* DEVICE [dnum][2][K][n] */
+int hexl_hks_keyswitch(hexl_hks* hks, uint64_t* d_result, const uint64_t* d_t_target, size_t batch, uint64_t n_limbs);
+int hexl_hks_relinearize(hexl_hks* hks, uint64_t* d_out, const uint64_t* d_ct3, size_t batch, uint64_t n_limbs);
+int hexl_hks_rotate(hexl_hks* hks, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t n_limbs, uint64_t galois_elt);
+size_t hexl_hks_scratch_bytes(const hexl_hks* hks, size_t batch);
 /* Arithmetic tier per limb (introspection for logs and tests): tiers[i], i < key_modulus_size, = the forward transforms' range-
  * reduction period modulo q_i on the FP64 path -- 12 / 6 / 3 for q_i <= 2^49 / 2^50 / 2^51 (1 + 2^-7), 0 = every value reduced after
  * every operation (q_i up to 2^52); -1 for every limb of a plan on the integer kernels (a modulus >= 2^52). Every transform runs modulo
