@@ -85,6 +85,9 @@ C_ABI = {
     "hexl_hks_relinearize": [_vp, _vp, _vp, _sz, _u64],
     "hexl_hks_rotate": [_vp, _vp, _vp, _sz, _u64, _u64],
     "hexl_hks_scratch_bytes": [_vp, _sz],
+    "hexl_hks_rotate_hoisted": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz, ctypes.POINTER(_vp), _vp, _sz, _u64],
+    "hexl_hks_linear_transform": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_vp), _sz, _vp, _vp, _vp, _sz, _u64],
+    "hexl_hks_hoisted_scratch_bytes": [_vp, _sz],
     "hexl_ntt_fwd_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64],
     "hexl_ntt_inv_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64, _u64, _u64],
     "hexl_dyadic_multiply_host": [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _sz, _u64,
@@ -125,7 +128,8 @@ def lib() -> ctypes.CDLL:
         for name, args in C_ABI.items():
             fn = getattr(_lib, name)
             fn.argtypes = args
-            fn.restype = _sz if name in ("hexl_ks_scratch_bytes", "hexl_lt_bsgs_scratch_bytes", "hexl_hks_scratch_bytes") else _i
+            fn.restype = _sz if name in ("hexl_ks_scratch_bytes", "hexl_lt_bsgs_scratch_bytes", "hexl_hks_scratch_bytes",
+                                      "hexl_hks_hoisted_scratch_bytes") else _i
     return _lib
 
 
@@ -512,6 +516,10 @@ class HybridKeySwitch:
     def scratch_bytes(self, batch: int) -> int:
         return lib().hexl_hks_scratch_bytes(self.h, batch)
 
+    def hoisted_scratch_bytes(self, batch: int) -> int:
+        """scratch_bytes plus the buffer hks_rotate_hoisted / hks_linear_transform keep on their first object"""
+        return lib().hexl_hks_hoisted_scratch_bytes(self.h, batch)
+
     def close(self):
         if getattr(self, "h", None):
             lib().hexl_hks_destroy(self.h)
@@ -539,6 +547,29 @@ def linear_transform(plans, galois_elts, pts, out, ct, batch: int, pt_identity=N
         raise ValueError("linear_transform: one plan, one Galois element and one plaintext per rotation")
     _check(lib().hexl_linear_transform(_handles(plans), _u64_array(galois_elts), ptr_array(pts), len(plans), None if pt_identity is None else _ptr(pt_identity), _ptr(out),
                                        _ptr(ct), batch), "hexl_linear_transform")
+
+
+def hks_rotate_hoisted(hks_list, galois_elts, outs, ct, batch: int, n_limbs: int):
+    """outs[r][batch][2][n_limbs][n] = (sigma_g(c0), 0) + ModDown(sum_d sigma_g(ext_d) . key_r[d]) for g = galois_elts[r] and the hybrid
+    key of hks_list[r], with the extended digits ext of ct's component 1 computed once for all of them (hexl_hks_rotate_hoisted).
+    Decrypts like hks_list[r].rotate(outs[r], ct, batch, n_limbs, g) but is word-identical to it only for g = 1. The objects share one
+    plan and one alpha; the scratch is hks_list[0]'s."""
+    if not (len(hks_list) == len(galois_elts) == len(outs)):
+        raise ValueError("hks_rotate_hoisted: one object, one Galois element and one output per rotation")
+    _check(lib().hexl_hks_rotate_hoisted(_handles(hks_list), _u64_array(galois_elts), len(hks_list), ptr_array(outs), _ptr(ct), batch, n_limbs),
+           "hexl_hks_rotate_hoisted")
+
+
+def hks_linear_transform(hks_list, galois_elts, pts, pt_identity, out, ct, batch: int, n_limbs: int):
+    """out[batch][2][n_limbs][n] = sum_r pts[r] . Rotate_g_r(ct) + pt_identity . ct on the hybrid keys of hks_list[r], with the mod-up of
+    ct's component 1 AND the mod-down shared by all rotations (hexl_hks_linear_transform). Each pts[r] is [K][n]: the plaintext modulo
+    all K plan limbs in NTT form (plan.rns_ntt_fwd / plan.ckks_encode at K limbs), one encoding for every level; pt_identity is
+    [>= n_limbs][n] or None. The objects share one plan and one alpha; the scratch is hks_list[0]'s."""
+    if not (len(hks_list) == len(galois_elts) == len(pts)):
+        raise ValueError("hks_linear_transform: one object, one Galois element and one plaintext per rotation")
+    _check(lib().hexl_hks_linear_transform(_handles(hks_list), _u64_array(galois_elts), ptr_array(pts), len(hks_list),
+                                           None if pt_identity is None else _ptr(pt_identity), _ptr(out), _ptr(ct), batch, n_limbs),
+           "hexl_hks_linear_transform")
 
 
 def _opt_ptrs(items):
@@ -571,6 +602,6 @@ def lt_bsgs_scratch_bytes(plan, n_baby: int, batch: int) -> int:
 
 from .host_api import HexlFpga  # noqa: E402  (mirror of host/inc/hexl-fpga.h)
 
-__all__ = ["Context", "KeySwitchPlan", "HybridKeySwitch", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform",
+__all__ = ["Context", "KeySwitchPlan", "HybridKeySwitch", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform", "hks_rotate_hoisted", "hks_linear_transform",
            "linear_transform_bsgs", "lt_bsgs_scratch_bytes", "C_ABI", "SAMPLE_UNIFORM", "SAMPLE_TERNARY", "SAMPLE_CBD21", "KEY_FROM_POLY", "KEY_FROM_SQUARE", "KEY_FROM_GALOIS", "seed_words",
            "LIB_PATH", "ROOT"]

@@ -189,9 +189,9 @@ struct GaloisPtArgs {
     const KsModF64* mods;       // [K]
     const u64* ct;              // [nb][2][L][n]
     u64* out;                   // [nb][2][L][n]
-    const HxLtRot* rots;        // [n_rot]: plaintext [L + 1][n] (rows 0 ... L - 1 are read here) and Galois element
+    const HxLtRot* rots;        // [n_rot]: plaintext [> L][n] (rows 0 ... L - 1 are read here) and Galois element
     const u64* pt_id;           // [L][n]; nullptr: no identity term
-    u32* range_flag;            // raised for a ciphertext word read here that is not below its modulus
+    u32* range_flag;            // raised for a ciphertext word read here that is not below its modulus; nullptr: nothing is reported
     u32 n_rot, nb, L, logn;
 };
 constexpr u32 GPT_THREADS = 256, GPT_LOG_CHUNK = 9;     // two adjacent words per lane: 512 words of one polynomial per workgroup
@@ -240,14 +240,16 @@ __global__ __launch_bounds__(GPT_THREADS) void k_galois_c0_pt(GaloisPtArgs a) {
     for (int e = 0; e < 2; ++e) out0[e] = hxf::from_f64(hxf::lift(acc[e], m));
     *reinterpret_cast<u2*>(o0 + j) = out0;
     *reinterpret_cast<u2*>(o1 + j) = out1;
-    hxf::report_range(bad, a.range_flag);
+    if (a.range_flag) hxf::report_range(bad, a.range_flag);      // (uniform)
 }
 
+// n_limbs: the limbs of d_ct, d_out and d_pt_identity -- the plan's L, or the level of a hybrid caller (keyswitch_hybrid.hip), whose
+// plaintexts are [K][n] and which passes no flag
 int hx_launch_galois_c0_pt(hexl_ks_plan* p, u64* d_out, const u64* d_ct, const HxLtRot* d_rots, size_t n_rot, const u64* d_pt_identity,
-                           size_t nb) {
+                           size_t nb, u32 n_limbs, u32* d_range_flag) {
     if (!nb) return 0;
-    const GaloisPtArgs a{p->d_mods_f64, d_ct, d_out, d_rots, d_pt_identity, p->d_flag, (u32)n_rot, (u32)nb, p->L, p->logn};
-    const dim3 grid((u32)hx_ww_grid(p, nb, p->L, GPT_LOG_CHUNK)), block(GPT_THREADS);
+    const GaloisPtArgs a{p->d_mods_f64, d_ct, d_out, d_rots, d_pt_identity, d_range_flag, (u32)n_rot, (u32)nb, n_limbs, p->logn};
+    const dim3 grid((u32)hx_ww_grid(p, nb, n_limbs, GPT_LOG_CHUNK)), block(GPT_THREADS);
     if (d_pt_identity) hipLaunchKernelGGL((k_galois_c0_pt<true>), grid, block, 0, p->ctx->stream, a);
     else hipLaunchKernelGGL((k_galois_c0_pt<false>), grid, block, 0, p->ctx->stream, a);
     return (int)hipGetLastError();

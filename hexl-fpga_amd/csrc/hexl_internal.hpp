@@ -291,12 +291,13 @@ int hx_launch_galois_c0(hexl_ctx*, u64* d_out, const u64* d_ct, size_t nb, u32 L
 // hexl_linear_transform (keyswitch_f64.hip): the hoisted rotations weighted by plaintexts and summed in the extended basis, one mod-down
 // per chunk. HxLtRot: one rotation of the per-call device table (in the context's d_shared) that hx_launch_galois_c0_pt (ckks_ops.hip)
 // walks: d_out[nb][2][L][n] = (sum_r pt_r . sigma_{g_r}(c0) + pt_id . c0, pt_id . c1), canonical words, on the context's stream; the
-// range flag of `p` is raised for a ciphertext word it reads that is not below its modulus
-struct HxLtRot { const u64* pt; u64 g; };                       // pt: [L + 1][n], the kernel reads rows 0 ... L - 1
+// range flag given (the plan's d_flag; nullptr: none) is raised for a ciphertext word it reads that is not below its modulus. n_limbs:
+// the limbs of d_ct, d_out and d_pt_identity -- p->L, or the level of hexl_hks_linear_transform (keyswitch_hybrid.hip)
+struct HxLtRot { const u64* pt; u64 g; };                       // pt: [L + 1][n] ([K][n] for the hybrid caller), the kernel reads rows 0 ... n_limbs - 1
 int hx_launch_linear_transform(hexl_ks_plan* const* plans, const u64* galois_elts, const u64* const* d_pts, size_t n_rot,
                                const u64* d_pt_identity, u64* d_out, const u64* d_ct, size_t batch);
 int hx_launch_galois_c0_pt(hexl_ks_plan* p, u64* d_out, const u64* d_ct, const HxLtRot* d_rots, size_t n_rot, const u64* d_pt_identity,
-                           size_t nb);
+                           size_t nb, u32 n_limbs, u32* d_range_flag);
 // hexl_linear_transform_bsgs (keyswitch_f64.hip): the mod-up once, one key multiply-accumulate per baby step into the plan's baby store,
 // then per giant step a key-free weighted sum of the stored products, one mod-down into the plan's t buffer and one hoisted rotation
 // accumulated into d_out. `p0` (the first non-NULL plan, baby plans first) lends scratch, buffers, tier and range flag. Arguments checked

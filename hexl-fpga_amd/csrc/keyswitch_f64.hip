@@ -836,7 +836,7 @@ int hx_launch_linear_transform(hexl_ks_plan* const* plans, const u64* galois_elt
         const u64* ct = d_ct + b0 * run.per;
         u64* out = d_out + b0 * run.per;
         if (int rc = run.up(ct + half, nb)) return rc;
-        if (int rc = hx_launch_galois_c0_pt(p0, out, ct, (const HxLtRot*)c->d_shared.get(), n_rot, d_pt_identity, nb)) return rc;
+        if (int rc = hx_launch_galois_c0_pt(p0, out, ct, (const HxLtRot*)c->d_shared.get(), n_rot, d_pt_identity, nb, p0->L, p0->d_flag)) return rc;
         for (size_t r = 0; r < n_rot; ++r)
             if (int rc = run.mac(plans[r], (u32)galois_elts[r], r ? KSF_MAC_PT_ACC : KSF_MAC_PT_FIRST, d_pts[r], nullptr, nb)) return rc;
         return run.down(p0, out, nb);
@@ -916,7 +916,7 @@ int hx_launch_linear_transform_bsgs(hexl_ks_plan* p0, hexl_ks_plan* const* baby_
             const size_t cnt = off[j + 1] - off[j];
             const u32 g = (u32)giant_elts[j];
             u64* t = (j == 0 && g == 1) ? out : p0->d_bsgs_t;
-            if (int rc = hx_launch_galois_c0_pt(p0, t, ct, d_rots + off[j], cnt, d_pt_identity ? d_pt_identity[j] : nullptr, nb)) return rc;
+            if (int rc = hx_launch_galois_c0_pt(p0, t, ct, d_rots + off[j], cnt, d_pt_identity ? d_pt_identity[j] : nullptr, nb, p0->L, p0->d_flag)) return rc;
             if (cnt) {
                 if (int rc = run.sum(d_terms + off[j], cnt, nb)) return rc;
                 if (int rc = run.down(p0, t, nb)) return rc;        // accumulated into what the c0 kernel wrote

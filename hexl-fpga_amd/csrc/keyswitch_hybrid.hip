@@ -9,6 +9,9 @@
 //   4a  b_s = (INTT_s(acc[k][s]) + floor(P/2)) mod q_s for s in S, in place                                            k_hks_intt_sp
 //   4b  w_i = sum_s b_s (P/q_s)^-1 (P/q_s mod q_i) + fix_i  for i < l                                                  k_hks_conv<true>
 //   4c  result[k][i] += (acc[k][i] - NTT_i(w_i)) P^-1                                                                   k_hks_down
+// The hoisted callers (hexl_hks_rotate_hoisted, hexl_hks_linear_transform) run steps 1-2 ONCE per chunk on c1 of the
+// ciphertexts, read in place, and step 3 per rotation with sigma_g applied to ext on the way in and the keys of that rotation's object:
+//   3g  acc[k][j] = sum_d sigma_g(ext_d[j]) key_r[d][k][j]   (stored, or weighted by a plaintext and summed over the rotations)   k_hks_mac_galois
 // The transforms are one workgroup per polynomial on WgNttF64, limb-major, as k_rns_fwd / k_rns_inv (rns_ops.hip) and k_rs_intt /
 // k_rs_down (ckks_ops.hip); every intermediate lies at its LOGICAL index (coefficients in natural order, NTT form in the transforms'
 // output order), so the word-wise kernels between them need no index map and the keys keep the caller's order. The scalar chains
@@ -40,10 +43,13 @@ struct hexl_hks {
     // scratch of one chunk, grow-only (the stream drain rule of the context: everything runs on its stream)
     HxDevBuf<u64> d_coef;             // [chunk][L][n]        a_i, canonical, natural order; after step 3: w of component 0 (doubles)
     HxDevBuf<double> d_ext;           // [chunk][dnum][K][n]  x_d, then ext_d; after step 3 its first l rows per instance: w of component 1
+                                      //                      (the hoisted callers keep ext for the next rotation: d_w1)
     HxDevBuf<double> d_acc;           // [chunk][2][K][n]     acc; rows of S: b_s after step 4a
     HxDevBuf<u64> d_slice;            // rotate / relinearize: the key switch's input of one slice, [slice][L][n]
+    HxDevBuf<double> d_w1;            // the hoisted callers: w of component 1, [chunk][L][n] (grow-only, allocated at their first call)
     explicit hexl_hks(hexl_ks_plan* p)
-        : plan(p), d_keys(p->ctx), d_src(p->ctx), d_wt(p->ctx), d_down(p->ctx), d_coef(p->ctx), d_ext(p->ctx), d_acc(p->ctx), d_slice(p->ctx) {}
+        : plan(p), d_keys(p->ctx), d_src(p->ctx), d_wt(p->ctx), d_down(p->ctx), d_coef(p->ctx), d_ext(p->ctx), d_acc(p->ctx), d_slice(p->ctx),
+          d_w1(p->ctx) {}
 };
 
 struct HksArgs {
@@ -53,20 +59,22 @@ struct HksArgs {
     const HksWt* wt;            // [16][16]
     const HksDown* down;        // [K]
     const double* keys;         // [dnum][2][K][n]
-    const u64* t;               // [nb][l][n]
+    const u64* t;               // [nb][tstride][n], rows 0 ... l - 1 of an instance are read (tstride = l, or 2 l for c1 of a ciphertext in place)
     u64* result;                // [nb][2][l][n]
     u64* coef;                  // [nb][l][n]
     double* ext;                // [nb][dl][T][n]
     double* acc;                // [nb][2][T][n]
-    u32 L, K, l, T, dl, alpha, nb, logn;
+    double* w1;                 // [nb][l][n]: w of component 1 (the hoisted callers); nullptr: the first rows of the instance's ext block
+    u32 L, K, l, T, dl, alpha, nb, logn, tstride;
     unsigned long long limbmap; // nibble jT = plan limb of row jT of T_l (T_l is not a prefix of the plan's limbs when l < L)
     unsigned long long tiermap; // LAZY = -1: nibble i = reduction period of limb i (keyswitch_f64.hip)
 };
 __device__ __forceinline__ u32 hks_limb(const HksArgs& a, u32 jT) { return u32(a.limbmap >> (4 * jT)) & 15u; }
 // w of (instance b, component k, limb i): component 0 in the coefficient buffer, component 1 in the first rows of the instance's ext block
-// (both are dead once step 3 has run, and dl * T >= l)
+// (both are dead once step 3 has run, and dl * T >= l) -- or in a buffer of its own where ext has to survive step 4 (uniform)
 __device__ __forceinline__ double* hks_w(const HksArgs& a, u32 b, u32 k, u32 i, size_t n) {
-    return k == 0 ? reinterpret_cast<double*>(a.coef) + (size_t(b) * a.l + i) * n : a.ext + (size_t(b) * a.dl * a.T + i) * n;
+    if (k == 0) return reinterpret_cast<double*>(a.coef) + (size_t(b) * a.l + i) * n;
+    return a.w1 ? a.w1 + (size_t(b) * a.l + i) * n : a.ext + (size_t(b) * a.dl * a.T + i) * n;
 }
 
 struct HksFwdOpt : NttOpt { static constexpr int XSD = 0; };      // centred inputs, FINAL's range reduction behind the tail (rns_ops.hip RnsFwdOpt)
@@ -81,7 +89,7 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_intt(HksArgs a) {
     const KsModF64 md = a.mods[i];
     const Mod m = md.m;
     const double* tb = a.tables + size_t(i) * 4 * G::N;
-    const u64* src = a.t + (size_t(b) * a.l + i) * G::N;
+    const u64* src = a.t + (size_t(b) * a.tstride + i) * G::N;
     const u32 tB = u32(G::idxB(0, tid));
     double v[G::E];
 #pragma unroll
@@ -281,6 +289,78 @@ __global__ __launch_bounds__(HKS_THREADS) void k_hks_mac(HksArgs a) {
     }
 }
 
+// step 3 of the hoisted callers, one rotation: sum[b][k][jT] = sum_d sigma_g(ext[b][d][jT]) . key_r[d][k][limb of jT] -- k_hks_mac with ext
+// gathered. ext lies at its logical index, so word j of sigma_g(ext) is word galois_src(j) of ext, no position map. pi_g maps every
+// aligned block of 2^k indices onto an aligned block of 2^k (keyswitch_f64.hip k_ksf_mac_galois); with k = 1: the sources of a lane's two
+// adjacent indices c, c + 1 are the two words of ONE aligned pair, s and s ^ 1 -- (2 brv(c + 1) + 1) g = (2 brv(c) + 1) g + n g, and
+// n g = n (mod 2n) for an odd g, which flips the top bit of (e - 1) / 2 and so the lowest bit of the source. The gather is therefore one
+// 16-byte load at s & ~1 and a swap when s is odd: keys, plaintext, acc AND ext stay 16-byte accesses, and a wave's 64 sources are the
+// 1 KiB of one aligned block of 128 indices, whole cache lines in another order. g = 1 is served too (s = c, no swap).
+// What becomes of the reduced sum (an hks_mac_term output, i.e. a reduce output: what lt_mac / lt_mac_acc take as `inner`) is MODE:
+//   HKS_MAC_STORE     hexl_hks_rotate_hoisted: acc = sum
+//   HKS_MAC_PT_FIRST  hexl_hks_linear_transform, a chunk's first rotation: acc = pt[limb of jT] . sum (hxf::lt_mac), acc is not read
+//   HKS_MAC_PT_ACC    ... its later rotations: acc = acc + pt . sum (hxf::lt_mac_acc), the old words requested in front of the gather
+// pt is [K][n] canonical words in the transforms' output order: the lane's pair is converted once (hxf::lt_pt) and serves every instance
+// it walks. acc never leaves the extended basis between rotations, so step 4 runs once for all of them.
+struct HksRot { const double* keys; const u64* pt; u32 g; };      // the rotation's object's keys [dnum][2][K][n]; pt: the plaintext modes
+enum HksMacMode : int { HKS_MAC_STORE, HKS_MAC_PT_FIRST, HKS_MAC_PT_ACC };
+
+template <int MAXD, HksMacMode MODE>
+__global__ __launch_bounds__(HKS_THREADS) void k_hks_mac_galois(HksArgs a, HksRot rot) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
+    const u32 n = 1u << a.logn, pairs = n >> 1;
+    const u32 gid = blockIdx.x * blockDim.x + threadIdx.x;        // (row of T_l, pair)
+    const u32 jT = gid / pairs;
+    if (jT >= a.T) return;
+    const u32 c = (gid - jT * pairs) * 2;
+    const u32 s = galois_src(c, a.logn, rot.g);                   // the source of c; that of c + 1 is s ^ 1
+    const u32 sp = s & ~1u;
+    const bool swap = s & 1u;
+    const u32 j = hks_limb(a, jT);
+    const Mod m = a.mods[j].m;
+    d2 w = {0.0, 0.0};
+    if constexpr (MODE != HKS_MAC_STORE) {
+        const u2 t = *reinterpret_cast<const u2*>(rot.pt + size_t(j) * n + c);
+        w.x = hxf::lt_pt(hxf::to_f64(t.x), m); w.y = hxf::lt_pt(hxf::to_f64(t.y), m);
+    }
+    d2 key[MAXD][2];
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d)
+        if (d < (int)a.dl) {
+            key[d][0] = *reinterpret_cast<const d2*>(rot.keys + ((size_t(d) * 2 + 0) * a.K + j) * n + c);
+            key[d][1] = *reinterpret_cast<const d2*>(rot.keys + ((size_t(d) * 2 + 1) * a.K + j) * n + c);
+        }
+    for (u32 b = blockIdx.y; b < a.nb; b += gridDim.y) {
+        const double* ub = a.ext + (size_t(b) * a.dl * a.T + jT) * n + sp;
+        d2* p0 = reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 0) * a.T + jT) * n + c);
+        d2* p1 = reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 1) * a.T + jT) * n + c);
+        d2 prev0 = {0.0, 0.0}, prev1 = {0.0, 0.0};
+        if constexpr (MODE == HKS_MAC_PT_ACC) { prev0 = *p0; prev1 = *p1; }
+        d2 acc0 = {0.0, 0.0}, acc1 = {0.0, 0.0};
+#pragma unroll
+        for (int d = 0; d < MAXD; ++d)
+            if (d < (int)a.dl) {
+                const d2 v = *reinterpret_cast<const d2*>(ub + size_t(d) * a.T * n);
+                const d2 u = {swap ? v.y : v.x, swap ? v.x : v.y};
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    acc0[e] = hxf::hks_mac_term(acc0[e], u[e], key[d][0][e], m);
+                    acc1[e] = hxf::hks_mac_term(acc1[e], u[e], key[d][1][e], m);
+                }
+            }
+        if constexpr (MODE != HKS_MAC_STORE) {
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                acc0[e] = MODE == HKS_MAC_PT_FIRST ? hxf::lt_mac(acc0[e], w[e], m) : hxf::lt_mac_acc(acc0[e], w[e], prev0[e], m);
+                acc1[e] = MODE == HKS_MAC_PT_FIRST ? hxf::lt_mac(acc1[e], w[e], m) : hxf::lt_mac_acc(acc1[e], w[e], prev1[e], m);
+            }
+        }
+        *p0 = acc0;
+        *p1 = acc1;
+    }
+}
+
 // the key install: the caller's [dnum][2][K][n] canonical words as centred doubles at the same place, one workgroup per (row, piece)
 struct HksInstallArgs { const KsModF64* mods; const u64* in; double* out; u32 K, logn; };
 __global__ __launch_bounds__(HKS_THREADS) void k_hks_install(HksInstallArgs a) {
@@ -339,24 +419,58 @@ static void hks_with_max(u32 count, F f) {                        // register ro
 }
 static u32 hks_piece_grid(const hexl_ks_plan* p, size_t rows) { return (u32)(rows << (p->logn - HKS_LOG_PIECE)); }
 
+// A chunk's launches in three stages, all on the context's stream: steps 1-2 (up), step 3 (mac) and step 4 (down). The key switch runs
+// them back to back; the hoisted callers run `up` once per chunk and the other two per rotation, or `down` once (hks_hoist_*).
 template <int LOGN, int LOGE, int LAZY>
-static int hks_run_chunk(hexl_hks* h, const HksArgs& a) {
+static int hks_optin(hexl_hks* h) {
+    return hx_lds_optin<k_hks_intt<LOGN, LOGE, LAZY>, k_hks_fwd<LOGN, LOGE, LAZY>, k_hks_intt_sp<LOGN, LOGE, LAZY>,
+                        k_hks_down<LOGN, LOGE, LAZY>>(h->plan->ctx->device, Geom<LOGN, LOGE>::LDS_USED);
+}
+
+template <int LOGN, int LOGE, int LAZY>
+static int hks_stage_up(hexl_hks* h, const HksArgs& a) {
     using G = Geom<LOGN, LOGE>;
     hexl_ks_plan* p = h->plan;
-    if (int rc = hx_lds_optin<k_hks_intt<LOGN, LOGE, LAZY>, k_hks_fwd<LOGN, LOGE, LAZY>, k_hks_intt_sp<LOGN, LOGE, LAZY>,
-                              k_hks_down<LOGN, LOGE, LAZY>>(p->ctx->device, G::LDS_USED)) return rc;
+    if (int rc = hks_optin<LOGN, LOGE, LAZY>(h)) return rc;
     hipStream_t st = p->ctx->stream;
     const dim3 wg(G::T), ww(HKS_THREADS);
-    const u32 nb = a.nb, np = a.K - a.L;
+    const u32 nb = a.nb;
     hipLaunchKernelGGL((k_hks_intt<LOGN, LOGE, LAZY>), dim3(a.l * nb), wg, G::LDS_USED, st, a);
     hks_with_max(a.alpha < a.l ? a.alpha : a.l, [&](auto M) {
         hipLaunchKernelGGL((k_hks_conv<false, decltype(M)::value>), dim3(hks_piece_grid(p, size_t(nb) * a.dl)), ww, 0, st, a);
     });
     hipLaunchKernelGGL((k_hks_fwd<LOGN, LOGE, LAZY>), dim3(a.T * a.dl * nb), wg, G::LDS_USED, st, a);
+    return (int)hipGetLastError();
+}
+
+// one workgroup column per 512 indices of a row of T_l, up to 8 rows of workgroups share the batch (no transform: no geometry, no tier)
+static dim3 hks_mac_grid(const HksArgs& a) { return dim3(a.T * ((1u << a.logn) / 2) / HKS_THREADS, a.nb < 8 ? a.nb : 8); }
+static int hks_stage_mac(hexl_hks* h, const HksArgs& a) {
     hks_with_max(a.dl, [&](auto M) {
-        const dim3 grid(a.T * (G::N / 2) / HKS_THREADS, nb < 8 ? nb : 8);
-        hipLaunchKernelGGL((k_hks_mac<decltype(M)::value>), grid, ww, 0, st, a);
+        hipLaunchKernelGGL((k_hks_mac<decltype(M)::value>), hks_mac_grid(a), dim3(HKS_THREADS), 0, h->plan->ctx->stream, a);
     });
+    return (int)hipGetLastError();
+}
+static int hks_stage_mac_galois(hexl_hks* h, const HksArgs& a, const HksRot& rot, HksMacMode mode) {
+    hipStream_t st = h->plan->ctx->stream;
+    const dim3 grid = hks_mac_grid(a), ww(HKS_THREADS);
+    hks_with_max(a.dl, [&](auto M) {
+        constexpr int D = decltype(M)::value;
+        if (mode == HKS_MAC_STORE)         hipLaunchKernelGGL((k_hks_mac_galois<D, HKS_MAC_STORE>), grid, ww, 0, st, a, rot);
+        else if (mode == HKS_MAC_PT_FIRST) hipLaunchKernelGGL((k_hks_mac_galois<D, HKS_MAC_PT_FIRST>), grid, ww, 0, st, a, rot);
+        else                               hipLaunchKernelGGL((k_hks_mac_galois<D, HKS_MAC_PT_ACC>), grid, ww, 0, st, a, rot);
+    });
+    return (int)hipGetLastError();
+}
+
+template <int LOGN, int LOGE, int LAZY>
+static int hks_stage_down(hexl_hks* h, const HksArgs& a) {
+    using G = Geom<LOGN, LOGE>;
+    hexl_ks_plan* p = h->plan;
+    if (int rc = hks_optin<LOGN, LOGE, LAZY>(h)) return rc;
+    hipStream_t st = p->ctx->stream;
+    const dim3 wg(G::T), ww(HKS_THREADS);
+    const u32 nb = a.nb, np = a.K - a.L;
     hipLaunchKernelGGL((k_hks_intt_sp<LOGN, LOGE, LAZY>), dim3(np * 2 * nb), wg, G::LDS_USED, st, a);
     HksArgs dn = a;
     dn.src = h->d_src + size_t(HKS_DOWN_ROW) * HKS_MAX_LIMBS;
@@ -368,19 +482,27 @@ static int hks_run_chunk(hexl_hks* h, const HksArgs& a) {
     return (int)hipGetLastError();
 }
 
+template <int LOGN, int LOGE, int LAZY>
+static int hks_run_chunk(hexl_hks* h, const HksArgs& a) {
+    if (int rc = hks_stage_up<LOGN, LOGE, LAZY>(h, a)) return rc;
+    if (int rc = hks_stage_mac(h, a)) return rc;
+    return hks_stage_down<LOGN, LOGE, LAZY>(h, a);
+}
+
 static size_t hks_chunk_of(const hexl_hks* h, size_t batch) { return hx_ks_chunk_of(h->plan, batch); }
 static size_t hks_words_per_instance(const hexl_hks* h) {         // in units of n 64-bit words, at the full level
     return size_t(h->plan->L) + size_t(h->dnum) * h->plan->K + 2 * size_t(h->plan->K);
 }
 
-// the key switch of `batch` instances at level l: d_result[batch][2][l][n] += KS(d_t[batch][l][n]), chunk by chunk on the context's stream
-static int hks_launch(hexl_hks* h, u64* d_result, const u64* d_t, size_t batch, u32 l) {
-    hexl_ks_plan* p = h->plan;
-    const size_t n = p->n, L = p->L, K = p->K;
-    const size_t chunk = hks_chunk_of(h, batch);
+// the scratch of chunks of `chunk` instances and a chunk's kernel arguments at level l, all but the per-chunk pointers and nb
+static int hks_reserve(hexl_hks* h, size_t chunk) {
+    const size_t n = h->plan->n, L = h->plan->L, K = h->plan->K;
     if (int rc = h->d_coef.reserve(chunk * L * n)) return rc;
     if (int rc = h->d_ext.reserve(chunk * h->dnum * K * n)) return rc;
-    if (int rc = h->d_acc.reserve(chunk * 2 * K * n)) return rc;
+    return h->d_acc.reserve(chunk * 2 * K * n);
+}
+static HksArgs hks_args(const hexl_hks* h, u32 l) {
+    const hexl_ks_plan* p = h->plan;
     HksArgs a{};
     a.mods = p->d_mods_f64; a.tables = p->d_tables_f64;
     a.src = h->d_src + size_t(l - 1) * HKS_MAX_LIMBS;
@@ -388,11 +510,21 @@ static int hks_launch(hexl_hks* h, u64* d_result, const u64* d_t, size_t batch, 
     a.down = h->d_down;
     a.keys = h->d_keys;
     a.coef = h->d_coef; a.ext = h->d_ext; a.acc = h->d_acc;
-    a.L = (u32)L; a.K = (u32)K; a.l = l; a.T = l + h->np;
+    a.L = p->L; a.K = p->K; a.l = l; a.T = l + h->np;
     a.dl = (l + h->alpha - 1) / h->alpha;
-    a.alpha = h->alpha; a.logn = p->logn;
-    for (u32 jT = 0; jT < a.T; ++jT) a.limbmap |= (unsigned long long)(jT < l ? jT : L + (jT - l)) << (4 * jT);
+    a.alpha = h->alpha; a.logn = p->logn; a.tstride = l;
+    for (u32 jT = 0; jT < a.T; ++jT) a.limbmap |= (unsigned long long)(jT < l ? jT : p->L + (jT - l)) << (4 * jT);
     a.tiermap = hx_tiermap(p);
+    return a;
+}
+
+// the key switch of `batch` instances at level l: d_result[batch][2][l][n] += KS(d_t[batch][l][n]), chunk by chunk on the context's stream
+static int hks_launch(hexl_hks* h, u64* d_result, const u64* d_t, size_t batch, u32 l) {
+    hexl_ks_plan* p = h->plan;
+    const size_t n = p->n;
+    const size_t chunk = hks_chunk_of(h, batch);
+    if (int rc = hks_reserve(h, chunk)) return rc;
+    HksArgs a = hks_args(h, l);
     const int lazy = hks_level_tier(p, l);
     return hx_for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
         a.t = d_t + b0 * l * n;
@@ -564,4 +696,135 @@ extern "C" int hexl_hks_rotate(hexl_hks* h, uint64_t* d_out, const uint64_t* d_c
 extern "C" size_t hexl_hks_scratch_bytes(const hexl_hks* h, size_t batch) {
     if (!h) return 0;
     return hks_chunk_of(h, batch) * hks_words_per_instance(h) * h->plan->n * sizeof(u64);
+}
+
+// ---- the hoisted callers: many rotations of one ciphertext batch share steps 1-2 (hexl_hks_rotate_hoisted), and step 4 as well
+// (hexl_hks_linear_transform). One run works in hks[0]'s scratch, chunk after chunk, everything on the context's stream: one lane, so
+// the next chunk's mod-up overwrites ext behind the last multiply-accumulate that read it. The other objects lend their keys only. ----
+struct HksHoist {
+    hexl_hks* h0;
+    hexl_ks_plan* p;
+    size_t chunk, per;                                            // instances per chunk; words of one ciphertext, 2 l n
+    HksArgs a;
+    int lazy;
+    HksHoist(hexl_hks* h, size_t batch, u32 l)
+        : h0(h), p(h->plan), chunk(hks_chunk_of(h, batch)), per(2 * size_t(l) * h->plan->n), a(hks_args(h, l)), lazy(hks_level_tier(h->plan, l)) {}
+    // hks[0]'s key switch scratch and w of component 1 in a buffer of its own: ext has to survive step 4 for the next rotation
+    int reserve() {
+        if (int rc = hks_reserve(h0, chunk)) return rc;
+        if (int rc = h0->d_w1.reserve(chunk * p->L * p->n)) return rc;
+        a.coef = h0->d_coef; a.ext = h0->d_ext; a.acc = h0->d_acc; a.w1 = h0->d_w1;
+        a.tstride = 2 * a.l;
+        return 0;
+    }
+    // steps 1-2 on component 1 of nb ciphertexts [nb][2][l][n], read in place, into ext
+    int up(const u64* d_ct, size_t nb) {
+        a.t = d_ct + per / 2;
+        a.nb = (u32)nb;
+        return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return hks_stage_up<N, E, Z>(h0, a); });
+    }
+    int mac(const hexl_hks* keys, u32 g, HksMacMode mode, const u64* d_pt) const {
+        return hks_stage_mac_galois(h0, a, HksRot{keys->d_keys, d_pt, g}, mode);
+    }
+    // step 4 on acc, ADDED into d_out
+    int down(u64* d_out) {
+        a.result = d_out;
+        return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return hks_stage_down<N, E, Z>(h0, a); });
+    }
+};
+
+// What the two hoisted entry points check alike, in the house order (everything here decides HEXL_E_BADARG): the objects share hks[0]'s
+// plan and alpha, the level, the Galois elements, sizes and grids. s: bytes of a batch of ciphertexts, of one plaintext [K][n], of the
+// rows of an identity plaintext that are read.
+struct HksHoistBytes { size_t ct, pt, id; };
+static bool hks_hoist_ok(hexl_hks* const* hks, const u64* galois_elts, size_t n_rot, size_t batch, u64 n_limbs, HksHoistBytes* s) {
+    const hexl_hks* h0 = hks[0];
+    if (!hks_call_ok(h0, batch, n_limbs, 2, &s->ct)) return false;
+    const hexl_ks_plan* p = h0->plan;
+    size_t scratch;                                               // with w of component 1: L more rows per instance
+    if (!hx_words_bytes(hks_chunk_of(h0, batch), 1, hks_words_per_instance(h0) + p->L, p->n, &scratch)) return false;
+    s->pt = size_t(p->K) * p->n * sizeof(u64);
+    s->id = size_t(n_limbs) * p->n * sizeof(u64);
+    for (size_t r = 0; r < n_rot; ++r)
+        if (hks[r]->plan != p || hks[r]->alpha != h0->alpha || !hks_galois_elt_ok(galois_elts[r], p->n)) return false;
+    return true;
+}
+
+extern "C" int hexl_hks_rotate_hoisted(hexl_hks* const* hks, const uint64_t* galois_elts, size_t n_rot, uint64_t* const* d_outs,
+                                       const uint64_t* d_ct, size_t batch, uint64_t n_limbs) {
+    if (!hks || !galois_elts || !d_outs || !d_ct) return HEXL_E_BADARG;
+    if (!n_rot) return 0;
+    for (size_t r = 0; r < n_rot; ++r)
+        if (!hks[r] || !d_outs[r]) return HEXL_E_BADARG;
+    HksHoistBytes s;
+    if (!hks_hoist_ok(hks, galois_elts, n_rot, batch, n_limbs, &s)) return HEXL_E_BADARG;
+    for (size_t r = 0; r < n_rot; ++r) {
+        if (hx_ranges_overlap(d_outs[r], s.ct, d_ct, s.ct)) return HEXL_E_BADARG;
+        for (size_t q = 0; q < r; ++q)
+            if (hx_ranges_overlap(d_outs[r], s.ct, d_outs[q], s.ct)) return HEXL_E_BADARG;
+    }
+    for (size_t r = 0; r < n_rot; ++r)
+        if (!hks[r]->have_keys) return HEXL_E_NOKEYS;
+    if (!batch) return 0;
+    hexl_ks_plan* p = hks[0]->plan;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    HksHoist run(hks[0], batch, (u32)n_limbs);
+    if (int rc = run.reserve()) return rc;
+    // per chunk: the mod-up of c1, then per rotation (sigma_g(c0), 0) into its output, its multiply-accumulate and step 4 added into it
+    return hx_for_chunks(batch, run.chunk, [&](size_t b0, size_t nb) {
+        const u64* ct = d_ct + b0 * run.per;
+        if (int rc = run.up(ct, nb)) return rc;
+        for (size_t r = 0; r < n_rot; ++r) {
+            const u32 g = (u32)galois_elts[r];
+            u64* out = d_outs[r] + b0 * run.per;
+            if (int rc = hx_launch_galois_c0(p->ctx, out, ct, nb, (u32)n_limbs, p->logn, g)) return rc;
+            if (int rc = run.mac(hks[r], g, HKS_MAC_STORE, nullptr)) return rc;
+            if (int rc = run.down(out)) return rc;
+        }
+        return 0;
+    });
+}
+
+extern "C" int hexl_hks_linear_transform(hexl_hks* const* hks, const uint64_t* galois_elts, const uint64_t* const* d_pts, size_t n_rot,
+                                         const uint64_t* d_pt_identity, uint64_t* d_out, const uint64_t* d_ct, size_t batch,
+                                         uint64_t n_limbs) {
+    if (!hks || !galois_elts || !d_pts || !d_out || !d_ct || !n_rot) return HEXL_E_BADARG;
+    if (n_rot > SIZE_MAX / sizeof(HxLtRot)) return HEXL_E_BADARG;
+    for (size_t r = 0; r < n_rot; ++r)
+        if (!hks[r] || !d_pts[r]) return HEXL_E_BADARG;
+    HksHoistBytes s;
+    if (!hks_hoist_ok(hks, galois_elts, n_rot, batch, n_limbs, &s)) return HEXL_E_BADARG;
+    if (hx_ranges_overlap(d_out, s.ct, d_ct, s.ct)) return HEXL_E_BADARG;
+    if (d_pt_identity && hx_ranges_overlap(d_out, s.ct, d_pt_identity, s.id)) return HEXL_E_BADARG;
+    for (size_t r = 0; r < n_rot; ++r)
+        if (hx_ranges_overlap(d_out, s.ct, d_pts[r], s.pt)) return HEXL_E_BADARG;
+    for (size_t r = 0; r < n_rot; ++r)
+        if (!hks[r]->have_keys) return HEXL_E_NOKEYS;
+    if (!batch) return 0;
+    hexl_ks_plan* p = hks[0]->plan;
+    hexl_ctx* c = p->ctx;
+    HX_CHECK(hipSetDevice(c->device));
+    HksHoist run(hks[0], batch, (u32)n_limbs);
+    if (int rc = run.reserve()) return rc;
+    // the per-call table of the key-free kernel, as hx_launch_linear_transform builds it (keyswitch_f64.hip): pageable source, so the copy
+    // has left it when hipMemcpyAsync returns, and the stream orders it behind the previous call's kernels that read the table
+    std::vector<HxLtRot> table(n_rot);
+    for (size_t r = 0; r < n_rot; ++r) table[r] = HxLtRot{d_pts[r], galois_elts[r]};
+    if (int rc = c->d_shared.reserve(n_rot * sizeof(HxLtRot))) return rc;
+    HX_CHECK(hipMemcpyAsync(c->d_shared, table.data(), n_rot * sizeof(HxLtRot), hipMemcpyHostToDevice, c->stream));
+    // per chunk: the mod-up of c1, the key-free terms into d_out, one multiply-accumulate per rotation into acc, step 4 ONCE added into d_out
+    return hx_for_chunks(batch, run.chunk, [&](size_t b0, size_t nb) {
+        const u64* ct = d_ct + b0 * run.per;
+        u64* out = d_out + b0 * run.per;
+        if (int rc = run.up(ct, nb)) return rc;
+        if (int rc = hx_launch_galois_c0_pt(p, out, ct, (const HxLtRot*)c->d_shared.get(), n_rot, d_pt_identity, nb, (u32)n_limbs, nullptr)) return rc;
+        for (size_t r = 0; r < n_rot; ++r)
+            if (int rc = run.mac(hks[r], (u32)galois_elts[r], r ? HKS_MAC_PT_ACC : HKS_MAC_PT_FIRST, d_pts[r])) return rc;
+        return run.down(out);
+    });
+}
+
+extern "C" size_t hexl_hks_hoisted_scratch_bytes(const hexl_hks* h, size_t batch) {
+    if (!h) return 0;
+    return hks_chunk_of(h, batch) * (hks_words_per_instance(h) + h->plan->L) * h->plan->n * sizeof(u64);
 }

@@ -583,6 +583,58 @@ int hexl_hks_keyswitch(hexl_hks* hks, uint64_t* d_result, const uint64_t* d_t_ta
 int hexl_hks_relinearize(hexl_hks* hks, uint64_t* d_out, const uint64_t* d_ct3, size_t batch, uint64_t n_limbs);
 int hexl_hks_rotate(hexl_hks* hks, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t n_limbs, uint64_t galois_elt);
 size_t hexl_hks_scratch_bytes(const hexl_hks* hks, size_t batch);
+/* Hoisted rotations and the linear transform on the hybrid key switch: many plaintext-weighted rotations of ONE
+ * ciphertext batch. R calls of hexl_hks_rotate repeat steps 1-2 of the definition above -- the l inverse transforms, the base
+ * conversion and the sum_d (l + n_p - |G_d|) forward transforms -- which depend on c1 alone and not on the key. Per instance at the
+ * full level of L = 12, alpha = 4, n_p = 4: 80 R transforms for R calls of hexl_hks_rotate, 48 + 32 R for hexl_hks_rotate_hoisted
+ * (steps 1-2 once), 80 whatever R is for hexl_hks_linear_transform (step 4 once as well).
+ *   hks[r]        the hybrid key from s(X^g_r) to s, galois_elts[r] = g_r; r < n_rot. All objects must be attached to the SAME plan with
+ *                 the same alpha (an object owns its key and borrows everything else, so several objects on one plan is the natural
+ *                 arrangement). The same object, or the same g, may appear more than once. hks[0]'s scratch is used; the other objects
+ *                 contribute their keys only.
+ *   n_limbs = l   the level, 1 <= l <= L. d_ct, d_out and d_outs[r] are DEVICE [batch][2][l][n]; d_outs is a HOST array of device pointers.
+ *   d_pts         HOST array of n_rot device pointers, each [K][n]: the plaintext modulo ALL K plan limbs, in NTT form, every word below
+ *                 its modulus -- exactly what hexl_rns_ntt_fwd or hexl_ckks_encode with n_limbs = K writes. Only the rows of T_l (i < l
+ *                 and L ... K - 1) are read, so one encoded plaintext serves every level, as one key does.
+ *   d_pt_identity NULL, or DEVICE [>= l][n] of which rows i < l are read: it weights the key-free term pt_id . (c0, c1).
+ * Per instance, every line modulo its limb's modulus and every stored word canonical (normative). Let ext_d[j], j in T_l,
+ * d < ceil(l / alpha), be steps 1-2 of the definition above applied to t = c1 (the rows inside their own digit, ext_d[j] = c1[j],
+ * included), and sigma_g the word permutation of hexl_apply_galois.
+ *   hexl_hks_rotate_hoisted, for every r:
+ *     acc_r[k][j] = sum_d sigma_{g_r}(ext_d[j]) . key_r[d][k][j]
+ *     d_outs[r] WRITTEN with step 4 applied to acc_r with result = (sigma_{g_r}(c0), 0)
+ *   hexl_hks_linear_transform:
+ *     acc[k][j] = sum_r pt_r[j] . (sum_d sigma_{g_r}(ext_d[j]) . key_r[d][k][j])   for j in T_l; step 4 applied ONCE to acc; d_out WRITTEN with
+ *     out[0][i] = sum_r pt_r[i] . sigma_{g_r}(c0[i]) + pt_id[i] . c0[i] + down(acc[0])[i]
+ *     out[1][i] =                                      pt_id[i] . c1[i] + down(acc[1])[i]
+ *     down(acc)[i] = (acc[i] - NTT_i((w_i + fix_i) mod q_i)) . (P^-1 mod q_i) as in step 4; the pt_id terms are absent when d_pt_identity is NULL.
+ * Every output word is the canonical residue of an exactly defined class: neither the order of accumulation nor where the c0 term is
+ * added can change a word. Word identities (tested):
+ *   - for g = 1 hexl_hks_rotate_hoisted is word for word hexl_hks_rotate;
+ *   - for g != 1 it is NOT word for word hexl_hks_rotate -- the situation of hexl_rotate_hoisted against hexl_rotate: sigma_g applied to
+ *     the extended digit negates coefficients, and the lifts of a negated coefficient differ by |G_d| D modulo q_j. Both are lifts of
+ *     magnitude below |G_d| D_d congruent to the digit, and both decrypt alike under the same noise bound as above;
+ *   - hexl_hks_linear_transform with n_rot = 1, no identity term and an all-ones plaintext is word for word hexl_hks_rotate_hoisted;
+ *   - with alpha = 1, K = L + 1 and n_limbs = L both calls equal hexl_rotate_hoisted / hexl_linear_transform word for word on per-limb
+ *     plans (h_modswitch[i] = P^-1 mod q_i) that got the same key buffers through hexl_ks_set_keys_device; the d_pts layouts coincide
+ *     ([K][n] is [L + 1][n]).
+ * Noise of the linear transform, for CBD21 key errors, a ternary secret and plaintexts given as small integer polynomials (the same
+ * polynomial reduced modulo every limb of T_l, special primes included), ||.||_1 the 1-norm of the centred coefficient vector:
+ *   (sum_r ||pt_r||_1) . 21 n sum_d |G_d| D_d / P + (n_p + 1/2)(n + 1)      -- the rounding term once; the identity term adds none.
+ * HEXL_E_BADARG, in this order: a null argument or array entry, d_pt_identity excepted (batch == 0 does not excuse it); objects that do
+ * not share hks[0]'s plan and alpha; n_limbs outside 1 ... L; a g that is even or >= 2n; an output that overlaps d_ct, another output,
+ * any plaintext or the identity plaintext; a size or a grid that overflows; n_rot == 0 in the linear transform. Then HEXL_E_NOKEYS if
+ * any object has no keys. Then 0 with nothing written for batch == 0, or for n_rot == 0 in hexl_hks_rotate_hoisted (which then checks
+ * the three array arguments and d_ct for NULL only).
+ * Both calls are asynchronous on the context's stream, on one lane; the host arrays may be reused on return (per-rotation pointers
+ * travel in kernel arguments and in the context's grow-only table space). Precondition: every input word is below its modulus. This
+ * version does NOT raise the input-range flag (hexl_ks_range_check) for them either.
+ * Device memory: hks[0]'s scratch as above plus one grow-only buffer, min(batch, chunk) x L x n doubles -- in a plain key switch the
+ * mod-down's w of component 1 overwrites the extended digits, which here must survive for the next rotation.
+ * hexl_hks_hoisted_scratch_bytes(hks, batch) is hexl_hks_scratch_bytes plus that buffer; hexl_hks_scratch_bytes itself is unchanged. */
+int hexl_hks_rotate_hoisted(hexl_hks* const* hks, const uint64_t* galois_elts, size_t n_rot, uint64_t* const* d_outs, const uint64_t* d_ct, size_t batch, uint64_t n_limbs);
+int hexl_hks_linear_transform(hexl_hks* const* hks, const uint64_t* galois_elts, const uint64_t* const* d_pts, size_t n_rot, const uint64_t* d_pt_identity, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t n_limbs);
+size_t hexl_hks_hoisted_scratch_bytes(const hexl_hks* hks, size_t batch);
 /* Arithmetic tier per limb (introspection for logs and tests): tiers[i], i < key_modulus_size, = the forward transforms' range-
  * reduction period modulo q_i on the FP64 path -- 12 / 6 / 3 for q_i <= 2^49 / 2^50 / 2^51 (1 + 2^-7), 0 = every value reduced after
  * every operation (q_i up to 2^52); -1 for every limb of a plan on the integer kernels (a modulus >= 2^52). Every transform runs modulo
