@@ -88,6 +88,9 @@ C_ABI = {
     "hexl_hks_rotate_hoisted": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz, ctypes.POINTER(_vp), _vp, _sz, _u64],
     "hexl_hks_linear_transform": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_vp), _sz, _vp, _vp, _vp, _sz, _u64],
     "hexl_hks_hoisted_scratch_bytes": [_vp, _sz],
+    "hexl_hks_linear_transform_bsgs": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz, ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz,
+                                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _sz, _u64],
+    "hexl_hks_bsgs_scratch_bytes": [_vp, _sz, _sz],
     "hexl_ntt_fwd_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64],
     "hexl_ntt_inv_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64, _u64, _u64],
     "hexl_dyadic_multiply_host": [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _sz, _u64,
@@ -129,7 +132,7 @@ def lib() -> ctypes.CDLL:
             fn = getattr(_lib, name)
             fn.argtypes = args
             fn.restype = _sz if name in ("hexl_ks_scratch_bytes", "hexl_lt_bsgs_scratch_bytes", "hexl_hks_scratch_bytes",
-                                      "hexl_hks_hoisted_scratch_bytes") else _i
+                                      "hexl_hks_hoisted_scratch_bytes", "hexl_hks_bsgs_scratch_bytes") else _i
     return _lib
 
 
@@ -520,6 +523,10 @@ class HybridKeySwitch:
         """scratch_bytes plus the buffer hks_rotate_hoisted / hks_linear_transform keep on their first object"""
         return lib().hexl_hks_hoisted_scratch_bytes(self.h, batch)
 
+    def bsgs_scratch_bytes(self, n_baby: int, batch: int) -> int:
+        """device bytes an hks_linear_transform_bsgs call with this object first holds on it: hoisted scratch, baby store and t_j"""
+        return lib().hexl_hks_bsgs_scratch_bytes(self.h, n_baby, batch)
+
     def close(self):
         if getattr(self, "h", None):
             lib().hexl_hks_destroy(self.h)
@@ -572,6 +579,24 @@ def hks_linear_transform(hks_list, galois_elts, pts, pt_identity, out, ct, batch
            "hexl_hks_linear_transform")
 
 
+def hks_linear_transform_bsgs(baby_hks, baby_elts, giant_hks, giant_elts, pts, pt_identity, out, ct, batch: int, n_limbs: int):
+    """out[batch][2][n_limbs][n] = sum_j Rotate_G_j( sum_i pts[j][i] . Rotate_g_i(ct) + pt_identity[j] . ct ) on the hybrid keys of
+    baby_hks[i] (g_i = baby_elts[i]) and giant_hks[j] (G_j = giant_elts[j]) (hexl_hks_linear_transform_bsgs): n_baby + n_giant keys and
+    key passes instead of n_baby * n_giant. pts is a list of n_giant rows of n_baby entries, each None (an absent diagonal) or [K][n] as
+    for hks_linear_transform, already rotated by G_j^-1; pt_identity is None or a list of n_giant entries, each None or [>= n_limbs][n].
+    A baby object whose column is empty and a giant object with G_j = 1 may be None. Word for word hks_linear_transform per row ->
+    hks_rotate_hoisted -> sum; the objects share one plan and one alpha, the scratch is the first object's."""
+    n_baby, n_giant = len(baby_hks), len(giant_hks)
+    if len(baby_elts) != n_baby or len(giant_elts) != n_giant or len(pts) != n_giant or any(len(row) != n_baby for row in pts):
+        raise ValueError("hks_linear_transform_bsgs: one element per object and n_giant rows of n_baby plaintexts")
+    if pt_identity is not None and len(pt_identity) != n_giant:
+        raise ValueError("hks_linear_transform_bsgs: one identity plaintext (or None) per giant step")
+    flat = [p for row in pts for p in row]
+    _check(lib().hexl_hks_linear_transform_bsgs(_handles(baby_hks), _u64_array(baby_elts), n_baby, _handles(giant_hks), _u64_array(giant_elts),
+                                                n_giant, _opt_ptrs(flat), None if pt_identity is None else _opt_ptrs(pt_identity), _ptr(out),
+                                                _ptr(ct), batch, n_limbs), "hexl_hks_linear_transform_bsgs")
+
+
 def _opt_ptrs(items):
     """ctypes array of pointers with None entries as NULL"""
     return (_vp * len(items))(*[None if a is None else _ptr(a) for a in items])
@@ -602,6 +627,6 @@ def lt_bsgs_scratch_bytes(plan, n_baby: int, batch: int) -> int:
 
 from .host_api import HexlFpga  # noqa: E402  (mirror of host/inc/hexl-fpga.h)
 
-__all__ = ["Context", "KeySwitchPlan", "HybridKeySwitch", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform", "hks_rotate_hoisted", "hks_linear_transform",
+__all__ = ["Context", "KeySwitchPlan", "HybridKeySwitch", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform", "hks_rotate_hoisted", "hks_linear_transform", "hks_linear_transform_bsgs",
            "linear_transform_bsgs", "lt_bsgs_scratch_bytes", "C_ABI", "SAMPLE_UNIFORM", "SAMPLE_TERNARY", "SAMPLE_CBD21", "KEY_FROM_POLY", "KEY_FROM_SQUARE", "KEY_FROM_GALOIS", "seed_words",
            "LIB_PATH", "ROOT"]

@@ -288,10 +288,11 @@ __global__ __launch_bounds__(GPT_THREADS) void k_galois_add(GaloisAddArgs a) {
     *reinterpret_cast<u2*>(a.out + row + j) = o;
 }
 
-int hx_launch_galois_add(hexl_ks_plan* p, u64* d_out, const u64* d_t, size_t nb, u32 g, u32 n_comp) {
+// n_limbs: the limbs of d_out and d_t -- the plan's L, or the level of the hybrid caller (keyswitch_hybrid.hip), as hx_launch_galois_c0_pt
+int hx_launch_galois_add(hexl_ks_plan* p, u64* d_out, const u64* d_t, size_t nb, u32 g, u32 n_comp, u32 n_limbs) {
     if (!nb) return 0;
-    const GaloisAddArgs a{p->d_mods_f64, d_t, d_out, (u32)nb, p->L, p->logn, g};
-    hipLaunchKernelGGL(k_galois_add, dim3((u32)hx_ww_grid(p, nb * n_comp, p->L, GPT_LOG_CHUNK)), dim3(GPT_THREADS), 0, p->ctx->stream, a);
+    const GaloisAddArgs a{p->d_mods_f64, d_t, d_out, (u32)nb, n_limbs, p->logn, g};
+    hipLaunchKernelGGL(k_galois_add, dim3((u32)hx_ww_grid(p, nb * n_comp, n_limbs, GPT_LOG_CHUNK)), dim3(GPT_THREADS), 0, p->ctx->stream, a);
     return (int)hipGetLastError();
 }
 

@@ -302,14 +302,15 @@ int hx_launch_galois_c0_pt(hexl_ks_plan* p, u64* d_out, const u64* d_ct, const H
 // then per giant step a key-free weighted sum of the stored products, one mod-down into the plan's t buffer and one hoisted rotation
 // accumulated into d_out. `p0` (the first non-NULL plan, baby plans first) lends scratch, buffers, tier and range flag. Arguments checked
 // by the entry point (ckks_ops.hip). hx_lt_bsgs_chunk: instances per chunk -- the keyswitch's, cut so that the baby store stays within
-// HX_LT_BSGS_STORE_BYTES unless HEXL_KS_CHUNK forces it. hx_launch_galois_add (ckks_ops.hip): d_out[nb][2][L][n] += sigma_g of the first
-// n_comp components of d_t, word by word modulo q_i, on the context's stream.
+// HX_LT_BSGS_STORE_BYTES unless HEXL_KS_CHUNK forces it. hx_launch_galois_add (ckks_ops.hip): d_out[nb][2][n_limbs][n] += sigma_g of the
+// first n_comp components of d_t, word by word modulo q_i, on the context's stream; n_limbs: p->L, or the level of
+// hexl_hks_linear_transform_bsgs (keyswitch_hybrid.hip).
 constexpr size_t HX_LT_BSGS_STORE_BYTES = size_t(2) << 30;
 size_t hx_lt_bsgs_chunk(const hexl_ks_plan* p, size_t n_baby, size_t batch);
 int hx_launch_linear_transform_bsgs(hexl_ks_plan* p0, hexl_ks_plan* const* baby_plans, const u64* baby_elts, size_t n_baby,
                                     hexl_ks_plan* const* giant_plans, const u64* giant_elts, size_t n_giant, const u64* const* d_pts,
                                     const u64* const* d_pt_identity, u64* d_out, const u64* d_ct, size_t batch);
-int hx_launch_galois_add(hexl_ks_plan* p, u64* d_out, const u64* d_t, size_t nb, u32 g, u32 n_comp);
+int hx_launch_galois_add(hexl_ks_plan* p, u64* d_out, const u64* d_t, size_t nb, u32 g, u32 n_comp, u32 n_limbs);
 // plan-driven RNS transforms and the plaintext multiply (rns_ops.hip); arguments checked by their entry points (hexl_rns_ntt_fwd,
 // hexl_rns_ntt_inv, hexl_multiply_plain)
 int hx_launch_rns_ntt(hexl_ks_plan*, u64* d_out, const u64* d_in, size_t count, u32 n_limbs, bool inverse);

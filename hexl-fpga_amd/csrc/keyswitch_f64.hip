@@ -923,11 +923,11 @@ int hx_launch_linear_transform_bsgs(hexl_ks_plan* p0, hexl_ks_plan* const* baby_
             }
             if (g == 1) {
                 if (j)
-                    if (int rc = hx_launch_galois_add(p0, out, t, nb, 1, 2)) return rc;
+                    if (int rc = hx_launch_galois_add(p0, out, t, nb, 1, 2, p0->L)) return rc;
                 continue;
             }
             if (int rc = run.up(t + half, nb)) return rc;           // the babies are stored: u is free
-            if (int rc = j ? hx_launch_galois_add(p0, out, t, nb, g, 1) : hx_launch_galois_c0(c, out, t, nb, p0->L, p0->logn, g)) return rc;
+            if (int rc = j ? hx_launch_galois_add(p0, out, t, nb, g, 1, p0->L) : hx_launch_galois_c0(c, out, t, nb, p0->L, p0->logn, g)) return rc;
             if (int rc = run.mac(giant_plans[j], g, KSF_MAC_STORE, nullptr, nullptr, nb)) return rc;
             if (int rc = run.down(giant_plans[j], out, nb)) return rc;
         }

@@ -47,9 +47,12 @@ struct hexl_hks {
     HxDevBuf<double> d_acc;           // [chunk][2][K][n]     acc; rows of S: b_s after step 4a
     HxDevBuf<u64> d_slice;            // rotate / relinearize: the key switch's input of one slice, [slice][L][n]
     HxDevBuf<double> d_w1;            // the hoisted callers: w of component 1, [chunk][L][n] (grow-only, allocated at their first call)
+    // hexl_hks_linear_transform_bsgs, both grow-only and allocated at its first call
+    HxDevBuf<double> d_bsgs_b;        // baby store: [n_baby][chunk][2][K][n], slice i = the stored sums of baby step i, [nb][2][T][n] of it used
+    HxDevBuf<u64> d_bsgs_t;           // one giant step's inner sum t_j: [chunk][2][L][n] canonical words ([nb][2][l][n] of it used)
     explicit hexl_hks(hexl_ks_plan* p)
         : plan(p), d_keys(p->ctx), d_src(p->ctx), d_wt(p->ctx), d_down(p->ctx), d_coef(p->ctx), d_ext(p->ctx), d_acc(p->ctx), d_slice(p->ctx),
-          d_w1(p->ctx) {}
+          d_w1(p->ctx), d_bsgs_b(p->ctx), d_bsgs_t(p->ctx) {}
 };
 
 struct HksArgs {
@@ -361,6 +364,57 @@ __global__ __launch_bounds__(HKS_THREADS) void k_hks_mac_galois(HksArgs a, HksRo
     }
 }
 
+// step 3 of one giant step of hexl_hks_linear_transform_bsgs, k_lt_bsgs_sum (keyswitch_f64.hip) on this layout:
+//     acc[b][k][jT] = sum_r pt_r[limb of jT] . B_r[b][k][jT]
+// B_r is what k_hks_mac_galois<., HKS_MAC_STORE> stored for the baby step of term r: the inner sum of the plaintext modes, computed once
+// per chunk instead of once per giant step. No keys, no gather, no position map: a stored vector lies at its logical index like every
+// hybrid intermediate, so a lane owns two adjacent indices of one row of T_l as in k_hks_mac and every access is 16 bytes. It walks the
+// row's terms of the per-call table (wave-uniform: scalar loads), keeps both accumulators in registers across them and writes acc ONCE --
+// where k_hks_mac_galois<., HKS_MAC_PT_ACC> reads and writes acc per term. The plaintext is indexed by the PHYSICAL limb (pt is [K][n]),
+// the stored vectors and acc by the row jT of T_l. The scalar chain is that of the plaintext modes unchanged and in the same order --
+// lt_pt, lt_mac for the first term, lt_mac_acc after it -- on the same inner operand (an hks_mac_term output, stored exactly), so acc
+// holds the very doubles hexl_hks_linear_transform's multiply-accumulates leave for that row.
+struct HksBsgsTerm { const u64* pt; const double* B; };           // pt: [K][n]; B: the baby step's slice [nb][2][T][n]
+
+__global__ __launch_bounds__(HKS_THREADS) void k_hks_bsgs_sum(HksArgs a, const HksBsgsTerm* terms, u32 n_terms) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
+    const u32 n = 1u << a.logn, pairs = n >> 1;
+    const u32 gid = blockIdx.x * blockDim.x + threadIdx.x;        // (row of T_l, pair)
+    const u32 jT = gid / pairs;
+    if (jT >= a.T) return;
+    const u32 c = (gid - jT * pairs) * 2;
+    const u32 j = hks_limb(a, jT);
+    const Mod m = a.mods[j].m;
+    const size_t po = size_t(j) * n + c;
+    for (u32 b = blockIdx.y; b < a.nb; b += gridDim.y) {
+        const size_t o0 = ((size_t(b) * 2 + 0) * a.T + jT) * n + c, o1 = ((size_t(b) * 2 + 1) * a.T + jT) * n + c;
+        const HksBsgsTerm first = terms[0];                       // uniform: scalar loads
+        const u2 t = *reinterpret_cast<const u2*>(first.pt + po);
+        const d2 f0 = *reinterpret_cast<const d2*>(first.B + o0), f1 = *reinterpret_cast<const d2*>(first.B + o1);
+        d2 acc0, acc1;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const double w = hxf::lt_pt(hxf::to_f64(t[e]), m);
+            acc0[e] = hxf::lt_mac(f0[e], w, m);
+            acc1[e] = hxf::lt_mac(f1[e], w, m);
+        }
+        for (u32 r = 1; r < n_terms; ++r) {
+            const HksBsgsTerm term = terms[r];
+            const u2 tr = *reinterpret_cast<const u2*>(term.pt + po);
+            const d2 v0 = *reinterpret_cast<const d2*>(term.B + o0), v1 = *reinterpret_cast<const d2*>(term.B + o1);
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const double w = hxf::lt_pt(hxf::to_f64(tr[e]), m);
+                acc0[e] = hxf::lt_mac_acc(v0[e], w, acc0[e], m);
+                acc1[e] = hxf::lt_mac_acc(v1[e], w, acc1[e], m);
+            }
+        }
+        *reinterpret_cast<d2*>(a.acc + o0) = acc0;
+        *reinterpret_cast<d2*>(a.acc + o1) = acc1;
+    }
+}
+
 // the key install: the caller's [dnum][2][K][n] canonical words as centred doubles at the same place, one workgroup per (row, piece)
 struct HksInstallArgs { const KsModF64* mods; const u64* in; double* out; u32 K, logn; };
 __global__ __launch_bounds__(HKS_THREADS) void k_hks_install(HksInstallArgs a) {
@@ -460,6 +514,11 @@ static int hks_stage_mac_galois(hexl_hks* h, const HksArgs& a, const HksRot& rot
         else if (mode == HKS_MAC_PT_FIRST) hipLaunchKernelGGL((k_hks_mac_galois<D, HKS_MAC_PT_FIRST>), grid, ww, 0, st, a, rot);
         else                               hipLaunchKernelGGL((k_hks_mac_galois<D, HKS_MAC_PT_ACC>), grid, ww, 0, st, a, rot);
     });
+    return (int)hipGetLastError();
+}
+
+static int hks_stage_bsgs_sum(hexl_hks* h, const HksArgs& a, const HksBsgsTerm* d_terms, u32 n_terms) {
+    hipLaunchKernelGGL(k_hks_bsgs_sum, hks_mac_grid(a), dim3(HKS_THREADS), 0, h->plan->ctx->stream, a, d_terms, n_terms);
     return (int)hipGetLastError();
 }
 
@@ -723,9 +782,14 @@ struct HksHoist {
         a.nb = (u32)nb;
         return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return hks_stage_up<N, E, Z>(h0, a); });
     }
-    int mac(const hexl_hks* keys, u32 g, HksMacMode mode, const u64* d_pt) const {
-        return hks_stage_mac_galois(h0, a, HksRot{keys->d_keys, d_pt, g}, mode);
+    // `store` (HKS_MAC_STORE): the sums go there, [nb][2][T][n], instead of acc
+    int mac(const hexl_hks* keys, u32 g, HksMacMode mode, const u64* d_pt, double* store = nullptr) const {
+        HksArgs m = a;
+        if (store) m.acc = store;
+        return hks_stage_mac_galois(h0, m, HksRot{keys->d_keys, d_pt, g}, mode);
     }
+    // step 3 of a giant step: the weighted sum of stored baby products into acc
+    int sum(const HksBsgsTerm* d_terms, size_t n_terms) const { return hks_stage_bsgs_sum(h0, a, d_terms, (u32)n_terms); }
     // step 4 on acc, ADDED into d_out
     int down(u64* d_out) {
         a.result = d_out;
@@ -827,4 +891,157 @@ extern "C" int hexl_hks_linear_transform(hexl_hks* const* hks, const uint64_t* g
 extern "C" size_t hexl_hks_hoisted_scratch_bytes(const hexl_hks* h, size_t batch) {
     if (!h) return 0;
     return hks_chunk_of(h, batch) * (hks_words_per_instance(h) + h->plan->L) * h->plan->n * sizeof(u64);
+}
+
+// ---- baby-step/giant-step linear transform on the hybrid gadget (hexl_hks_linear_transform_bsgs):
+//      out = sum_j Rot_{G_j}( sum_i pt_{j,i} . Rot_{g_i}(ct) + pt_id_j . ct ),  hx_launch_linear_transform_bsgs (keyswitch_f64.hip) stage by
+// stage on the hybrid stages. Per chunk, in h0's scratch (h0: the first non-NULL object, baby objects first):
+//   the mod-up of c1 once; one k_hks_mac_galois<., STORE> per baby step that some row uses, its sums pointed at that step's slice of the
+//   baby store (coef and ext are free after the last of them);
+//   per giant step j: the key-free part of row j into t_j (hx_launch_galois_c0_pt), the weighted sum of the stored products into acc
+//   (k_hks_bsgs_sum) and the mod-down ONCE, added into t_j -- hexl_hks_linear_transform's words for row j; then t_j rotated by G_j as
+//   hexl_hks_rotate_hoisted rotates it (mod-up of t_j's component 1 into the same coef / ext, giant_hks[j]'s keys) with the key-free part
+//   sigma_{G_j}(t_j[0]) WRITTEN to d_out by the first giant step and ADDED by the later ones, and the mod-down accumulating on top.
+//   G_j = 1: t_j itself is written (the first giant step computes it in place in d_out) or added.
+// Where w of component 1 lives (the scratch pitfall of 4.6.11): in BOTH mod-downs -- the row's and the giant rotation's -- in d_w1, the
+// hoisted callers' buffer, never on ext; w of component 0 in coef, which is dead once the mod-up's conversion has run and is rewritten
+// by the next mod-up only behind the mod-down that read it (one stream). So no consumer of ext can meet a w.
+// Every word that reaches d_out is canonical and every addition is modulo q_i, so d_out holds the sum of the per-row results of the two
+// parent entry points, word for word. ----
+static size_t hks_bsgs_slice_bytes(const hexl_hks* h) { return 2 * size_t(h->plan->K) * h->plan->n * sizeof(double); }   // one baby step, one instance
+static size_t hks_bsgs_chunk(const hexl_hks* h, size_t n_baby, size_t batch) {
+    const size_t chunk = hks_chunk_of(h, batch);
+    if (hx_ks_chunk_forced() || !n_baby || !chunk) return chunk;  // a forced chunk stays
+    const size_t fit = HX_LT_BSGS_STORE_BYTES / hks_bsgs_slice_bytes(h) / n_baby;
+    return fit >= chunk ? chunk : fit ? fit : 1;
+}
+
+extern "C" size_t hexl_hks_bsgs_scratch_bytes(const hexl_hks* h, size_t n_baby, size_t batch) {
+    if (!h) return 0;
+    const hexl_ks_plan* p = h->plan;
+    const size_t chunk = hks_bsgs_chunk(h, n_baby, batch);
+    // per instance: the hoisted callers' scratch and t_j
+    const size_t fixed = (hks_words_per_instance(h) + p->L) * p->n * sizeof(u64) + 2 * size_t(p->L) * p->n * sizeof(u64);
+    if (chunk && (fixed > SIZE_MAX / chunk || n_baby > (SIZE_MAX / chunk - fixed) / hks_bsgs_slice_bytes(h))) return SIZE_MAX;
+    return chunk * (n_baby * hks_bsgs_slice_bytes(h) + fixed);
+}
+
+extern "C" int hexl_hks_linear_transform_bsgs(hexl_hks* const* baby_hks, const uint64_t* baby_elts, size_t n_baby,
+                                              hexl_hks* const* giant_hks, const uint64_t* giant_elts, size_t n_giant,
+                                              const uint64_t* const* d_pts, const uint64_t* const* d_pt_identity, uint64_t* d_out,
+                                              const uint64_t* d_ct, size_t batch, uint64_t n_limbs) {
+    if (!baby_hks || !baby_elts || !giant_hks || !giant_elts || !d_pts || !d_out || !d_ct || !n_giant) return HEXL_E_BADARG;
+    if (n_giant > SIZE_MAX / sizeof(HxLtRot) / 2 || (n_baby && n_giant > SIZE_MAX / sizeof(HxLtRot) / 2 / n_baby)) return HEXL_E_BADARG;
+    // the object that lends its scratch and buffers: baby_hks[0] whenever there is one
+    hexl_hks* h0 = nullptr;
+    for (size_t i = 0; i < n_baby && !h0; ++i) h0 = baby_hks[i];
+    for (size_t j = 0; j < n_giant && !h0; ++j) h0 = giant_hks[j];
+    if (!h0) return HEXL_E_BADARG;
+    // in the order of the header: the rows, the objects against the first one, the level, the elements, the overlaps, the sizes
+    auto matches = [&](const hexl_hks* h) { return !h || (h->plan == h0->plan && h->alpha == h0->alpha); };
+    for (size_t j = 0; j < n_giant; ++j) {
+        bool any = d_pt_identity && d_pt_identity[j];
+        for (size_t i = 0; i < n_baby && !any; ++i) any = d_pts[j * n_baby + i] != nullptr;
+        if (!any) return HEXL_E_BADARG;                             // a giant row with no term at all
+    }
+    for (size_t i = 0; i < n_baby; ++i)
+        if (!matches(baby_hks[i])) return HEXL_E_BADARG;
+    for (size_t j = 0; j < n_giant; ++j)
+        if (!matches(giant_hks[j])) return HEXL_E_BADARG;
+    for (size_t j = 0; j < n_giant; ++j)
+        for (size_t i = 0; i < n_baby; ++i)
+            if (d_pts[j * n_baby + i] && !baby_hks[i]) return HEXL_E_BADARG;
+    for (size_t j = 0; j < n_giant; ++j)
+        if (!giant_hks[j] && giant_elts[j] != 1) return HEXL_E_BADARG;
+    HksHoistBytes s;
+    // plan, level, sizes and grids at the key switch's chunk, which this call's never exceeds
+    if (!hks_call_ok(h0, batch, n_limbs, 2, &s.ct)) return HEXL_E_BADARG;
+    hexl_ks_plan* p = h0->plan;
+    s.pt = size_t(p->K) * p->n * sizeof(u64);
+    s.id = size_t(n_limbs) * p->n * sizeof(u64);
+    for (size_t i = 0; i < n_baby; ++i)
+        if (!hks_galois_elt_ok(baby_elts[i], p->n)) return HEXL_E_BADARG;
+    for (size_t j = 0; j < n_giant; ++j)
+        if (!hks_galois_elt_ok(giant_elts[j], p->n)) return HEXL_E_BADARG;
+    if (hx_ranges_overlap(d_out, s.ct, d_ct, s.ct)) return HEXL_E_BADARG;
+    for (size_t j = 0; j < n_giant; ++j) {
+        const u64* pt_id = d_pt_identity ? d_pt_identity[j] : nullptr;
+        if (pt_id && hx_ranges_overlap(d_out, s.ct, pt_id, s.id)) return HEXL_E_BADARG;
+        for (size_t i = 0; i < n_baby; ++i)
+            if (const u64* pt = d_pts[j * n_baby + i])
+                if (hx_ranges_overlap(d_out, s.ct, pt, s.pt)) return HEXL_E_BADARG;
+    }
+    if (n_baby > HX_LT_BSGS_STORE_BYTES / hks_bsgs_slice_bytes(h0)) return HEXL_E_BADARG;   // not one instance would fit the baby store
+    if (hexl_hks_bsgs_scratch_bytes(h0, n_baby, batch) == SIZE_MAX) return HEXL_E_BADARG;
+    for (size_t j = 0; j < n_giant; ++j) {
+        if (giant_elts[j] != 1 && !giant_hks[j]->have_keys) return HEXL_E_NOKEYS;
+        for (size_t i = 0; i < n_baby; ++i)
+            if (d_pts[j * n_baby + i] && !baby_hks[i]->have_keys) return HEXL_E_NOKEYS;
+    }
+    if (!batch) return 0;
+    hexl_ctx* c = p->ctx;
+    HX_CHECK(hipSetDevice(c->device));
+    const u32 l = (u32)n_limbs;
+    HksHoist run(h0, batch, l);
+    run.chunk = hks_bsgs_chunk(h0, n_baby, batch);
+    if (int rc = run.reserve()) return rc;
+    const size_t chunk = run.chunk, n = p->n, slice = chunk * 2 * p->K * n;     // doubles of one baby step's slice
+    if (n_baby)
+        if (int rc = h0->d_bsgs_b.reserve(n_baby * slice)) return rc;
+    if (int rc = h0->d_bsgs_t.reserve(chunk * 2 * p->L * n)) return rc;
+    // the per-call tables, row after row: what the c0 kernel walks (plaintext, Galois element) and what the sum kernel walks (plaintext,
+    // baby slice). Pageable sources, stream-ordered behind the previous call's readers, as hexl_hks_linear_transform's table
+    std::vector<HxLtRot> rots;
+    std::vector<HksBsgsTerm> terms;
+    std::vector<size_t> off(n_giant + 1);
+    std::vector<char> used(n_baby, 0);
+    for (size_t j = 0; j < n_giant; ++j) {
+        off[j] = rots.size();
+        for (size_t i = 0; i < n_baby; ++i)
+            if (const u64* pt = d_pts[j * n_baby + i]) {
+                rots.push_back(HxLtRot{pt, baby_elts[i]});
+                terms.push_back(HksBsgsTerm{pt, h0->d_bsgs_b + i * slice});
+                used[i] = 1;
+            }
+    }
+    const size_t total = off[n_giant] = rots.size();
+    static_assert(sizeof(HxLtRot) == 16 && sizeof(HksBsgsTerm) == 16, "the two tables share one 16-byte-aligned reservation");
+    if (total) {
+        if (int rc = c->d_shared.reserve(total * (sizeof(HxLtRot) + sizeof(HksBsgsTerm)))) return rc;
+        HX_CHECK(hipMemcpyAsync(c->d_shared, rots.data(), total * sizeof(HxLtRot), hipMemcpyHostToDevice, c->stream));
+        HX_CHECK(hipMemcpyAsync((HxLtRot*)c->d_shared.get() + total, terms.data(), total * sizeof(HksBsgsTerm), hipMemcpyHostToDevice, c->stream));
+    }
+    const HxLtRot* d_rots = (const HxLtRot*)c->d_shared.get();
+    const HksBsgsTerm* d_terms = (const HksBsgsTerm*)(d_rots + total);
+    return hx_for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
+        const u64* ct = d_ct + b0 * run.per;
+        u64* out = d_out + b0 * run.per;
+        run.a.nb = (u32)nb;
+        if (total) {
+            if (int rc = run.up(ct, nb)) return rc;
+            for (size_t i = 0; i < n_baby; ++i)
+                if (used[i])
+                    if (int rc = run.mac(baby_hks[i], (u32)baby_elts[i], HKS_MAC_STORE, nullptr, h0->d_bsgs_b + i * slice)) return rc;
+        }
+        for (size_t j = 0; j < n_giant; ++j) {
+            const size_t cnt = off[j + 1] - off[j];
+            const u32 g = (u32)giant_elts[j];
+            u64* t = (j == 0 && g == 1) ? out : h0->d_bsgs_t.get();
+            if (int rc = hx_launch_galois_c0_pt(p, t, ct, d_rots + off[j], cnt, d_pt_identity ? d_pt_identity[j] : nullptr, nb, l, nullptr)) return rc;
+            if (cnt) {
+                if (int rc = run.sum(d_terms + off[j], cnt)) return rc;
+                if (int rc = run.down(t)) return rc;                // accumulated into what the c0 kernel wrote; w1 in d_w1
+            }
+            if (g == 1) {
+                if (j)
+                    if (int rc = hx_launch_galois_add(p, out, t, nb, 1, 2, l)) return rc;
+                continue;
+            }
+            if (int rc = run.up(t, nb)) return rc;                  // the babies are stored: coef and ext are free
+            if (int rc = j ? hx_launch_galois_add(p, out, t, nb, g, 1, l) : hx_launch_galois_c0(c, out, t, nb, l, p->logn, g)) return rc;
+            if (int rc = run.mac(giant_hks[j], g, HKS_MAC_STORE, nullptr)) return rc;
+            if (int rc = run.down(out)) return rc;                  // w1 in d_w1 again
+        }
+        return 0;
+    });
 }

@@ -635,6 +635,48 @@ size_t hexl_hks_scratch_bytes(const hexl_hks* hks, size_t batch);
 int hexl_hks_rotate_hoisted(hexl_hks* const* hks, const uint64_t* galois_elts, size_t n_rot, uint64_t* const* d_outs, const uint64_t* d_ct, size_t batch, uint64_t n_limbs);
 int hexl_hks_linear_transform(hexl_hks* const* hks, const uint64_t* galois_elts, const uint64_t* const* d_pts, size_t n_rot, const uint64_t* d_pt_identity, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t n_limbs);
 size_t hexl_hks_hoisted_scratch_bytes(const hexl_hks* hks, size_t batch);
+/* Baby-step/giant-step diagonals on the hybrid key switch, hexl_linear_transform_bsgs with the hybrid calls'
+ * conventions:
+ *   d_out = sum_j Rot_{G_j}( sum_i pt_{j,i} . Rot_{g_i}(ct) + pt_id_j . ct )   at level l = n_limbs
+ * with n_baby + #{G_j != 1} hybrid keys and key passes instead of the n_baby x n_giant of one flat hexl_hks_linear_transform.
+ *   baby_hks[i]   the hybrid key from s(X^g_i) to s, baby_elts[i] = g_i; i < n_baby. An entry may be NULL when no row has a plaintext in
+ *                 its column.
+ *   giant_hks[j]  the same for giant_elts[j] = G_j; j < n_giant. May be NULL when G_j = 1.
+ *                 Every non-NULL object must be attached to the SAME plan with the same alpha. Objects and elements may repeat, and one
+ *                 g may be a baby step and a giant step. The first non-NULL object (baby array first, then giant) owns the scratch, as
+ *                 hks[0] does above; the others contribute their keys only.
+ *   d_pts         HOST array of n_giant x n_baby DEVICE pointers, row-major (j, i). NULL = an absent diagonal; otherwise [K][n] exactly as
+ *                 for hexl_hks_linear_transform (all K plan limbs, NTT form, only the rows of T_l read: one encoded plaintext serves every
+ *                 level). Diagonal (j, i) is supplied already rotated by G_j^-1.
+ *   d_pt_identity NULL, or a HOST array of n_giant entries, each NULL or DEVICE [>= l][n].
+ *   d_ct, d_out   DEVICE [batch][2][l][n]; d_out is WRITTEN.
+ * Definition (normative): the composition of the two calls above. For every giant step j
+ *   t_j = hexl_hks_linear_transform(row j's non-NULL baby objects, elements and plaintexts in the order of i, d_pt_identity[j], ct, l)
+ *         (a row with only an identity term: t_j = pt_id_j . (c0, c1) mod q_i),
+ *   r_j = t_j if G_j = 1, else hexl_hks_rotate_hoisted(&giant_hks[j], &G_j, 1, ., t_j, l),
+ *   d_out = sum_j r_j mod q_i, every word canonical.
+ * The call is word for word that composition: both building blocks end in canonical residues of exactly defined classes, so storing the
+ * baby products instead of recomputing them per row, and the order of accumulation, cannot change a word. With alpha = 1, K = L + 1 and
+ * n_limbs = L it equals hexl_linear_transform_bsgs word for word on per-limb plans keyed from the same device buffers. It is NOT word for
+ * word what these routes give, which all decrypt alike: R calls of hexl_hks_rotate weighted and summed by the caller (the lifts of a
+ * permuted digit differ, as above), and the flat hexl_hks_linear_transform over the n_baby x n_giant composed rotations (one rounding by
+ * P instead of one per row and one per rotated giant step).
+ * Noise, under the assumptions of the bound above: sum_j B_lt(row j) + #{j : G_j != 1} . B, with B_lt the linear transform's bound for
+ * row j's plaintexts and B the key switch's; sigma_G is a signed permutation and preserves the infinity norm, identity-only rows add nothing.
+ * HEXL_E_BADARG: a null argument or array, d_pt_identity excepted (batch == 0 does not excuse it); n_giant == 0; no object at all; a giant
+ * row with neither a plaintext nor an identity term; objects that do not share the first one's plan and alpha; a NULL baby object whose
+ * column has a plaintext; a NULL giant object with G_j != 1; n_limbs outside 1 ... L; an element that is even or >= 2n, used or not;
+ * d_out overlapping d_ct, any plaintext or any identity plaintext; a size or a grid that overflows, including an n_baby for which not
+ * one instance fits the baby store. Then HEXL_E_NOKEYS if any object that is USED has no keys (an unused one may lack them). Then
+ * batch == 0 returns 0 with nothing written. n_baby == 0 is allowed when every row has its identity term.
+ * Asynchronous on the context's stream, on one lane; the host arrays may be reused on return. Precondition: every input word is below
+ * its modulus; like the rest of the hybrid family this call does NOT raise the input-range flag (hexl_ks_range_check).
+ * Device memory on the scratch owner, grow-only: the hoisted calls' scratch, the baby store (n_baby x chunk x 2 x K x n doubles) and
+ * t_j (chunk x 2 x L x n words); chunk is the key switch's, cut so that the baby store stays within 2 GiB (never below one instance)
+ * unless HEXL_KS_CHUNK forces it. hexl_hks_bsgs_scratch_bytes(hks, n_baby, batch) is that sum; hexl_hks_scratch_bytes and
+ * hexl_hks_hoisted_scratch_bytes are unchanged. */
+int hexl_hks_linear_transform_bsgs(hexl_hks* const* baby_hks, const uint64_t* baby_elts, size_t n_baby, hexl_hks* const* giant_hks, const uint64_t* giant_elts, size_t n_giant, const uint64_t* const* d_pts, const uint64_t* const* d_pt_identity, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t n_limbs);
+size_t hexl_hks_bsgs_scratch_bytes(const hexl_hks* hks, size_t n_baby, size_t batch);
 /* Arithmetic tier per limb (introspection for logs and tests): tiers[i], i < key_modulus_size, = the forward transforms' range-
  * reduction period modulo q_i on the FP64 path -- 12 / 6 / 3 for q_i <= 2^49 / 2^50 / 2^51 (1 + 2^-7), 0 = every value reduced after
  * every operation (q_i up to 2^52); -1 for every limb of a plan on the integer kernels (a modulus >= 2^52). Every transform runs modulo
