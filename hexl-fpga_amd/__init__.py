@@ -91,6 +91,10 @@ C_ABI = {
     "hexl_hks_linear_transform_bsgs": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz, ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz,
                                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _sz, _u64],
     "hexl_hks_bsgs_scratch_bytes": [_vp, _sz, _sz],
+    "hexl_hks_multiply_sum_relinearize": [_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _sz, _sz, _u64],
+    "hexl_hks_relinearize_rescale": [_vp, _vp, _vp, _sz, _u64],
+    "hexl_hks_multiply_sum_rescale": [_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _sz, _sz, _u64],
+    "hexl_hks_mul_scratch_bytes": [_vp, _sz],
     "hexl_ntt_fwd_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64],
     "hexl_ntt_inv_host": [_vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _u64, _u64, _u64, _u64],
     "hexl_dyadic_multiply_host": [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _sz, _u64,
@@ -132,7 +136,7 @@ def lib() -> ctypes.CDLL:
             fn = getattr(_lib, name)
             fn.argtypes = args
             fn.restype = _sz if name in ("hexl_ks_scratch_bytes", "hexl_lt_bsgs_scratch_bytes", "hexl_hks_scratch_bytes",
-                                      "hexl_hks_hoisted_scratch_bytes", "hexl_hks_bsgs_scratch_bytes") else _i
+                                      "hexl_hks_hoisted_scratch_bytes", "hexl_hks_bsgs_scratch_bytes", "hexl_hks_mul_scratch_bytes") else _i
     return _lib
 
 
@@ -526,6 +530,30 @@ class HybridKeySwitch:
     def bsgs_scratch_bytes(self, n_baby: int, batch: int) -> int:
         """device bytes an hks_linear_transform_bsgs call with this object first holds on it: hoisted scratch, baby store and t_j"""
         return lib().hexl_hks_bsgs_scratch_bytes(self.h, n_baby, batch)
+
+    def multiply_sum_relinearize(self, out, a_s, b_s, batch: int, n_limbs: int, in_limbs=None):
+        """out[batch][2][n_limbs][n] = relinearize(plan.ct_tensor_sum(a_s, b_s, n_limbs)) on the hybrid key, word for word, without the
+        three-component sum ever existing in memory; operands as KeySwitchPlan.ct_tensor_sum, in_limbs entries in n_limbs ... K"""
+        pa, pb, il = self.plan._tensor_operands("hks multiply_sum_relinearize", a_s, b_s, in_limbs)
+        _check(lib().hexl_hks_multiply_sum_relinearize(self.h, _ptr(out), pa, pb, None if il is None else il.ctypes.data, len(a_s), batch,
+                                                       n_limbs), "hexl_hks_multiply_sum_relinearize")
+
+    def relinearize_rescale(self, out, ct3, batch: int, n_limbs: int):
+        """out[batch][2][n_limbs - 1][n] = (P (d0, d1) + KSacc(d2)) / (P q_(n_limbs-1)) rounded, of ct3[batch][3][n_limbs][n]: the
+        relinearisation and the rescale in ONE mod-down (n_limbs >= 2). Decrypts like relinearize -> plan.rescale, but is not
+        word-identical to it (one rounding instead of two)."""
+        _check(lib().hexl_hks_relinearize_rescale(self.h, _ptr(out), _ptr(ct3), batch, n_limbs), "hexl_hks_relinearize_rescale")
+
+    def multiply_sum_rescale(self, out, a_s, b_s, batch: int, n_limbs: int, in_limbs=None):
+        """out[batch][2][n_limbs - 1][n] = relinearize_rescale(plan.ct_tensor_sum(a_s, b_s, n_limbs)), word for word, with neither the
+        three-component sum nor the un-rescaled ciphertext in memory (n_limbs >= 2); operands as KeySwitchPlan.ct_tensor_sum"""
+        pa, pb, il = self.plan._tensor_operands("hks multiply_sum_rescale", a_s, b_s, in_limbs)
+        _check(lib().hexl_hks_multiply_sum_rescale(self.h, _ptr(out), pa, pb, None if il is None else il.ctypes.data, len(a_s), batch,
+                                                   n_limbs), "hexl_hks_multiply_sum_rescale")
+
+    def mul_scratch_bytes(self, batch: int) -> int:
+        """scratch_bytes plus the slice and (d0, d1) buffers the multiply calls keep on the object"""
+        return lib().hexl_hks_mul_scratch_bytes(self.h, batch)
 
     def close(self):
         if getattr(self, "h", None):

@@ -14,24 +14,9 @@ using hxf::Mod;
 
 constexpr u32 TS_THREADS = 256, TS_VECS = 2;
 constexpr u32 TS_LOG_CHUNK = 10;    // 1024 words of one polynomial per workgroup (the smallest ring): TS_VECS 16-byte vectors per lane
-constexpr u32 TS_MAX_TERMS = 8, TS_MAX_LIMBS = 16;                // hexl_ks_plan::tier has 16 limbs
 static_assert(TS_THREADS * TS_VECS * 2 == 1u << TS_LOG_CHUNK, "a workgroup covers its piece exactly");
 static_assert(TS_THREADS == HX_WW_THREADS && TS_LOG_CHUNK == HX_WW_LOG_CHUNK, "hx_ww_grid counts these workgroups");
-
-// Pointers and limb counts travel BY VALUE in the kernel arguments, as k_ct_lincomb's (rns_ops.hip): nothing is uploaded, so the host
-// arrays are the caller's again when the call returns. The output goes through TWO descriptors -- components 0-1 of instance b at
-// out01 + b stride01 (laid out [2][L][n]), component 2 at out2 + b stride2 ([L][n]) -- so that one kernel writes hexl_ct_tensor_sum's
-// [batch][3][L][n] buffer and, for hexl_multiply_sum_relinearize, a two-component output and the keyswitch's t_target slice.
-struct TsArgs {
-    const KsModF64* mods;       // [K]
-    const u64* a[TS_MAX_TERMS]; // term t: [batch][2][la[t]][n], read through its first L limbs
-    const u64* b[TS_MAX_TERMS]; //         [batch][2][lb[t]][n]; may be a[t] (a square)
-    u32 la[TS_MAX_TERMS], lb[TS_MAX_TERMS];
-    u64* out01;
-    u64* out2;
-    unsigned long long stride01, stride2;       // words between instances
-    u32 logn, L, n_terms;
-};
+// TsArgs, the kernel's arguments, is hexl_internal.hpp's: the hybrid multiply (keyswitch_hybrid.hip) fills one too
 static_assert(sizeof(TsArgs) <= 4096, "the kernel arguments of k_ct_tensor_sum must fit the 4 KiB kernarg segment");
 
 // One workgroup per (instance, limb, piece of the polynomial), as k_pt_mul and k_ct_lincomb: the limb -- and with it the modulus -- is
@@ -120,7 +105,7 @@ __global__ __launch_bounds__(TS_THREADS) void k_ct_tensor_sum(TsArgs s) {
 }
 
 // nb instances: `s` with its operand and output pointers at the first of them
-static int launch_tensor(hexl_ks_plan* p, const TsArgs& s, size_t nb) {
+int hx_launch_tensor(hexl_ks_plan* p, const TsArgs& s, size_t nb) {
     const dim3 grid((u32)hx_ww_grid(p, nb, s.L)), block(TS_THREADS);
     hipStream_t st = p->ctx->stream;
     switch (s.n_terms) {
@@ -179,8 +164,8 @@ static int relin_slices(hexl_ks_plan* p, u64* d_out, size_t batch, F fill) {
 // stubs for them) ----
 // The operands of a tensor sum, checked and laid into `s` (pointers at instance 0): HEXL_E_BADARG for a null entry, a limb count outside
 // n_limbs ... K, or an operand that shares a byte with [d_out, d_out + out_bytes) -- the layouts differ, so there is no in-place form.
-static int tensor_operands(const hexl_ks_plan* p, const u64* const* d_as, const u64* const* d_bs, const u64* in_limbs, size_t n_terms,
-                           size_t batch, u64 n_limbs, const u64* d_out, size_t out_bytes, TsArgs& s) {
+int hx_tensor_operands(const hexl_ks_plan* p, const u64* const* d_as, const u64* const* d_bs, const u64* in_limbs, size_t n_terms,
+                       size_t batch, u64 n_limbs, const u64* d_out, size_t out_bytes, TsArgs& s) {
     const size_t poly = size_t(p->n) * sizeof(u64);
     for (size_t t = 0; t < n_terms; ++t) {
         const u64 la = in_limbs ? in_limbs[2 * t] : n_limbs, lb = in_limbs ? in_limbs[2 * t + 1] : n_limbs;
@@ -210,13 +195,13 @@ extern "C" int hexl_ct_tensor_sum(hexl_ks_plan* p, uint64_t* d_out, const uint64
         !hx_ww_grid_ok(p, batch, n_limbs))
         return HEXL_E_BADARG;
     TsArgs s{};
-    if (int rc = tensor_operands(p, d_as, d_bs, in_limbs, n_terms, batch, n_limbs, d_out, out_bytes, s)) return rc;
+    if (int rc = hx_tensor_operands(p, d_as, d_bs, in_limbs, n_terms, batch, n_limbs, d_out, out_bytes, s)) return rc;
     if (!batch) return 0;
     s.out01 = d_out;
     s.out2 = d_out + 2 * size_t(n_limbs) * p->n;
     s.stride01 = s.stride2 = 3ull * n_limbs * p->n;
     HX_CHECK(hipSetDevice(p->ctx->device));
-    return launch_tensor(p, s, batch);
+    return hx_launch_tensor(p, s, batch);
 }
 
 extern "C" int hexl_relinearize(hexl_ks_plan* p, uint64_t* d_out, const uint64_t* d_ct3, size_t batch) {
@@ -245,7 +230,7 @@ extern "C" int hexl_multiply_sum_relinearize(hexl_ks_plan* p, uint64_t* d_out, c
         !hx_ww_grid_ok(p, hx_ks_chunk_of(p, batch), p->L))
         return HEXL_E_BADARG;
     TsArgs s{};
-    if (int rc = tensor_operands(p, d_as, d_bs, in_limbs, n_terms, batch, p->L, d_out, out_bytes, s)) return rc;
+    if (int rc = hx_tensor_operands(p, d_as, d_bs, in_limbs, n_terms, batch, p->L, d_out, out_bytes, s)) return rc;
     if (!p->have_keys) return HEXL_E_NOKEYS;
     if (!batch) return 0;
     HX_CHECK(hipSetDevice(p->ctx->device));
@@ -260,6 +245,6 @@ extern "C" int hexl_multiply_sum_relinearize(hexl_ks_plan* p, uint64_t* d_out, c
         }
         c.out01 = out;
         c.out2 = t;
-        return launch_tensor(p, c, nb);
+        return hx_launch_tensor(p, c, nb);
     });
 }

@@ -316,6 +316,28 @@ int hx_launch_galois_add(hexl_ks_plan* p, u64* d_out, const u64* d_t, size_t nb,
 int hx_launch_rns_ntt(hexl_ks_plan*, u64* d_out, const u64* d_in, size_t count, u32 n_limbs, bool inverse);
 int hx_launch_multiply_plain(hexl_ks_plan*, u64* d_out, const u64* d_ct, const u64* d_pt, size_t batch, u32 n_components, u32 n_limbs,
                              bool per_instance, bool accumulate);
+// The ciphertext tensor sum (ct_tensor.hip k_ct_tensor_sum). Pointers and limb counts travel BY VALUE in the kernel arguments, as
+// k_ct_lincomb's (rns_ops.hip): nothing is uploaded, so the host arrays are the caller's again when the call returns. The output goes
+// through TWO descriptors -- components 0-1 of instance b at out01 + b stride01 (laid out [2][L][n]), component 2 at out2 + b stride2
+// ([L][n]) -- so that one kernel writes hexl_ct_tensor_sum's [batch][3][L][n] buffer and, for the fused multiplies
+// (hexl_multiply_sum_relinearize; keyswitch_hybrid.hip hexl_hks_multiply_sum_*), a two-component buffer and the key switch's input slice.
+constexpr u32 TS_MAX_TERMS = 8, TS_MAX_LIMBS = 16;                // hexl_ks_plan::tier has 16 limbs
+struct TsArgs {
+    const KsModF64* mods;       // [K]
+    const u64* a[TS_MAX_TERMS]; // term t: [batch][2][la[t]][n], read through its first L limbs
+    const u64* b[TS_MAX_TERMS]; //         [batch][2][lb[t]][n]; may be a[t] (a square)
+    u32 la[TS_MAX_TERMS], lb[TS_MAX_TERMS];
+    u64* out01;
+    u64* out2;
+    unsigned long long stride01, stride2;       // words between instances
+    u32 logn, L, n_terms;
+};
+// The operands of a tensor sum, checked and laid into `s` (pointers at instance 0): HEXL_E_BADARG for a null entry, a limb count outside
+// n_limbs ... K, or an operand that shares a byte with [d_out, d_out + out_bytes). hx_launch_tensor: nb instances on the context's
+// stream, `s` with its operand and output pointers at the first of them.
+int hx_tensor_operands(const hexl_ks_plan* p, const u64* const* d_as, const u64* const* d_bs, const u64* in_limbs, size_t n_terms,
+                       size_t batch, u64 n_limbs, const u64* d_out, size_t out_bytes, TsArgs& s);
+int hx_launch_tensor(hexl_ks_plan* p, const TsArgs& s, size_t nb);
 // device-side encode / decode (ckks_encode.hip); arguments checked by their entry points (hexl_rns_from_f64, hexl_rns_to_f64,
 // hexl_ckks_encode, hexl_ckks_decode). d_slots = nullptr: the real coefficients themselves are the caller's (d_coeffs).
 int hx_launch_encode(hexl_ks_plan*, u64* d_out, const double* d_coeffs, const double* d_slots, size_t count, u32 n_limbs, double scale);

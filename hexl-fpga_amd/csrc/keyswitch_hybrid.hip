@@ -3,12 +3,17 @@
 // (hexl_hks borrows the plan's context, stream, moduli, constants and tables, and owns its keys, conversion constants and scratch).
 // Per chunk of instances at level l (T_l = {0 .. l-1} + S, S = {L .. K-1}, dl = ceil(l / alpha) digits), every line modulo its limb:
 //   1   a_i = INTT_i(t[i]), canonical words; ext_d[i] = t[i] for the digit d that holds i                              k_hks_intt
-//   2a  y_i = a_i (D/q_i)^-1;  x_d[j] = sum_{i in G_d} y_i (D/q_i mod q_j)  for every j in T_l outside the digit       k_hks_conv<false>
+//   2a  y_i = a_i (D/q_i)^-1;  x_d[j] = sum_{i in G_d} y_i (D/q_i mod q_j)  for every j in T_l outside the digit       k_hks_conv<UP>
 //   2b  ext_d[j] = NTT_j(x_d[j]), in place                                                                             k_hks_fwd
 //   3   acc[k][j] = sum_d ext_d[j] key[d][k][j]                                                                        k_hks_mac
 //   4a  b_s = (INTT_s(acc[k][s]) + floor(P/2)) mod q_s for s in S, in place                                            k_hks_intt_sp
-//   4b  w_i = sum_s b_s (P/q_s)^-1 (P/q_s mod q_i) + fix_i  for i < l                                                  k_hks_conv<true>
+//   4b  w_i = sum_s b_s (P/q_s)^-1 (P/q_s mod q_i) + fix_i  for i < l                                                  k_hks_conv<DOWN>
 //   4c  result[k][i] += (acc[k][i] - NTT_i(w_i)) P^-1                                                                   k_hks_down
+// The hybrid multiply (hexl_hks_relinearize_rescale, hexl_hks_multiply_sum_rescale) replaces step 4 by ONE mod-down that
+// divides X_k = P d_k + KSacc_k by R = P q_(l-1), from the source basis B = S + {l - 1} into the limbs i < l - 1:
+//   4a' b_s = (INTT_s(acc'[k][s]) + floor(R/2)) mod q_s for s in B, in place; acc'[k][l-1] = acc[k][l-1] + (P mod q) d_k[l-1]    k_hks_rs_intt
+//   4b' w_i = sum_{s in B} b_s (R/q_s)^-1 (R/q_s mod q_i) + fix_i  for i < l - 1                                        k_hks_conv<RS>
+//   4c' out[k][i] = (acc[k][i] + (P mod q_i) d_k[i] - NTT_i(w_i)) R^-1, WRITTEN, [2][l - 1][n]                            k_hks_rs_down
 // The hoisted callers (hexl_hks_rotate_hoisted, hexl_hks_linear_transform) run steps 1-2 ONCE per chunk on c1 of the
 // ciphertexts, read in place, and step 3 per rotation with sigma_g applied to ext on the way in and the keys of that rotation's object:
 //   3g  acc[k][j] = sum_d sigma_g(ext_d[j]) key_r[d][k][j]   (stored, or weighted by a plaintext and summed over the rotations)   k_hks_mac_galois
@@ -31,6 +36,12 @@ struct HksDown {                                                  // per plan li
     double fix;              // i < L: q_i - (floor(P/2) mod q_i), in [1, q_i]
     double half;             // s in S: floor(P/2) mod q_s
 };
+struct HksRs {                                                    // per (level l >= 2, plan limb): the rescaling mod-down, R = P q_(l-1)
+    double rinv, rinv_p;     // i < l - 1: R^-1 mod q_i centred, fl(. / q_i)
+    double fix;              // i < l - 1: q_i - (floor(R/2) mod q_i), in [1, q_i]
+    double half;             // s in S or s = l - 1: floor(R/2) mod q_s
+    double pm, pm_p;         // i < l: P mod q_i centred, fl(. / q_i)
+};
 
 struct hexl_hks {
     hexl_ks_plan* plan = nullptr;
@@ -40,6 +51,10 @@ struct hexl_hks {
     HxDevBuf<HksSrc> d_src;           // [17][16]: row l - 1 = level l (source limb i of its digit), row 16 = the mod-down (source s in S)
     HxDevBuf<HksWt> d_wt;             // [17][16][16]: (row, source limb, target limb)
     HxDevBuf<HksDown> d_down;         // [K]
+    // the rescaling mod-down (hexl_hks_relinearize_rescale), row l - 1 = level l >= 2: sources S and the limb l - 1, targets i < l - 1
+    HxDevBuf<HksSrc> d_rs_src;        // [16][16]: (level, source limb)
+    HxDevBuf<HksWt> d_rs_wt;          // [16][16][16]: (level, source limb, target limb)
+    HxDevBuf<HksRs> d_rs;             // [16][16]: (level, plan limb)
     // scratch of one chunk, grow-only (the stream drain rule of the context: everything runs on its stream)
     HxDevBuf<u64> d_coef;             // [chunk][L][n]        a_i, canonical, natural order; after step 3: w of component 0 (doubles)
     HxDevBuf<double> d_ext;           // [chunk][dnum][K][n]  x_d, then ext_d; after step 3 its first l rows per instance: w of component 1
@@ -50,20 +65,25 @@ struct hexl_hks {
     // hexl_hks_linear_transform_bsgs, both grow-only and allocated at its first call
     HxDevBuf<double> d_bsgs_b;        // baby store: [n_baby][chunk][2][K][n], slice i = the stored sums of baby step i, [nb][2][T][n] of it used
     HxDevBuf<u64> d_bsgs_t;           // one giant step's inner sum t_j: [chunk][2][L][n] canonical words ([nb][2][l][n] of it used)
+    HxDevBuf<u64> d_d01;              // hexl_hks_multiply_sum_rescale: (d0, d1) of one chunk's tensor sums, [chunk][2][L][n] (grow-only,
+                                      // [nb][2][l][n] of it used; allocated at its first call)
     explicit hexl_hks(hexl_ks_plan* p)
-        : plan(p), d_keys(p->ctx), d_src(p->ctx), d_wt(p->ctx), d_down(p->ctx), d_coef(p->ctx), d_ext(p->ctx), d_acc(p->ctx), d_slice(p->ctx),
-          d_w1(p->ctx), d_bsgs_b(p->ctx), d_bsgs_t(p->ctx) {}
+        : plan(p), d_keys(p->ctx), d_src(p->ctx), d_wt(p->ctx), d_down(p->ctx), d_rs_src(p->ctx), d_rs_wt(p->ctx), d_rs(p->ctx), d_coef(p->ctx), d_ext(p->ctx), d_acc(p->ctx), d_slice(p->ctx),
+          d_w1(p->ctx), d_bsgs_b(p->ctx), d_bsgs_t(p->ctx), d_d01(p->ctx) {}
 };
 
 struct HksArgs {
     const KsModF64* mods;       // [K]
     const double* tables;       // [K][4][n] (keyswitch_f64.hip KsArgsF)
-    const HksSrc* src;          // [16]: the level's row (k_hks_conv<true>: the mod-down row)
+    const HksSrc* src;          // [16]: the level's row (k_hks_conv<DOWN>: the mod-down row)
     const HksWt* wt;            // [16][16]
     const HksDown* down;        // [K]
+    const HksRs* rs;            // [16]: the level's row (the rescaling mod-down; its src / wt rows are set for k_hks_conv<HKS_CONV_RS>)
     const double* keys;         // [dnum][2][K][n]
     const u64* t;               // [nb][tstride][n], rows 0 ... l - 1 of an instance are read (tstride = l, or 2 l for c1 of a ciphertext in place)
-    u64* result;                // [nb][2][l][n]
+    u64* result;                // [nb][2][l][n] (the rescaling mod-down: [nb][2][l - 1][n])
+    const u64* d01;             // the rescaling mod-down: word of (d_k, instance b, limb i) at d01 + b d01_stride + (k l + i) n
+    unsigned long long d01_stride;
     u64* coef;                  // [nb][l][n]
     double* ext;                // [nb][dl][T][n]
     double* acc;                // [nb][2][T][n]
@@ -197,6 +217,78 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_down(HksArgs a) {
     }
 }
 
+// step 4a', one workgroup per (row of B = S + {l - 1}, instance, component), in place: k_hks_intt_sp with floor(R/2) for floor(P/2) and
+// one more row per (instance, component) -- the data limb l - 1, which takes (P mod q) d_k on the way in (step 3'). That row of acc is
+// dead for everything else: the rescaled output has no limb l - 1.
+template <int LOGN, int LOGE, int LAZY>
+__global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_rs_intt(HksArgs a) {
+    using G = Geom<LOGN, LOGE>;
+    extern __shared__ __attribute__((aligned(16))) double ldsd[];
+    const int tid = threadIdx.x;
+    const u32 np = a.K - a.L;
+    const u32 si = blockIdx.x / (2 * a.nb), bk = blockIdx.x - si * 2 * a.nb;
+    const bool data = si == np;                                  // (uniform)
+    const u32 s = data ? a.l - 1 : a.L + si, jT = data ? a.l - 1 : a.l + si;
+    const KsModF64 md = a.mods[s];
+    const Mod m = md.m;
+    const HksRs rs = a.rs[s];
+    const double* tb = a.tables + size_t(s) * 4 * G::N;
+    double* row = a.acc + (size_t(bk) * a.T + jT) * G::N;
+    const u32 tB = u32(G::idxB(0, tid));
+    double v[G::E];
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) v[r] = (row + G::idxB(r, 0))[tB];               // an hks_mac_term output: |v| <= q_s/2 + 2
+    if (data) {
+        const u64* dk = a.d01 + size_t(bk >> 1) * a.d01_stride + (size_t(bk & 1) * a.l + s) * G::N;
+#pragma unroll
+        for (int r = 0; r < G::E; ++r) v[r] = hxf::hks_acc_pd(v[r], hxf::to_f64((dk + G::idxB(r, 0))[tB]), rs.pm, rs.pm_p, m);
+    }
+    with_tier<LAZY, LOGN == 14>(a.tiermap, s, [&](auto T) {
+        WgNttF64<LOGN, LOGE, decltype(T)::value, InvNoWpOpt<true>>::template inverse<true>(
+            v, ldsd, tid, tb + 2 * G::N, tb + 3 * G::N, m, md.sc);
+    });
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) (row + G::idxA(r, 0))[u32(tid)] = hxf::hks_round(v[r], rs.half, m);
+}
+
+// step 4c', one workgroup per (limb i < l - 1, instance, component): k_hks_down with d_k in place of the old result word, R^-1 in place
+// of P^-1, and the output WRITTEN in the [2][l - 1][n] layout. acc and d_k are requested behind the transform, in groups of eight
+// registers as there.
+template <int LOGN, int LOGE, int LAZY>
+__global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_rs_down(HksArgs a) {
+    using G = Geom<LOGN, LOGE>;
+    extern __shared__ __attribute__((aligned(16))) double ldsd[];
+    const int tid = threadIdx.x;
+    const u32 i = blockIdx.x / (2 * a.nb), bk = blockIdx.x - i * 2 * a.nb;
+    const u32 b = bk >> 1, k = bk & 1;
+    const Mod m = a.mods[i].m;
+    const HksRs rs = a.rs[i];
+    const double* tb = a.tables + size_t(i) * 4 * G::N;
+    const double* w = hks_w(a, b, k, i, G::N);
+    double v[G::E];
+#pragma unroll
+    for (int r = 0; r < G::E; ++r) v[r] = hxf::reduce((w + G::idxA(r, 0))[u32(tid)], m);
+    with_tier<LAZY, LOGN == 14>(a.tiermap, i, [&](auto T) {
+        WgNttF64<LOGN, LOGE, decltype(T)::value, HksFwdOpt>::template forward<true, true>(v, ldsd, tid, tb, tb + G::N, m);
+    });
+    const double* pk = a.acc + (size_t(bk) * a.T + i) * G::N;
+    const u64* dk = a.d01 + size_t(b) * a.d01_stride + (size_t(k) * a.l + i) * G::N;
+    u64* res = a.result + (size_t(bk) * (a.l - 1) + i) * G::N;
+    const u32 tB = u32(G::idxB(0, tid));
+    constexpr int GRP = G::E < 8 ? G::E : 8;
+#pragma unroll
+    for (int r0 = 0; r0 < G::E; r0 += GRP) {
+        double pv[GRP];
+        u64 dv[GRP];
+#pragma unroll
+        for (int r = 0; r < GRP; ++r) { pv[r] = (pk + G::idxB(r0 + r, 0))[tB]; dv[r] = (dk + G::idxB(r0 + r, 0))[tB]; }
+#pragma unroll
+        for (int r = 0; r < GRP; ++r)
+            (res + G::idxB(r0 + r, 0))[tB] =
+                hxf::from_f64(hxf::hks_down_rs(hxf::to_f64(dv[r]), pv[r], v[r0 + r], rs.pm, rs.pm_p, rs.rinv, rs.rinv_p, m));
+    }
+}
+
 // ---- the word-wise kernels: 256 lanes, a lane owns two adjacent indices (16-byte accesses), a workgroup 512 of them ----
 constexpr u32 HKS_THREADS = 256, HKS_LOG_PIECE = 9;
 static_assert(HKS_THREADS * 2 == 1u << HKS_LOG_PIECE, "a workgroup covers its piece exactly");
@@ -206,27 +298,34 @@ static_assert(HKS_THREADS == HX_WW_THREADS, "hx_ww_grid(., ., ., HKS_LOG_PIECE) 
 // (mod-up: sources the words a_i of G_d, targets every row of T_l outside the digit) or component k (DOWN: sources b_s, s in S, targets
 // the data limbs i < l, fix_i added). Per coefficient the <= MAXS source words are loaded and y formed ONCE; every target limb reduces y
 // into its own range before the products (hks_conv_term). Moduli and weights of a target are wave-uniform: scalar loads.
-template <bool DOWN, int MAXS>
+// HKS_CONV_RS is the mod-down of the rescaling calls: one more source per component, the row l - 1 of acc (limb l - 1, not contiguous
+// with the special rows), one target fewer, and the constants of R = P q_(l-1) (a.src / a.wt: the level's row of d_rs_src / d_rs_wt).
+enum HksConv : int { HKS_CONV_UP, HKS_CONV_DOWN, HKS_CONV_RS };
+template <HksConv MODE, int MAXS>
 __global__ __launch_bounds__(HKS_THREADS) void k_hks_conv(HksArgs a) {
     typedef double d2 __attribute__((ext_vector_type(2)));
     typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
+    constexpr bool DOWN = MODE != HKS_CONV_UP, RS = MODE == HKS_CONV_RS;
     const u32 lp = a.logn - HKS_LOG_PIECE;
     const u32 grp = blockIdx.x >> lp, piece = blockIdx.x - (grp << lp);
     const u32 ng = DOWN ? 2u : a.dl;
     const u32 b = grp / ng, g = grp - b * ng;
     const size_t n = size_t(1) << a.logn, c = (size_t(piece) << HKS_LOG_PIECE) + 2 * threadIdx.x;
     const u32 s0 = DOWN ? a.L : g * a.alpha;                      // first source limb (plan index)
-    const u32 ns = DOWN ? a.K - a.L : (a.l - s0 < a.alpha ? a.l - s0 : a.alpha);
+    const u32 ns = RS ? a.K - a.L + 1 : DOWN ? a.K - a.L : (a.l - s0 < a.alpha ? a.l - s0 : a.alpha);
+    // source si: its plan limb, and (the mod-downs) its row of T_l in acc -- RS: the last source is the data limb l - 1
+    auto src_limb = [&](u32 si) { return RS && si + 1 == ns ? a.l - 1 : s0 + si; };
+    auto src_row = [&](u32 si) { return RS && si + 1 == ns ? a.l - 1 : a.l + si; };
     double y[MAXS][2];
 #pragma unroll
     for (int si = 0; si < MAXS; ++si)
         if (si < (int)ns) {
-            const u32 i = s0 + si;
+            const u32 i = src_limb(si);
             const Mod m = a.mods[i].m;
             const HksSrc hs = a.src[i];
             double v[2];
             if constexpr (DOWN) {
-                const d2 t = *reinterpret_cast<const d2*>(a.acc + ((size_t(b) * 2 + g) * a.T + a.l + si) * n + c);
+                const d2 t = *reinterpret_cast<const d2*>(a.acc + ((size_t(b) * 2 + g) * a.T + src_row(si)) * n + c);
                 v[0] = t.x; v[1] = t.y;
             } else {
                 const u2 t = *reinterpret_cast<const u2*>(a.coef + (size_t(b) * a.l + i) * n + c);
@@ -235,7 +334,7 @@ __global__ __launch_bounds__(HKS_THREADS) void k_hks_conv(HksArgs a) {
             y[si][0] = hxf::hks_digit(v[0], hs.hinv, hs.hinv_p, m);
             y[si][1] = hxf::hks_digit(v[1], hs.hinv, hs.hinv_p, m);
         }
-    const u32 nt = DOWN ? a.l : a.T;
+    const u32 nt = RS ? a.l - 1 : DOWN ? a.l : a.T;
     for (u32 jT = 0; jT < nt; ++jT) {
         const u32 j = hks_limb(a, jT);
         if (!DOWN && j >= s0 && j < s0 + ns) continue;            // inside the digit: k_hks_intt wrote the row
@@ -244,11 +343,11 @@ __global__ __launch_bounds__(HKS_THREADS) void k_hks_conv(HksArgs a) {
 #pragma unroll
         for (int si = 0; si < MAXS; ++si)
             if (si < (int)ns) {
-                const HksWt wt = a.wt[(s0 + si) * HKS_MAX_LIMBS + j];
+                const HksWt wt = a.wt[src_limb(si) * HKS_MAX_LIMBS + j];
                 acc0 = hxf::hks_conv_term(acc0, y[si][0], wt.w, wt.wp, m);
                 acc1 = hxf::hks_conv_term(acc1, y[si][1], wt.w, wt.wp, m);
             }
-        const double fix = DOWN ? a.down[j].fix : 0.0;
+        const double fix = RS ? a.rs[j].fix : DOWN ? a.down[j].fix : 0.0;
         const d2 o = {hxf::hks_conv_finish(acc0, fix, m), hxf::hks_conv_finish(acc1, fix, m)};
         double* dst = DOWN ? hks_w(a, b, g, jT, n) : a.ext + ((size_t(b) * a.dl + g) * a.T + jT) * n;
         *reinterpret_cast<d2*>(dst + c) = o;
@@ -491,7 +590,7 @@ static int hks_stage_up(hexl_hks* h, const HksArgs& a) {
     const u32 nb = a.nb;
     hipLaunchKernelGGL((k_hks_intt<LOGN, LOGE, LAZY>), dim3(a.l * nb), wg, G::LDS_USED, st, a);
     hks_with_max(a.alpha < a.l ? a.alpha : a.l, [&](auto M) {
-        hipLaunchKernelGGL((k_hks_conv<false, decltype(M)::value>), dim3(hks_piece_grid(p, size_t(nb) * a.dl)), ww, 0, st, a);
+        hipLaunchKernelGGL((k_hks_conv<HKS_CONV_UP, decltype(M)::value>), dim3(hks_piece_grid(p, size_t(nb) * a.dl)), ww, 0, st, a);
     });
     hipLaunchKernelGGL((k_hks_fwd<LOGN, LOGE, LAZY>), dim3(a.T * a.dl * nb), wg, G::LDS_USED, st, a);
     return (int)hipGetLastError();
@@ -535,9 +634,29 @@ static int hks_stage_down(hexl_hks* h, const HksArgs& a) {
     dn.src = h->d_src + size_t(HKS_DOWN_ROW) * HKS_MAX_LIMBS;
     dn.wt = h->d_wt + size_t(HKS_DOWN_ROW) * HKS_MAX_LIMBS * HKS_MAX_LIMBS;
     hks_with_max(np, [&](auto M) {
-        hipLaunchKernelGGL((k_hks_conv<true, decltype(M)::value>), dim3(hks_piece_grid(p, size_t(nb) * 2)), ww, 0, st, dn);
+        hipLaunchKernelGGL((k_hks_conv<HKS_CONV_DOWN, decltype(M)::value>), dim3(hks_piece_grid(p, size_t(nb) * 2)), ww, 0, st, dn);
     });
     hipLaunchKernelGGL((k_hks_down<LOGN, LOGE, LAZY>), dim3(a.l * 2 * nb), wg, G::LDS_USED, st, a);
+    return (int)hipGetLastError();
+}
+
+// step 4' in place of step 4 (a.rs, a.d01 and a.result set by the caller; l >= 2)
+template <int LOGN, int LOGE, int LAZY>
+static int hks_stage_down_rs(hexl_hks* h, const HksArgs& a) {
+    using G = Geom<LOGN, LOGE>;
+    hexl_ks_plan* p = h->plan;
+    if (int rc = hx_lds_optin<k_hks_rs_intt<LOGN, LOGE, LAZY>, k_hks_rs_down<LOGN, LOGE, LAZY>>(p->ctx->device, G::LDS_USED)) return rc;
+    hipStream_t st = p->ctx->stream;
+    const dim3 wg(G::T), ww(HKS_THREADS);
+    const u32 nb = a.nb, nsrc = a.K - a.L + 1;
+    hipLaunchKernelGGL((k_hks_rs_intt<LOGN, LOGE, LAZY>), dim3(nsrc * 2 * nb), wg, G::LDS_USED, st, a);
+    HksArgs dn = a;
+    dn.src = h->d_rs_src + size_t(a.l - 1) * HKS_MAX_LIMBS;
+    dn.wt = h->d_rs_wt + size_t(a.l - 1) * HKS_MAX_LIMBS * HKS_MAX_LIMBS;
+    hks_with_max(nsrc, [&](auto M) {
+        hipLaunchKernelGGL((k_hks_conv<HKS_CONV_RS, decltype(M)::value>), dim3(hks_piece_grid(p, size_t(nb) * 2)), ww, 0, st, dn);
+    });
+    hipLaunchKernelGGL((k_hks_rs_down<LOGN, LOGE, LAZY>), dim3((a.l - 1) * 2 * nb), wg, G::LDS_USED, st, a);
     return (int)hipGetLastError();
 }
 
@@ -545,7 +664,7 @@ template <int LOGN, int LOGE, int LAZY>
 static int hks_run_chunk(hexl_hks* h, const HksArgs& a) {
     if (int rc = hks_stage_up<LOGN, LOGE, LAZY>(h, a)) return rc;
     if (int rc = hks_stage_mac(h, a)) return rc;
-    return hks_stage_down<LOGN, LOGE, LAZY>(h, a);
+    return a.d01 ? hks_stage_down_rs<LOGN, LOGE, LAZY>(h, a) : hks_stage_down<LOGN, LOGE, LAZY>(h, a);
 }
 
 static size_t hks_chunk_of(const hexl_hks* h, size_t batch) { return hx_ks_chunk_of(h->plan, batch); }
@@ -567,6 +686,7 @@ static HksArgs hks_args(const hexl_hks* h, u32 l) {
     a.src = h->d_src + size_t(l - 1) * HKS_MAX_LIMBS;
     a.wt = h->d_wt + size_t(l - 1) * HKS_MAX_LIMBS * HKS_MAX_LIMBS;
     a.down = h->d_down;
+    a.rs = h->d_rs + size_t(l - 1) * HKS_MAX_LIMBS;
     a.keys = h->d_keys;
     a.coef = h->d_coef; a.ext = h->d_ext; a.acc = h->d_acc;
     a.L = p->L; a.K = p->K; a.l = l; a.T = l + h->np;
@@ -600,33 +720,42 @@ static int hks_constants(hexl_hks* h) {
     const std::vector<u64>& q = p->moduli;
     std::vector<HksSrc> src(size_t(HKS_DOWN_ROW + 1) * HKS_MAX_LIMBS, HksSrc{0.0, 0.0});
     std::vector<HksWt> wt(size_t(HKS_DOWN_ROW + 1) * HKS_MAX_LIMBS * HKS_MAX_LIMBS, HksWt{0.0, 0.0});
-    // the sources lo ... hi - 1 convert into the targets of `targets`: (D / q_i)^-1 mod q_i and (D / q_i) mod q_j, D their product
-    auto fill = [&](u32 row, u32 lo, u32 hi, const std::vector<u32>& targets) {
-        for (u32 i = lo; i < hi; ++i) {
+    // the limbs of `sources` convert into the targets of `targets` (a target that is a source is skipped): (D / q_i)^-1 mod q_i and
+    // (D / q_i) mod q_j, D the sources' product
+    auto fill = [&](std::vector<HksSrc>& src, std::vector<HksWt>& wt, u32 row, const std::vector<u32>& sources, const std::vector<u32>& targets) {
+        auto is_source = [&](u32 j) {
+            for (u32 o : sources)
+                if (o == j) return true;
+            return false;
+        };
+        for (u32 i : sources) {
             auto hat_mod = [&](u64 m) {
                 u64 r = 1 % m;
-                for (u32 o = lo; o < hi; ++o)
+                for (u32 o : sources)
                     if (o != i) r = hxnt::mulmod(r, q[o] % m, m);
                 return r;
             };
             const double hinv = hx_centre(hxnt::invmod(hat_mod(q[i]), q[i]), q[i]);
             src[size_t(row) * HKS_MAX_LIMBS + i] = HksSrc{hinv, hinv / (double)q[i]};
             for (u32 j : targets) {
-                if (j >= lo && j < hi) continue;
+                if (is_source(j)) continue;
                 const double w = hx_centre(hat_mod(q[j]), q[j]);
                 wt[(size_t(row) * HKS_MAX_LIMBS + i) * HKS_MAX_LIMBS + j] = HksWt{w, w / (double)q[j]};
             }
         }
     };
+    auto limbs = [](u32 lo, u32 hi) {
+        std::vector<u32> v;
+        for (u32 i = lo; i < hi; ++i) v.push_back(i);
+        return v;
+    };
     for (u32 l = 1; l <= L; ++l) {
         std::vector<u32> basis;
         for (u32 j = 0; j < l; ++j) basis.push_back(j);
         for (u32 s = L; s < K; ++s) basis.push_back(s);
-        for (u32 lo = 0; lo < l; lo += alpha) fill(l - 1, lo, lo + alpha < l ? lo + alpha : l, basis);
+        for (u32 lo = 0; lo < l; lo += alpha) fill(src, wt, l - 1, limbs(lo, lo + alpha < l ? lo + alpha : l), basis);
     }
-    std::vector<u32> data;
-    for (u32 i = 0; i < L; ++i) data.push_back(i);
-    fill(HKS_DOWN_ROW, L, K, data);
+    fill(src, wt, HKS_DOWN_ROW, limbs(L, K), limbs(0, L));
     std::vector<HksDown> down(K, HksDown{0.0, 0.0, 0.0, 0.0});
     for (u32 i = 0; i < K; ++i) {
         u64 P = 1 % q[i];
@@ -640,6 +769,37 @@ static int hks_constants(hexl_hks* h) {
             down[i].half = (double)half;
         }
     }
+    // the rescaling mod-down of every level l >= 2 (row l - 1): R = P q_(l-1), sources B = S + {l - 1}, targets i < l - 1
+    std::vector<HksSrc> rs_src(size_t(HKS_MAX_LIMBS) * HKS_MAX_LIMBS, HksSrc{0.0, 0.0});
+    std::vector<HksWt> rs_wt(size_t(HKS_MAX_LIMBS) * HKS_MAX_LIMBS * HKS_MAX_LIMBS, HksWt{0.0, 0.0});
+    std::vector<HksRs> rs(size_t(HKS_MAX_LIMBS) * HKS_MAX_LIMBS, HksRs{0.0, 0.0, 0.0, 0.0, 0.0, 0.0});
+    for (u32 l = 2; l <= L; ++l) {
+        std::vector<u32> B = limbs(L, K);
+        B.push_back(l - 1);
+        fill(rs_src, rs_wt, l - 1, B, limbs(0, l - 1));
+        for (u32 i = 0; i < K; ++i) {
+            if (i >= l && i < L) continue;
+            u64 P = 1 % q[i];
+            for (u32 s = L; s < K; ++s) P = hxnt::mulmod(P, q[s] % q[i], q[i]);
+            const u64 R = hxnt::mulmod(P, q[l - 1] % q[i], q[i]);
+            // floor(R / 2) = (R - 1) / 2 for the odd R, as floor(P / 2) above (R = 0 modulo a source limb)
+            const u64 half = hxnt::mulmod((R + q[i] - 1) % q[i], (q[i] + 1) / 2, q[i]);
+            HksRs& c = rs[size_t(l - 1) * HKS_MAX_LIMBS + i];
+            c.half = (double)half;
+            if (i < l) {
+                c.pm = hx_centre(P, q[i]);
+                c.pm_p = c.pm / (double)q[i];
+            }
+            if (i < l - 1) {
+                c.rinv = hx_centre(hxnt::invmod(R, q[i]), q[i]);
+                c.rinv_p = c.rinv / (double)q[i];
+                c.fix = (double)(q[i] - half);
+            }
+        }
+    }
+    if (int rc = h->d_rs_src.upload_once(rs_src.data(), rs_src.size())) return rc;
+    if (int rc = h->d_rs_wt.upload_once(rs_wt.data(), rs_wt.size())) return rc;
+    if (int rc = h->d_rs.upload_once(rs.data(), rs.size())) return rc;
     if (int rc = h->d_src.upload_once(src.data(), src.size())) return rc;
     if (int rc = h->d_wt.upload_once(wt.data(), wt.size())) return rc;
     return h->d_down.upload_once(down.data(), down.size());
@@ -755,6 +915,113 @@ extern "C" int hexl_hks_rotate(hexl_hks* h, uint64_t* d_out, const uint64_t* d_c
 extern "C" size_t hexl_hks_scratch_bytes(const hexl_hks* h, size_t batch) {
     if (!h) return 0;
     return hks_chunk_of(h, batch) * hks_words_per_instance(h) * h->plan->n * sizeof(u64);
+}
+
+// ---- the hybrid multiply: the tensor sum, the key switch of its component 2 and -- the rescaling calls -- ONE mod-down
+// by R = P q_(l-1) instead of the key switch's by P and hexl_rescale's by q_(l-1). The tensor kernel is ct_tensor.hip's, launched through
+// hx_launch_tensor with its two output descriptors pointed at this object's buffers. ----
+// What the two tensor-fed entry points check alike, everything HEXL_E_BADARG: arrays, term count, handle and level (lo ... L), operand
+// entries and their overlap with d_out[batch][2][out_limbs][n], sizes and grids. `s` comes back with the operands laid in.
+static bool hks_mul_ok(const hexl_hks* h, const u64* d_out, const u64* const* d_as, const u64* const* d_bs, const u64* in_limbs, size_t n_terms,
+                       size_t batch, u64 n_limbs, u64 lo, u64 out_limbs, TsArgs& s) {
+    if (!h || !d_out || !d_as || !d_bs || !hx_in_range(n_terms, 1, TS_MAX_TERMS) || n_limbs < lo) return false;
+    size_t bytes, out_bytes, buffers;
+    if (!hks_call_ok(h, batch, n_limbs, 2, &bytes)) return false;
+    const hexl_ks_plan* p = h->plan;
+    // the largest operand has K limbs: if that size fits, every other one does; the slice and d01 buffers; the tensor kernel's grid
+    if (!hx_words_bytes(batch, 2, p->K, p->n, &bytes) || !hx_words_bytes(batch, 2, out_limbs, p->n, &out_bytes) ||
+        !hx_words_bytes(hks_chunk_of(h, batch), 3, p->L, p->n, &buffers) || !hx_ww_grid_ok(p, hks_chunk_of(h, batch), n_limbs) ||
+        !hx_wg_grid_ok(hks_chunk_of(h, batch), 2 * u64(p->K)))
+        return false;
+    return hx_tensor_operands(p, d_as, d_bs, in_limbs, n_terms, batch, n_limbs, d_out, out_bytes, s) == 0;
+}
+// the tensor sums of instances b0 ... b0 + nb - 1: components 0-1 to out01 ([nb][2][l][n]), component 2 to out2 ([nb][l][n])
+static int hks_mul_tensor(hexl_ks_plan* p, const TsArgs& s, size_t b0, size_t nb, u64* out01, u64* out2) {
+    const size_t n = p->n;
+    TsArgs c = s;
+    for (u32 k = 0; k < s.n_terms; ++k) {
+        c.a[k] += b0 * 2 * c.la[k] * n;
+        c.b[k] += b0 * 2 * c.lb[k] * n;
+    }
+    c.out01 = out01;
+    c.out2 = out2;
+    c.stride01 = 2ull * s.L * n;
+    c.stride2 = 1ull * s.L * n;
+    return hx_launch_tensor(p, c, nb);
+}
+
+extern "C" int hexl_hks_multiply_sum_relinearize(hexl_hks* h, uint64_t* d_out, const uint64_t* const* d_as, const uint64_t* const* d_bs,
+                                                 const uint64_t* in_limbs, size_t n_terms, size_t batch, uint64_t n_limbs) {
+    TsArgs s{};
+    if (!hks_mul_ok(h, d_out, d_as, d_bs, in_limbs, n_terms, batch, n_limbs, 1, n_limbs, s)) return HEXL_E_BADARG;
+    if (!h->have_keys) return HEXL_E_NOKEYS;
+    if (!batch) return 0;
+    hexl_ks_plan* p = h->plan;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    return hks_slices(h, d_out, batch, (u32)n_limbs, [&](size_t b0, size_t nb, u64* out, u64* t) { return hks_mul_tensor(p, s, b0, nb, out, t); });
+}
+
+// The rescaling key switch of `batch` instances at level l >= 2, chunk by chunk on the context's stream: d_out[batch][2][l - 1][n] WRITTEN.
+// feed(b0, nb, a) points a.t / a.tstride at the chunk's d2 and a.d01 / a.d01_stride at its (d0, d1), launching what fills them.
+template <class F>
+static int hks_launch_rs(hexl_hks* h, u64* d_out, size_t batch, u32 l, F feed) {
+    hexl_ks_plan* p = h->plan;
+    const size_t n = p->n;
+    const size_t chunk = hks_chunk_of(h, batch);
+    if (int rc = hks_reserve(h, chunk)) return rc;
+    HksArgs a = hks_args(h, l);
+    const int lazy = hks_level_tier(p, l);
+    return hx_for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
+        a.result = d_out + b0 * 2 * (l - 1) * n;
+        a.nb = (u32)nb;
+        if (int rc = feed(b0, nb, a)) return rc;
+        return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return hks_run_chunk<N, E, Z>(h, a); });
+    });
+}
+
+extern "C" int hexl_hks_relinearize_rescale(hexl_hks* h, uint64_t* d_out, const uint64_t* d_ct3, size_t batch, uint64_t n_limbs) {
+    size_t in_bytes;
+    if (!d_out || !d_ct3 || n_limbs < 2 || !hks_call_ok(h, batch, n_limbs, 3, &in_bytes)) return HEXL_E_BADARG;
+    if (hx_ranges_overlap(d_out, in_bytes / (3 * n_limbs) * 2 * (n_limbs - 1), d_ct3, in_bytes)) return HEXL_E_BADARG;
+    if (!hx_wg_grid_ok(hks_chunk_of(h, batch), 2 * u64(h->plan->K))) return HEXL_E_BADARG;
+    if (!h->have_keys) return HEXL_E_NOKEYS;
+    if (!batch) return 0;
+    HX_CHECK(hipSetDevice(h->plan->ctx->device));
+    const size_t n = h->plan->n, l = n_limbs;
+    // d2 and (d0, d1) are read where they lie: no split copy
+    return hks_launch_rs(h, d_out, batch, (u32)l, [&](size_t b0, size_t, HksArgs& a) {
+        a.d01 = d_ct3 + b0 * 3 * l * n;
+        a.d01_stride = 3ull * l * n;
+        a.t = a.d01 + 2 * l * n;
+        a.tstride = 3 * (u32)l;
+        return 0;
+    });
+}
+
+extern "C" int hexl_hks_multiply_sum_rescale(hexl_hks* h, uint64_t* d_out, const uint64_t* const* d_as, const uint64_t* const* d_bs,
+                                             const uint64_t* in_limbs, size_t n_terms, size_t batch, uint64_t n_limbs) {
+    TsArgs s{};
+    if (!hks_mul_ok(h, d_out, d_as, d_bs, in_limbs, n_terms, batch, n_limbs, 2, n_limbs - 1, s)) return HEXL_E_BADARG;
+    if (!h->have_keys) return HEXL_E_NOKEYS;
+    if (!batch) return 0;
+    hexl_ks_plan* p = h->plan;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    const size_t n = p->n, l = n_limbs, chunk = hks_chunk_of(h, batch);
+    if (int rc = h->d_slice.reserve(chunk * p->L * n)) return rc;
+    if (int rc = h->d_d01.reserve(chunk * 2 * p->L * n)) return rc;
+    // one lane: the next chunk's tensor kernel overwrites the two buffers behind this chunk's last kernel that reads them
+    return hks_launch_rs(h, d_out, batch, (u32)l, [&](size_t b0, size_t nb, HksArgs& a) {
+        a.d01 = h->d_d01;
+        a.d01_stride = 2ull * l * n;
+        a.t = h->d_slice;
+        a.tstride = (u32)l;
+        return hks_mul_tensor(p, s, b0, nb, h->d_d01, h->d_slice);
+    });
+}
+
+extern "C" size_t hexl_hks_mul_scratch_bytes(const hexl_hks* h, size_t batch) {
+    if (!h) return 0;
+    return hexl_hks_scratch_bytes(h, batch) + hks_chunk_of(h, batch) * 3 * h->plan->L * h->plan->n * sizeof(u64);
 }
 
 // ---- the hoisted callers: many rotations of one ciphertext batch share steps 1-2 (hexl_hks_rotate_hoisted), and step 4 as well

@@ -570,7 +570,8 @@ int hexl_ks_gen_keys(hexl_ks_plan* plan, const uint64_t* d_secret, int from_kind
  * HEXL_E_BADARG: a null handle or pointer (batch == 0 does not excuse it), a plan on the integer kernels or with K = L, alpha outside
  * 1 ... L, n_limbs outside 1 ... L, a galois_elt that is even or >= 2n, an output that overlaps an input, a size or a grid that
  * overflows; then HEXL_E_NOKEYS before hexl_hks_set_keys_device; then batch == 0 returns 0.
- * Device memory, owned by the object: the keys (dnum*2*K*n doubles), 74 KiB of constants for all levels (computed at create time), and
+ * Device memory, owned by the object: the keys (dnum*2*K*n doubles), 154 KiB of constants for all levels (computed at create time: 74 KiB
+ * for the key switch, 80 KiB for the rescaling mod-down of the hybrid multiply below), and
  * grow-only scratch for one chunk of min(batch, chunk) instances, chunk as for hexl_keyswitch (256 at n = 16384, the same number of
  * coefficients at other n; HEXL_KS_CHUNK): per instance L*n coefficient words, dnum*K*n extended doubles and 2*K*n accumulator doubles.
  * hexl_hks_scratch_bytes(hks, batch) is that sum at the full level (a lower level uses less of it). hexl_hks_relinearize and
@@ -677,6 +678,48 @@ size_t hexl_hks_hoisted_scratch_bytes(const hexl_hks* hks, size_t batch);
  * hexl_hks_hoisted_scratch_bytes are unchanged. */
 int hexl_hks_linear_transform_bsgs(hexl_hks* const* baby_hks, const uint64_t* baby_elts, size_t n_baby, hexl_hks* const* giant_hks, const uint64_t* giant_elts, size_t n_giant, const uint64_t* const* d_pts, const uint64_t* const* d_pt_identity, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t n_limbs);
 size_t hexl_hks_bsgs_scratch_bytes(const hexl_hks* hks, size_t n_baby, size_t batch);
+/* The hybrid multiply: a sum of ciphertext products, its relinearisation on the hybrid key and -- the two rescaling
+ * calls -- the rescale, in one call. On the hybrid gadget a product is otherwise hexl_ct_tensor_sum, hexl_hks_relinearize and
+ * hexl_rescale: the three-component sum and the un-rescaled ciphertext each pass through memory, and two mod-downs run (by P, then by
+ * q_(l-1)): 2 n_p + 4 l transforms per instance behind the multiply-accumulate. The rescaling calls divide ONCE, by R = P q_(l-1) from the
+ * source basis S and {l - 1}: 2 n_p + 2 l transforms (L = 12, alpha = 4, n_p = 4: 80 instead of 104) and one rounding instead of two.
+ *   d_as, d_bs, in_limbs, n_terms   as for hexl_ct_tensor_sum: HOST arrays of 1 ... 8 DEVICE operands [batch][2][in_limbs][n], in_limbs
+ *               NULL or 2 n_terms entries in l ... K; every operand is read through its first l limbs; d_bs[t] may be d_as[t].
+ *   n_limbs = l the level of the product. d_ct3 DEVICE [batch][3][l][n] = (d0, d1, d2).
+ *   hexl_hks_multiply_sum_relinearize   1 <= l <= L. d_out [batch][2][l][n] WRITTEN, word for word
+ *               hexl_ct_tensor_sum(plan, tmp, d_as, d_bs, in_limbs, n_terms, batch, l) then hexl_hks_relinearize(hks, d_out, tmp, batch, l);
+ *               the three-component sum never exists in memory.
+ *   hexl_hks_relinearize_rescale        2 <= l <= L. d_out [batch][2][l - 1][n] WRITTEN, as defined below.
+ *   hexl_hks_multiply_sum_rescale       2 <= l <= L. d_out [batch][2][l - 1][n] WRITTEN, word for word hexl_ct_tensor_sum at level l then
+ *               hexl_hks_relinearize_rescale; neither the three-component sum nor an un-rescaled ciphertext exists in memory.
+ * hexl_hks_relinearize_rescale per instance, every line modulo its limb's modulus and every stored word canonical (normative):
+ *   1-3 steps 1-3 of the hexl_hks_keyswitch definition applied to t = d2 at level l: acc[k][j] for k in {0, 1}, j in T_l
+ *   3'  acc'[k][i] = acc[k][i] + (P mod q_i) . d_k[i] for i < l;  acc'[k][s] = acc[k][s] for s in S
+ *       (P d_k vanishes modulo every special prime: acc'[k] is the residue vector of X_k = P d_k + KSacc_k modulo Q_l P)
+ *   4'  R = P q_(l-1) (odd), h = (R - 1) / 2, B = S and {l - 1}:
+ *       for s in B   b_s = INTT_s(acc'[k][s]) + (h mod q_s),  z_s = b_s . ((R / q_s)^-1 mod q_s);
+ *       for i < l - 1   w_i = sum_{s in B} z_s . ((R / q_s) mod q_i)  and
+ *         out[k][i] = (acc'[k][i] - NTT_i((w_i + fix_i) mod q_i)) . (R^-1 mod q_i),  fix_i = q_i - (h mod q_i)
+ * Consequence: for every coefficient out_k = round(X_k / R) - e with e an integer in [0, n_p] -- the uncorrected conversion from the
+ * n_p + 1 sources overshoots by at most n_p multiples of R. The fused result is therefore NOT word for word hexl_hks_relinearize
+ * followed by hexl_rescale: that route rounds twice, this one once. Both decrypt alike.
+ * Noise: for CBD21 key errors and a ternary secret, with D(s) = d0 + d1 s + d2 s^2 lifted centred modulo Q_l, out_0 + out_1 s equals
+ * D(s) / q_(l-1) up to an error of infinity norm at most
+ *   21 n sum_d |G_d| D_d / (P q_(l-1)) + (n_p + 1/2)(n + 1).
+ * All three are asynchronous on the context's stream, on one lane; the host arrays may be reused on return. Precondition: every input
+ * word is below its modulus; like the rest of the hybrid family they do NOT raise the input-range flag (hexl_ks_range_check).
+ * HEXL_E_BADARG: a null handle, pointer or array entry (batch == 0 does not excuse it); n_terms outside 1 ... 8; n_limbs outside its
+ * range (the lower bound is 2 for the two rescaling calls); an in_limbs entry outside l ... K; d_out overlapping any operand or d_ct3; a
+ * size or a grid that overflows. Then HEXL_E_NOKEYS before hexl_hks_set_keys_device; then batch == 0 returns 0 with nothing written.
+ * Device memory on the object, grow-only, beside the key switch's scratch: the slice buffer of hexl_hks_relinearize (chunk x L x n words:
+ * component 2 of one chunk's tensor sums) and, for hexl_hks_multiply_sum_rescale, (d0, d1) of one chunk (chunk x 2 x L x n words).
+ * hexl_hks_relinearize_rescale reads d0, d1 and d2 where they lie and needs neither. hexl_hks_mul_scratch_bytes(hks, batch) is
+ * hexl_hks_scratch_bytes plus both buffers; hexl_hks_scratch_bytes, hexl_hks_hoisted_scratch_bytes and hexl_hks_bsgs_scratch_bytes are
+ * unchanged. */
+int hexl_hks_multiply_sum_relinearize(hexl_hks* hks, uint64_t* d_out, const uint64_t* const* d_as, const uint64_t* const* d_bs, const uint64_t* in_limbs, size_t n_terms, size_t batch, uint64_t n_limbs);
+int hexl_hks_relinearize_rescale(hexl_hks* hks, uint64_t* d_out, const uint64_t* d_ct3, size_t batch, uint64_t n_limbs);
+int hexl_hks_multiply_sum_rescale(hexl_hks* hks, uint64_t* d_out, const uint64_t* const* d_as, const uint64_t* const* d_bs, const uint64_t* in_limbs, size_t n_terms, size_t batch, uint64_t n_limbs);
+size_t hexl_hks_mul_scratch_bytes(const hexl_hks* hks, size_t batch);
 /* Arithmetic tier per limb (introspection for logs and tests): tiers[i], i < key_modulus_size, = the forward transforms' range-
  * reduction period modulo q_i on the FP64 path -- 12 / 6 / 3 for q_i <= 2^49 / 2^50 / 2^51 (1 + 2^-7), 0 = every value reduced after
  * every operation (q_i up to 2^52); -1 for every limb of a plan on the integer kernels (a modulus >= 2^52). Every transform runs modulo
