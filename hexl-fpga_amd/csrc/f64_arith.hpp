@@ -173,7 +173,7 @@ HX_HD double f64_to_residue(double c, const Mod m) {
     return reduce(mul_mod(reduce(a, m), reduce(2147483648.0, m), m) + reduce(b, m), m);
 }
 
-// ---- the scalar chains of the hybrid key switch (keyswitch_hybrid.hip k_hks_conv, k_hks_mac, k_hks_intt_sp, k_hks_down), here so that
+// ---- the scalar chains of the hybrid key switch (keyswitch_hybrid.hip k_hks_conv, k_hks_mac, k_hks_down_intt, k_hks_down), here so that
 // tests/cpp/hks_selftest.cpp replays the kernels' own source against __int128 for every pairing of a source limb with a target limb ----
 // y = a (D / q_i)^-1 mod q_i, canonical: a a canonical word of limb i as a double (0 <= a < q_i < 2^52, exact), (hinv, hinv_p) the
 // inverse centred and fl(./q_i); m = q_i. a is inside mul_shoup's |x| <= 1.5p as it is, |product| <= p: reduce and lift take that.
@@ -201,13 +201,13 @@ HX_HD double hks_round(double v, double half, const Mod m) { return lift(reduce(
 HX_HD double hks_down(double old, double acc, double w, double pinv, double pinv_p, const Mod m) {
     return lift(reduce(old + mul_shoup(acc - w, pinv, pinv_p, m), m), m);
 }
-// ---- the rescaling mod-down of the hybrid multiply (keyswitch_hybrid.hip k_hks_rs_intt, k_hks_rs_down), replayed by
+// ---- the rescaling mod-down of the hybrid multiply (keyswitch_hybrid.hip k_hks_down_intt<., true>, k_hks_down<., true>), replayed by
 // tests/cpp/hks_mul_selftest.cpp. The base conversion between the two is hks_digit / hks_conv_term / hks_conv_finish unchanged, and the
 // rounding of the n_p + 1 source rows is hks_round with half = floor(R/2) mod q_s.
 // acc' = (acc + (P mod q) d) mod q, centred (step 3'): acc an output of hks_mac_term (|acc| <= q/2 + 2), d a canonical word of the same
 // limb as a double (0 <= d < q < 2^52, exact), (pm, pm_p) = P mod q centred and fl(./q); m = q. d is inside mul_shoup's |x| <= 1.5p as it
 // is, |product| <= (0.5 + d / (2p)) p <= p; |acc + product| <= 1.5p + 2 < 2^53: an exact integer inside reduce's domain, and
-// |acc'| <= q/2 + 2 -- what the inverse transform of k_hks_rs_intt takes, as k_hks_intt_sp's takes an hks_mac_term output.
+// |acc'| <= q/2 + 2 -- what the inverse transform of k_hks_down_intt<., true> takes, as that of k_hks_down_intt<., false> takes an hks_mac_term output.
 HX_HD double hks_acc_pd(double acc, double d, double pm, double pm_p, const Mod m) { return reduce(acc + mul_shoup(d, pm, pm_p, m), m); }
 // out = (acc + (P mod q_i) d - w) R^-1 mod q_i, canonical (step 4'): acc and d as for hks_acc_pd, w the range-reduced output of NTT_i
 // (|w| <= q_i/2 + 2), (rinv, rinv_p) = R^-1 mod q_i centred and fl(./q_i); m = q_i. |acc' - w| <= p + 4, inside mul_shoup's 1.5p,

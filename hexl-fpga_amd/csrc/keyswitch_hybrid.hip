@@ -6,17 +6,18 @@
 //   2a  y_i = a_i (D/q_i)^-1;  x_d[j] = sum_{i in G_d} y_i (D/q_i mod q_j)  for every j in T_l outside the digit       k_hks_conv<UP>
 //   2b  ext_d[j] = NTT_j(x_d[j]), in place                                                                             k_hks_fwd
 //   3   acc[k][j] = sum_d ext_d[j] key[d][k][j]                                                                        k_hks_mac
-//   4a  b_s = (INTT_s(acc[k][s]) + floor(P/2)) mod q_s for s in S, in place                                            k_hks_intt_sp
+//   4a  b_s = (INTT_s(acc[k][s]) + floor(P/2)) mod q_s for s in S, in place                                            k_hks_down_intt<false>
 //   4b  w_i = sum_s b_s (P/q_s)^-1 (P/q_s mod q_i) + fix_i  for i < l                                                  k_hks_conv<DOWN>
-//   4c  result[k][i] += (acc[k][i] - NTT_i(w_i)) P^-1                                                                   k_hks_down
+//   4c  result[k][i] += (acc[k][i] - NTT_i(w_i)) P^-1                                                                   k_hks_down<false>
 // The hybrid multiply (hexl_hks_relinearize_rescale, hexl_hks_multiply_sum_rescale) replaces step 4 by ONE mod-down that
-// divides X_k = P d_k + KSacc_k by R = P q_(l-1), from the source basis B = S + {l - 1} into the limbs i < l - 1:
-//   4a' b_s = (INTT_s(acc'[k][s]) + floor(R/2)) mod q_s for s in B, in place; acc'[k][l-1] = acc[k][l-1] + (P mod q) d_k[l-1]    k_hks_rs_intt
+// divides X_k = P d_k + KSacc_k by R = P q_(l-1), from the source basis B = S + {l - 1} into the limbs i < l - 1 -- the same three kernels
+// with RS set, on the rows of the constants that belong to R:
+//   4a' b_s = (INTT_s(acc'[k][s]) + floor(R/2)) mod q_s for s in B, in place; acc'[k][l-1] = acc[k][l-1] + (P mod q) d_k[l-1]    k_hks_down_intt<true>
 //   4b' w_i = sum_{s in B} b_s (R/q_s)^-1 (R/q_s mod q_i) + fix_i  for i < l - 1                                        k_hks_conv<RS>
-//   4c' out[k][i] = (acc[k][i] + (P mod q_i) d_k[i] - NTT_i(w_i)) R^-1, WRITTEN, [2][l - 1][n]                            k_hks_rs_down
+//   4c' out[k][i] = (acc[k][i] + (P mod q_i) d_k[i] - NTT_i(w_i)) R^-1, WRITTEN, [2][l - 1][n]                            k_hks_down<true>
 // The hoisted callers (hexl_hks_rotate_hoisted, hexl_hks_linear_transform) run steps 1-2 ONCE per chunk on c1 of the
 // ciphertexts, read in place, and step 3 per rotation with sigma_g applied to ext on the way in and the keys of that rotation's object:
-//   3g  acc[k][j] = sum_d sigma_g(ext_d[j]) key_r[d][k][j]   (stored, or weighted by a plaintext and summed over the rotations)   k_hks_mac_galois
+//   3g  acc[k][j] = sum_d sigma_g(ext_d[j]) key_r[d][k][j]   (stored, or weighted by a plaintext and summed over the rotations)   k_hks_mac, a mode with HksRot
 // The transforms are one workgroup per polynomial on WgNttF64, limb-major, as k_rns_fwd / k_rns_inv (rns_ops.hip) and k_rs_intt /
 // k_rs_down (ckks_ops.hip); every intermediate lies at its LOGICAL index (coefficients in natural order, NTT form in the transforms'
 // output order), so the word-wise kernels between them need no index map and the keys keep the caller's order. The scalar chains
@@ -28,33 +29,32 @@
 using namespace hx;
 
 constexpr u32 HKS_MAX_LIMBS = 16;                                 // hexl_ks_plan::tier has 16 limbs
-constexpr u32 HKS_DOWN_ROW = 16;                                  // row of the conversion tables that holds the mod-down (S -> data limbs)
+// The base conversions of every level, one CONVERSION ROW of the source and weight tables each:
+//   row l - 1        the mod-up of level l (sources: the limbs of a digit; targets: T_l outside the digit)
+//   row 16           the mod-down by P, the same at every level (sources S; targets the data limbs)
+//   row 16 + (l - 1) the rescaling mod-down of level l >= 2 (sources S and the limb l - 1; targets i < l - 1)
+// and one DIVISOR ROW of the third table per divisor of a mod-down: row 0 for P, row l - 1 for R = P q_(l-1).
+enum HksConv : int { HKS_CONV_UP, HKS_CONV_DOWN, HKS_CONV_RS };
+constexpr u32 HKS_CONV_ROWS = 2 * HKS_MAX_LIMBS;
 struct HksSrc { double hinv, hinv_p; };                           // (D / q_i)^-1 mod q_i centred, and fl(. / q_i)
 struct HksWt { double w, wp; };                                   // (D / q_i) mod q_j centred, and fl(. / q_j)
-struct HksDown {                                                  // per plan limb
-    double pinv, pinv_p;     // i < L: P^-1 mod q_i centred, fl(. / q_i)
-    double fix;              // i < L: q_i - (floor(P/2) mod q_i), in [1, q_i]
-    double half;             // s in S: floor(P/2) mod q_s
+struct HksDiv {                                                   // per (divisor Q = P or R, plan limb)
+    double inv, inv_p;       // a target limb i: Q^-1 mod q_i centred, fl(. / q_i)
+    double fix;              // a target limb i: q_i - (floor(Q/2) mod q_i), in [1, q_i]
+    double half;             // a source limb s: floor(Q/2) mod q_s
+    double pm, pm_p;         // Q = R, i < l: P mod q_i centred, fl(. / q_i)
 };
-struct HksRs {                                                    // per (level l >= 2, plan limb): the rescaling mod-down, R = P q_(l-1)
-    double rinv, rinv_p;     // i < l - 1: R^-1 mod q_i centred, fl(. / q_i)
-    double fix;              // i < l - 1: q_i - (floor(R/2) mod q_i), in [1, q_i]
-    double half;             // s in S or s = l - 1: floor(R/2) mod q_s
-    double pm, pm_p;         // i < l: P mod q_i centred, fl(. / q_i)
-};
+static size_t hks_conv_row(HksConv mode, u32 l) { return mode == HKS_CONV_UP ? l - 1 : mode == HKS_CONV_DOWN ? HKS_MAX_LIMBS : HKS_MAX_LIMBS + (l - 1); }
+static size_t hks_div_row(HksConv mode, u32 l) { return mode == HKS_CONV_RS ? l - 1 : 0; }
 
 struct hexl_hks {
     hexl_ks_plan* plan = nullptr;
     u32 alpha = 0, dnum = 0, np = 0;
     bool have_keys = false;
     HxDevBuf<double> d_keys;          // [dnum][2][K][n] centred, the caller's order
-    HxDevBuf<HksSrc> d_src;           // [17][16]: row l - 1 = level l (source limb i of its digit), row 16 = the mod-down (source s in S)
-    HxDevBuf<HksWt> d_wt;             // [17][16][16]: (row, source limb, target limb)
-    HxDevBuf<HksDown> d_down;         // [K]
-    // the rescaling mod-down (hexl_hks_relinearize_rescale), row l - 1 = level l >= 2: sources S and the limb l - 1, targets i < l - 1
-    HxDevBuf<HksSrc> d_rs_src;        // [16][16]: (level, source limb)
-    HxDevBuf<HksWt> d_rs_wt;          // [16][16][16]: (level, source limb, target limb)
-    HxDevBuf<HksRs> d_rs;             // [16][16]: (level, plan limb)
+    HxDevBuf<HksSrc> d_src;           // [32][16]: (conversion row, source limb)
+    HxDevBuf<HksWt> d_wt;             // [32][16][16]: (conversion row, source limb, target limb)
+    HxDevBuf<HksDiv> d_div;           // [16][16]: (divisor row, plan limb)
     // scratch of one chunk, grow-only (the stream drain rule of the context: everything runs on its stream)
     HxDevBuf<u64> d_coef;             // [chunk][L][n]        a_i, canonical, natural order; after step 3: w of component 0 (doubles)
     HxDevBuf<double> d_ext;           // [chunk][dnum][K][n]  x_d, then ext_d; after step 3 its first l rows per instance: w of component 1
@@ -68,18 +68,18 @@ struct hexl_hks {
     HxDevBuf<u64> d_d01;              // hexl_hks_multiply_sum_rescale: (d0, d1) of one chunk's tensor sums, [chunk][2][L][n] (grow-only,
                                       // [nb][2][l][n] of it used; allocated at its first call)
     explicit hexl_hks(hexl_ks_plan* p)
-        : plan(p), d_keys(p->ctx), d_src(p->ctx), d_wt(p->ctx), d_down(p->ctx), d_rs_src(p->ctx), d_rs_wt(p->ctx), d_rs(p->ctx), d_coef(p->ctx), d_ext(p->ctx), d_acc(p->ctx), d_slice(p->ctx),
+        : plan(p), d_keys(p->ctx), d_src(p->ctx), d_wt(p->ctx), d_div(p->ctx), d_coef(p->ctx), d_ext(p->ctx), d_acc(p->ctx), d_slice(p->ctx),
           d_w1(p->ctx), d_bsgs_b(p->ctx), d_bsgs_t(p->ctx), d_d01(p->ctx) {}
 };
 
 struct HksArgs {
     const KsModF64* mods;       // [K]
     const double* tables;       // [K][4][n] (keyswitch_f64.hip KsArgsF)
-    const HksSrc* src;          // [16]: the level's row (k_hks_conv<DOWN>: the mod-down row)
-    const HksWt* wt;            // [16][16]
-    const HksDown* down;        // [K]
-    const HksRs* rs;            // [16]: the level's row (the rescaling mod-down; its src / wt rows are set for k_hks_conv<HKS_CONV_RS>)
-    const double* keys;         // [dnum][2][K][n]
+    const HksSrc* src;          // [16]: the conversion row of the launch (hks_point_rows: the level's mod-up, or the stage's mod-down)
+    const HksWt* wt;            // [16][16]: the same row
+    const void* reserved;       // never set or read (see the assertion behind the struct)
+    const HksDiv* div;          // [16]: the divisor row of the launch
+    const double* keys;        // [dnum][2][K][n]
     const u64* t;               // [nb][tstride][n], rows 0 ... l - 1 of an instance are read (tstride = l, or 2 l for c1 of a ciphertext in place)
     u64* result;                // [nb][2][l][n] (the rescaling mod-down: [nb][2][l - 1][n])
     const u64* d01;             // the rescaling mod-down: word of (d_k, instance b, limb i) at d01 + b d01_stride + (k l + i) n
@@ -92,6 +92,9 @@ struct HksArgs {
     unsigned long long limbmap; // nibble jT = plan limb of row jT of T_l (T_l is not a prefix of the plan's limbs when l < L)
     unsigned long long tiermap; // LAZY = -1: nibble i = reduction period of limb i (keyswitch_f64.hip)
 };
+// the kernels of steps 1-3 do not read the divisor constants and keep the instruction streams they had while every field they load keeps
+// its kernel-argument offset: `reserved` stands where the second of the two former constants pointers stood
+static_assert(offsetof(HksArgs, div) == 40 && offsetof(HksArgs, keys) == 48 && sizeof(HksArgs) == 176, "HksArgs: kernel-argument offsets");
 __device__ __forceinline__ u32 hks_limb(const HksArgs& a, u32 jT) { return u32(a.limbmap >> (4 * jT)) & 15u; }
 // w of (instance b, component k, limb i): component 0 in the coefficient buffer, component 1 in the first rows of the instance's ext block
 // (both are dead once step 3 has run, and dl * T >= l) -- or in a buffer of its own where ext has to survive step 4 (uniform)
@@ -156,84 +159,24 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_fwd(HksArgs a) {
     for (int r = 0; r < G::E; ++r) (row + G::idxB(r, 0))[tB] = v[r];
 }
 
-// step 4a, one workgroup per (s in S, instance, component), in place: b_s = (INTT_s(acc[k][s]) + floor(P/2)) mod q_s, canonical
-template <int LOGN, int LOGE, int LAZY>
-__global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_intt_sp(HksArgs a) {
-    using G = Geom<LOGN, LOGE>;
-    extern __shared__ __attribute__((aligned(16))) double ldsd[];
-    const int tid = threadIdx.x;
-    const u32 si = blockIdx.x / (2 * a.nb), bk = blockIdx.x - si * 2 * a.nb;
-    const u32 s = a.L + si;
-    const KsModF64 md = a.mods[s];
-    const Mod m = md.m;
-    const double half = a.down[s].half;
-    const double* tb = a.tables + size_t(s) * 4 * G::N;
-    double* row = a.acc + (size_t(bk) * a.T + a.l + si) * G::N;
-    const u32 tB = u32(G::idxB(0, tid));
-    double v[G::E];
-#pragma unroll
-    for (int r = 0; r < G::E; ++r) v[r] = (row + G::idxB(r, 0))[tB];               // an hks_mac_term output: |v| <= q_s/2 + 2
-    with_tier<LAZY, LOGN == 14>(a.tiermap, s, [&](auto T) {
-        WgNttF64<LOGN, LOGE, decltype(T)::value, InvNoWpOpt<true>>::template inverse<true>(
-            v, ldsd, tid, tb + 2 * G::N, tb + 3 * G::N, m, md.sc);
-    });
-#pragma unroll
-    for (int r = 0; r < G::E; ++r) (row + G::idxA(r, 0))[u32(tid)] = hxf::hks_round(v[r], half, m);
-}
-
-// step 4c, one workgroup per (limb i < l, instance, component): k_rs_down's shape -- the transform of w, then the subtract-multiply-
-// accumulate epilogue on acc and the word `result` holds. acc and result are requested behind the transform (k_rs_down's LAZY < 0 form).
-template <int LOGN, int LOGE, int LAZY>
-__global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_down(HksArgs a) {
-    using G = Geom<LOGN, LOGE>;
-    extern __shared__ __attribute__((aligned(16))) double ldsd[];
-    const int tid = threadIdx.x;
-    const u32 i = blockIdx.x / (2 * a.nb), bk = blockIdx.x - i * 2 * a.nb;
-    const u32 b = bk >> 1, k = bk & 1;
-    const Mod m = a.mods[i].m;
-    const HksDown dn = a.down[i];
-    const double* tb = a.tables + size_t(i) * 4 * G::N;
-    const double* w = hks_w(a, b, k, i, G::N);
-    double v[G::E];
-#pragma unroll
-    for (int r = 0; r < G::E; ++r) v[r] = hxf::reduce((w + G::idxA(r, 0))[u32(tid)], m);
-    with_tier<LAZY, LOGN == 14>(a.tiermap, i, [&](auto T) {
-        WgNttF64<LOGN, LOGE, decltype(T)::value, HksFwdOpt>::template forward<true, true>(v, ldsd, tid, tb, tb + G::N, m);
-    });
-    const double* pk = a.acc + (size_t(bk) * a.T + i) * G::N;
-    u64* res = a.result + (size_t(bk) * a.l + i) * G::N;
-    const u32 tB = u32(G::idxB(0, tid));
-    // in groups of eight registers: beside the 2^LOGE words of w, all of acc and result do not fit the registers of N = 32768
-    constexpr int GRP = G::E < 8 ? G::E : 8;
-#pragma unroll
-    for (int r0 = 0; r0 < G::E; r0 += GRP) {
-        double pv[GRP];
-        u64 old[GRP];
-#pragma unroll
-        for (int r = 0; r < GRP; ++r) { pv[r] = (pk + G::idxB(r0 + r, 0))[tB]; old[r] = (res + G::idxB(r0 + r, 0))[tB]; }
-#pragma unroll
-        for (int r = 0; r < GRP; ++r)
-            (res + G::idxB(r0 + r, 0))[tB] = hxf::from_f64(hxf::hks_down(hxf::to_f64(old[r]), pv[r], v[r0 + r], dn.pinv, dn.pinv_p, m));
-    }
-}
-
-// step 4a', one workgroup per (row of B = S + {l - 1}, instance, component), in place: k_hks_intt_sp with floor(R/2) for floor(P/2) and
-// one more row per (instance, component) -- the data limb l - 1, which takes (P mod q) d_k on the way in (step 3'). That row of acc is
-// dead for everything else: the rescaled output has no limb l - 1.
-template <int LOGN, int LOGE, int LAZY>
-__global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_rs_intt(HksArgs a) {
+// Steps 4a and 4c, and 4a' and 4c' of the rescaling calls (RS): the mod-down by the divisor Q whose row a.div is, Q = P or R = P q_(l-1).
+// step 4a, one workgroup per (source row, instance, component), in place: b_s = (INTT_s(acc[k][s]) + floor(Q/2)) mod q_s, canonical.
+// The sources are the rows of S; RS: one more per (instance, component), the data limb l - 1, which takes (P mod q) d_k on the way in
+// (step 3'). That row of acc is dead for everything else: the rescaled output has no limb l - 1.
+template <int LOGN, int LOGE, int LAZY, bool RS>
+__global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_down_intt(HksArgs a) {
     using G = Geom<LOGN, LOGE>;
     extern __shared__ __attribute__((aligned(16))) double ldsd[];
     const int tid = threadIdx.x;
     const u32 np = a.K - a.L;
     const u32 si = blockIdx.x / (2 * a.nb), bk = blockIdx.x - si * 2 * a.nb;
-    const bool data = si == np;                                  // (uniform)
+    const bool data = RS && si == np;                            // (uniform)
     const u32 s = data ? a.l - 1 : a.L + si, jT = data ? a.l - 1 : a.l + si;
     const KsModF64 md = a.mods[s];
     const Mod m = md.m;
-    const HksRs rs = a.rs[s];
+    const HksDiv dv = a.div[s];
     const double* tb = a.tables + size_t(s) * 4 * G::N;
-    double* row = a.acc + (size_t(bk) * a.T + jT) * G::N;
+    double* row = a.acc + (RS ? size_t(bk) * a.T + jT : size_t(bk) * a.T + a.l + si) * G::N;   // one row; each mode's own sum order
     const u32 tB = u32(G::idxB(0, tid));
     double v[G::E];
 #pragma unroll
@@ -241,28 +184,28 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_rs_intt(HksArgs a) {
     if (data) {
         const u64* dk = a.d01 + size_t(bk >> 1) * a.d01_stride + (size_t(bk & 1) * a.l + s) * G::N;
 #pragma unroll
-        for (int r = 0; r < G::E; ++r) v[r] = hxf::hks_acc_pd(v[r], hxf::to_f64((dk + G::idxB(r, 0))[tB]), rs.pm, rs.pm_p, m);
+        for (int r = 0; r < G::E; ++r) v[r] = hxf::hks_acc_pd(v[r], hxf::to_f64((dk + G::idxB(r, 0))[tB]), dv.pm, dv.pm_p, m);
     }
     with_tier<LAZY, LOGN == 14>(a.tiermap, s, [&](auto T) {
         WgNttF64<LOGN, LOGE, decltype(T)::value, InvNoWpOpt<true>>::template inverse<true>(
             v, ldsd, tid, tb + 2 * G::N, tb + 3 * G::N, m, md.sc);
     });
 #pragma unroll
-    for (int r = 0; r < G::E; ++r) (row + G::idxA(r, 0))[u32(tid)] = hxf::hks_round(v[r], rs.half, m);
+    for (int r = 0; r < G::E; ++r) (row + G::idxA(r, 0))[u32(tid)] = hxf::hks_round(v[r], dv.half, m);
 }
 
-// step 4c', one workgroup per (limb i < l - 1, instance, component): k_hks_down with d_k in place of the old result word, R^-1 in place
-// of P^-1, and the output WRITTEN in the [2][l - 1][n] layout. acc and d_k are requested behind the transform, in groups of eight
-// registers as there.
-template <int LOGN, int LOGE, int LAZY>
-__global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_rs_down(HksArgs a) {
+// step 4c, one workgroup per (target limb i, instance, component): k_rs_down's shape -- the transform of w, then the epilogue on acc and
+// a second word, both requested behind the transform (k_rs_down's LAZY < 0 form). The second word is the one `result` holds, and the
+// output is accumulated onto it, [2][l][n]; RS: it is d_k, which enters as (P mod q_i) d_k, and the output is WRITTEN, [2][l - 1][n].
+template <int LOGN, int LOGE, int LAZY, bool RS>
+__global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_down(HksArgs a) {
     using G = Geom<LOGN, LOGE>;
     extern __shared__ __attribute__((aligned(16))) double ldsd[];
     const int tid = threadIdx.x;
     const u32 i = blockIdx.x / (2 * a.nb), bk = blockIdx.x - i * 2 * a.nb;
     const u32 b = bk >> 1, k = bk & 1;
     const Mod m = a.mods[i].m;
-    const HksRs rs = a.rs[i];
+    const HksDiv dv = a.div[i];
     const double* tb = a.tables + size_t(i) * 4 * G::N;
     const double* w = hks_w(a, b, k, i, G::N);
     double v[G::E];
@@ -272,20 +215,24 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_rs_down(HksArgs a) {
         WgNttF64<LOGN, LOGE, decltype(T)::value, HksFwdOpt>::template forward<true, true>(v, ldsd, tid, tb, tb + G::N, m);
     });
     const double* pk = a.acc + (size_t(bk) * a.T + i) * G::N;
-    const u64* dk = a.d01 + size_t(b) * a.d01_stride + (size_t(k) * a.l + i) * G::N;
-    u64* res = a.result + (size_t(bk) * (a.l - 1) + i) * G::N;
+    const u64* dk = RS ? a.d01 + size_t(b) * a.d01_stride + (size_t(k) * a.l + i) * G::N : nullptr;
+    u64* res = a.result + (size_t(bk) * (RS ? a.l - 1 : a.l) + i) * G::N;
+    const u64* second = RS ? dk : res;
     const u32 tB = u32(G::idxB(0, tid));
+    // in groups of eight registers: beside the 2^LOGE words of w, all of acc and the second words do not fit the registers of N = 32768
     constexpr int GRP = G::E < 8 ? G::E : 8;
 #pragma unroll
     for (int r0 = 0; r0 < G::E; r0 += GRP) {
         double pv[GRP];
-        u64 dv[GRP];
+        u64 sv[GRP];
 #pragma unroll
-        for (int r = 0; r < GRP; ++r) { pv[r] = (pk + G::idxB(r0 + r, 0))[tB]; dv[r] = (dk + G::idxB(r0 + r, 0))[tB]; }
+        for (int r = 0; r < GRP; ++r) { pv[r] = (pk + G::idxB(r0 + r, 0))[tB]; sv[r] = (second + G::idxB(r0 + r, 0))[tB]; }
 #pragma unroll
-        for (int r = 0; r < GRP; ++r)
-            (res + G::idxB(r0 + r, 0))[tB] =
-                hxf::from_f64(hxf::hks_down_rs(hxf::to_f64(dv[r]), pv[r], v[r0 + r], rs.pm, rs.pm_p, rs.rinv, rs.rinv_p, m));
+        for (int r = 0; r < GRP; ++r) {
+            const double x = hxf::to_f64(sv[r]);
+            (res + G::idxB(r0 + r, 0))[tB] = hxf::from_f64(RS ? hxf::hks_down_rs(x, pv[r], v[r0 + r], dv.pm, dv.pm_p, dv.inv, dv.inv_p, m)
+                                                              : hxf::hks_down(x, pv[r], v[r0 + r], dv.inv, dv.inv_p, m));
+        }
     }
 }
 
@@ -299,8 +246,7 @@ static_assert(HKS_THREADS == HX_WW_THREADS, "hx_ww_grid(., ., ., HKS_LOG_PIECE) 
 // the data limbs i < l, fix_i added). Per coefficient the <= MAXS source words are loaded and y formed ONCE; every target limb reduces y
 // into its own range before the products (hks_conv_term). Moduli and weights of a target are wave-uniform: scalar loads.
 // HKS_CONV_RS is the mod-down of the rescaling calls: one more source per component, the row l - 1 of acc (limb l - 1, not contiguous
-// with the special rows), one target fewer, and the constants of R = P q_(l-1) (a.src / a.wt: the level's row of d_rs_src / d_rs_wt).
-enum HksConv : int { HKS_CONV_UP, HKS_CONV_DOWN, HKS_CONV_RS };
+// with the special rows), one target fewer. a.src / a.wt / a.div are the rows of the launch's conversion and divisor (hks_point_rows).
 template <HksConv MODE, int MAXS>
 __global__ __launch_bounds__(HKS_THREADS) void k_hks_conv(HksArgs a) {
     typedef double d2 __attribute__((ext_vector_type(2)));
@@ -347,7 +293,7 @@ __global__ __launch_bounds__(HKS_THREADS) void k_hks_conv(HksArgs a) {
                 acc0 = hxf::hks_conv_term(acc0, y[si][0], wt.w, wt.wp, m);
                 acc1 = hxf::hks_conv_term(acc1, y[si][1], wt.w, wt.wp, m);
             }
-        const double fix = RS ? a.rs[j].fix : DOWN ? a.down[j].fix : 0.0;
+        const double fix = DOWN ? a.div[j].fix : 0.0;
         const d2 o = {hxf::hks_conv_finish(acc0, fix, m), hxf::hks_conv_finish(acc1, fix, m)};
         double* dst = DOWN ? hks_w(a, b, g, jT, n) : a.ext + ((size_t(b) * a.dl + g) * a.T + jT) * n;
         *reinterpret_cast<d2*>(dst + c) = o;
@@ -356,87 +302,66 @@ __global__ __launch_bounds__(HKS_THREADS) void k_hks_conv(HksArgs a) {
 
 // step 3: acc[b][k][jT] = sum_d ext[b][d][jT] . key[d][k][limb of jT], k_ksf_mac's structure with dl terms: a lane keeps the 2 dl key
 // vectors of its two indices in registers and walks the batch, so the keys are read once per launch and ext / acc exactly once.
-template <int MAXD>
-__global__ __launch_bounds__(HKS_THREADS) void k_hks_mac(HksArgs a) {
-    typedef double d2 __attribute__((ext_vector_type(2)));
-    const u32 n = 1u << a.logn, pairs = n >> 1;
-    const u32 gid = blockIdx.x * blockDim.x + threadIdx.x;        // (row of T_l, pair)
-    const u32 jT = gid / pairs;
-    if (jT >= a.T) return;
-    const u32 c = (gid - jT * pairs) * 2;
-    const u32 j = hks_limb(a, jT);
-    const Mod m = a.mods[j].m;
-    d2 key[MAXD][2];
-#pragma unroll
-    for (int d = 0; d < MAXD; ++d)
-        if (d < (int)a.dl) {
-            key[d][0] = *reinterpret_cast<const d2*>(a.keys + ((size_t(d) * 2 + 0) * a.K + j) * n + c);
-            key[d][1] = *reinterpret_cast<const d2*>(a.keys + ((size_t(d) * 2 + 1) * a.K + j) * n + c);
-        }
-    for (u32 b = blockIdx.y; b < a.nb; b += gridDim.y) {
-        const double* ub = a.ext + (size_t(b) * a.dl * a.T + jT) * n + c;
-        d2 acc0 = {0.0, 0.0}, acc1 = {0.0, 0.0};
-#pragma unroll
-        for (int d = 0; d < MAXD; ++d)
-            if (d < (int)a.dl) {
-                const d2 u = *reinterpret_cast<const d2*>(ub + size_t(d) * a.T * n);
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    acc0[e] = hxf::hks_mac_term(acc0[e], u[e], key[d][0][e], m);
-                    acc1[e] = hxf::hks_mac_term(acc1[e], u[e], key[d][1][e], m);
-                }
-            }
-        *reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 0) * a.T + jT) * n + c) = acc0;
-        *reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 1) * a.T + jT) * n + c) = acc1;
-    }
-}
-
-// step 3 of the hoisted callers, one rotation: sum[b][k][jT] = sum_d sigma_g(ext[b][d][jT]) . key_r[d][k][limb of jT] -- k_hks_mac with ext
+// step 3 of the hoisted callers, one rotation: sum[b][k][jT] = sum_d sigma_g(ext[b][d][jT]) . key_r[d][k][limb of jT] -- the same with ext
 // gathered. ext lies at its logical index, so word j of sigma_g(ext) is word galois_src(j) of ext, no position map. pi_g maps every
 // aligned block of 2^k indices onto an aligned block of 2^k (keyswitch_f64.hip k_ksf_mac_galois); with k = 1: the sources of a lane's two
 // adjacent indices c, c + 1 are the two words of ONE aligned pair, s and s ^ 1 -- (2 brv(c + 1) + 1) g = (2 brv(c) + 1) g + n g, and
 // n g = n (mod 2n) for an odd g, which flips the top bit of (e - 1) / 2 and so the lowest bit of the source. The gather is therefore one
 // 16-byte load at s & ~1 and a swap when s is odd: keys, plaintext, acc AND ext stay 16-byte accesses, and a wave's 64 sources are the
 // 1 KiB of one aligned block of 128 indices, whole cache lines in another order. g = 1 is served too (s = c, no swap).
-// What becomes of the reduced sum (an hks_mac_term output, i.e. a reduce output: what lt_mac / lt_mac_acc take as `inner`) is MODE:
+// Where ext is read and what becomes of the reduced sum (an hks_mac_term output, i.e. a reduce output: what lt_mac / lt_mac_acc take
+// as `inner`) is MODE:
+//   HKS_MAC_PLAIN     the key switch: no galois_src, no swap, keys from a.keys, acc = sum
 //   HKS_MAC_STORE     hexl_hks_rotate_hoisted: acc = sum
 //   HKS_MAC_PT_FIRST  hexl_hks_linear_transform, a chunk's first rotation: acc = pt[limb of jT] . sum (hxf::lt_mac), acc is not read
 //   HKS_MAC_PT_ACC    ... its later rotations: acc = acc + pt . sum (hxf::lt_mac_acc), the old words requested in front of the gather
 // pt is [K][n] canonical words in the transforms' output order: the lane's pair is converted once (hxf::lt_pt) and serves every instance
 // it walks. acc never leaves the extended basis between rotations, so step 4 runs once for all of them.
 struct HksRot { const double* keys; const u64* pt; u32 g; };      // the rotation's object's keys [dnum][2][K][n]; pt: the plaintext modes
-enum HksMacMode : int { HKS_MAC_STORE, HKS_MAC_PT_FIRST, HKS_MAC_PT_ACC };
+enum HksMacMode : int { HKS_MAC_PLAIN, HKS_MAC_STORE, HKS_MAC_PT_FIRST, HKS_MAC_PT_ACC };
 
-template <int MAXD, HksMacMode MODE>
-__global__ __launch_bounds__(HKS_THREADS) void k_hks_mac_galois(HksArgs a, HksRot rot) {
+// ONE kernel template for both: ROT is empty for HKS_MAC_PLAIN -- the kernel's arguments are (HksArgs) alone, as the key switch's always
+// were -- and {HksRot} for the other modes, (HksArgs, HksRot). `(rot, ...)` is that one HksRot; it is named only where MODE has one.
+template <int MAXD, HksMacMode MODE, class... ROT>
+__global__ __launch_bounds__(HKS_THREADS) void k_hks_mac(HksArgs a, ROT... rot) {
+    static_assert(sizeof...(ROT) == (MODE == HKS_MAC_PLAIN ? 0 : 1), "HksRot goes with every mode but the plain one");
     typedef double d2 __attribute__((ext_vector_type(2)));
     typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
+    constexpr bool PT = MODE == HKS_MAC_PT_FIRST || MODE == HKS_MAC_PT_ACC;
     const u32 n = 1u << a.logn, pairs = n >> 1;
     const u32 gid = blockIdx.x * blockDim.x + threadIdx.x;        // (row of T_l, pair)
     const u32 jT = gid / pairs;
     if (jT >= a.T) return;
     const u32 c = (gid - jT * pairs) * 2;
-    const u32 s = galois_src(c, a.logn, rot.g);                   // the source of c; that of c + 1 is s ^ 1
-    const u32 sp = s & ~1u;
-    const bool swap = s & 1u;
+    u32 sp = c;                                                   // the aligned pair that holds the sources of c and c + 1
+    bool swap = false;
+    if constexpr (MODE != HKS_MAC_PLAIN) {
+        const u32 s = galois_src(c, a.logn, (rot, ...).g);        // the source of c; that of c + 1 is s ^ 1
+        sp = s & ~1u;
+        swap = s & 1u;
+    }
     const u32 j = hks_limb(a, jT);
     const Mod m = a.mods[j].m;
     d2 w = {0.0, 0.0};
-    if constexpr (MODE != HKS_MAC_STORE) {
-        const u2 t = *reinterpret_cast<const u2*>(rot.pt + size_t(j) * n + c);
+    if constexpr (PT) {
+        const u2 t = *reinterpret_cast<const u2*>((rot, ...).pt + size_t(j) * n + c);
         w.x = hxf::lt_pt(hxf::to_f64(t.x), m); w.y = hxf::lt_pt(hxf::to_f64(t.y), m);
     }
     d2 key[MAXD][2];
 #pragma unroll
     for (int d = 0; d < MAXD; ++d)
         if (d < (int)a.dl) {
-            key[d][0] = *reinterpret_cast<const d2*>(rot.keys + ((size_t(d) * 2 + 0) * a.K + j) * n + c);
-            key[d][1] = *reinterpret_cast<const d2*>(rot.keys + ((size_t(d) * 2 + 1) * a.K + j) * n + c);
+            const double* keys;
+            if constexpr (MODE == HKS_MAC_PLAIN) keys = a.keys; else keys = (rot, ...).keys;
+            key[d][0] = *reinterpret_cast<const d2*>(keys + ((size_t(d) * 2 + 0) * a.K + j) * n + c);
+            key[d][1] = *reinterpret_cast<const d2*>(keys + ((size_t(d) * 2 + 1) * a.K + j) * n + c);
         }
     for (u32 b = blockIdx.y; b < a.nb; b += gridDim.y) {
         const double* ub = a.ext + (size_t(b) * a.dl * a.T + jT) * n + sp;
-        d2* p0 = reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 0) * a.T + jT) * n + c);
-        d2* p1 = reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 1) * a.T + jT) * n + c);
+        // acc of component k. The plain mode forms each address at its store, the others both in front of the gather, where the
+        // PT_ACC loads need them: the order each mode's instruction stream has always had
+        d2* p0 = MODE == HKS_MAC_PLAIN ? nullptr : reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 0) * a.T + jT) * n + c);
+        d2* p1 = MODE == HKS_MAC_PLAIN ? nullptr : reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 1) * a.T + jT) * n + c);
         d2 prev0 = {0.0, 0.0}, prev1 = {0.0, 0.0};
         if constexpr (MODE == HKS_MAC_PT_ACC) { prev0 = *p0; prev1 = *p1; }
         d2 acc0 = {0.0, 0.0}, acc1 = {0.0, 0.0};
@@ -451,25 +376,27 @@ __global__ __launch_bounds__(HKS_THREADS) void k_hks_mac_galois(HksArgs a, HksRo
                     acc1[e] = hxf::hks_mac_term(acc1[e], u[e], key[d][1][e], m);
                 }
             }
-        if constexpr (MODE != HKS_MAC_STORE) {
+        if constexpr (PT) {
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 acc0[e] = MODE == HKS_MAC_PT_FIRST ? hxf::lt_mac(acc0[e], w[e], m) : hxf::lt_mac_acc(acc0[e], w[e], prev0[e], m);
                 acc1[e] = MODE == HKS_MAC_PT_FIRST ? hxf::lt_mac(acc1[e], w[e], m) : hxf::lt_mac_acc(acc1[e], w[e], prev1[e], m);
             }
         }
+        if constexpr (MODE == HKS_MAC_PLAIN) p0 = reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 0) * a.T + jT) * n + c);
         *p0 = acc0;
+        if constexpr (MODE == HKS_MAC_PLAIN) p1 = reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 1) * a.T + jT) * n + c);
         *p1 = acc1;
     }
 }
 
 // step 3 of one giant step of hexl_hks_linear_transform_bsgs, k_lt_bsgs_sum (keyswitch_f64.hip) on this layout:
 //     acc[b][k][jT] = sum_r pt_r[limb of jT] . B_r[b][k][jT]
-// B_r is what k_hks_mac_galois<., HKS_MAC_STORE> stored for the baby step of term r: the inner sum of the plaintext modes, computed once
+// B_r is what k_hks_mac<., HKS_MAC_STORE> stored for the baby step of term r: the inner sum of the plaintext modes, computed once
 // per chunk instead of once per giant step. No keys, no gather, no position map: a stored vector lies at its logical index like every
 // hybrid intermediate, so a lane owns two adjacent indices of one row of T_l as in k_hks_mac and every access is 16 bytes. It walks the
 // row's terms of the per-call table (wave-uniform: scalar loads), keeps both accumulators in registers across them and writes acc ONCE --
-// where k_hks_mac_galois<., HKS_MAC_PT_ACC> reads and writes acc per term. The plaintext is indexed by the PHYSICAL limb (pt is [K][n]),
+// where k_hks_mac<., HKS_MAC_PT_ACC> reads and writes acc per term. The plaintext is indexed by the PHYSICAL limb (pt is [K][n]),
 // the stored vectors and acc by the row jT of T_l. The scalar chain is that of the plaintext modes unchanged and in the same order --
 // lt_pt, lt_mac for the first term, lt_mac_acc after it -- on the same inner operand (an hks_mac_term output, stored exactly), so acc
 // holds the very doubles hexl_hks_linear_transform's multiply-accumulates leave for that row.
@@ -576,8 +503,15 @@ static u32 hks_piece_grid(const hexl_ks_plan* p, size_t rows) { return (u32)(row
 // them back to back; the hoisted callers run `up` once per chunk and the other two per rotation, or `down` once (hks_hoist_*).
 template <int LOGN, int LOGE, int LAZY>
 static int hks_optin(hexl_hks* h) {
-    return hx_lds_optin<k_hks_intt<LOGN, LOGE, LAZY>, k_hks_fwd<LOGN, LOGE, LAZY>, k_hks_intt_sp<LOGN, LOGE, LAZY>,
-                        k_hks_down<LOGN, LOGE, LAZY>>(h->plan->ctx->device, Geom<LOGN, LOGE>::LDS_USED);
+    return hx_lds_optin<k_hks_intt<LOGN, LOGE, LAZY>, k_hks_fwd<LOGN, LOGE, LAZY>, k_hks_down_intt<LOGN, LOGE, LAZY, false>,
+                        k_hks_down<LOGN, LOGE, LAZY, false>, k_hks_down_intt<LOGN, LOGE, LAZY, true>, k_hks_down<LOGN, LOGE, LAZY, true>>(
+        h->plan->ctx->device, Geom<LOGN, LOGE>::LDS_USED);
+}
+// the rows of the constants a launch reads: the conversion `mode` at level l, and the divisor of that mod-down
+static void hks_point_rows(const hexl_hks* h, HksConv mode, u32 l, HksArgs& a) {
+    a.src = h->d_src + hks_conv_row(mode, l) * HKS_MAX_LIMBS;
+    a.wt = h->d_wt + hks_conv_row(mode, l) * HKS_MAX_LIMBS * HKS_MAX_LIMBS;
+    a.div = h->d_div + hks_div_row(mode, l) * HKS_MAX_LIMBS;
 }
 
 template <int LOGN, int LOGE, int LAZY>
@@ -600,7 +534,7 @@ static int hks_stage_up(hexl_hks* h, const HksArgs& a) {
 static dim3 hks_mac_grid(const HksArgs& a) { return dim3(a.T * ((1u << a.logn) / 2) / HKS_THREADS, a.nb < 8 ? a.nb : 8); }
 static int hks_stage_mac(hexl_hks* h, const HksArgs& a) {
     hks_with_max(a.dl, [&](auto M) {
-        hipLaunchKernelGGL((k_hks_mac<decltype(M)::value>), hks_mac_grid(a), dim3(HKS_THREADS), 0, h->plan->ctx->stream, a);
+        hipLaunchKernelGGL((k_hks_mac<decltype(M)::value, HKS_MAC_PLAIN>), hks_mac_grid(a), dim3(HKS_THREADS), 0, h->plan->ctx->stream, a);
     });
     return (int)hipGetLastError();
 }
@@ -609,9 +543,9 @@ static int hks_stage_mac_galois(hexl_hks* h, const HksArgs& a, const HksRot& rot
     const dim3 grid = hks_mac_grid(a), ww(HKS_THREADS);
     hks_with_max(a.dl, [&](auto M) {
         constexpr int D = decltype(M)::value;
-        if (mode == HKS_MAC_STORE)         hipLaunchKernelGGL((k_hks_mac_galois<D, HKS_MAC_STORE>), grid, ww, 0, st, a, rot);
-        else if (mode == HKS_MAC_PT_FIRST) hipLaunchKernelGGL((k_hks_mac_galois<D, HKS_MAC_PT_FIRST>), grid, ww, 0, st, a, rot);
-        else                               hipLaunchKernelGGL((k_hks_mac_galois<D, HKS_MAC_PT_ACC>), grid, ww, 0, st, a, rot);
+        if (mode == HKS_MAC_STORE)         hipLaunchKernelGGL((k_hks_mac<D, HKS_MAC_STORE, HksRot>), grid, ww, 0, st, a, rot);
+        else if (mode == HKS_MAC_PT_FIRST) hipLaunchKernelGGL((k_hks_mac<D, HKS_MAC_PT_FIRST, HksRot>), grid, ww, 0, st, a, rot);
+        else                               hipLaunchKernelGGL((k_hks_mac<D, HKS_MAC_PT_ACC, HksRot>), grid, ww, 0, st, a, rot);
     });
     return (int)hipGetLastError();
 }
@@ -621,42 +555,24 @@ static int hks_stage_bsgs_sum(hexl_hks* h, const HksArgs& a, const HksBsgsTerm* 
     return (int)hipGetLastError();
 }
 
-template <int LOGN, int LOGE, int LAZY>
+// step 4, or step 4' of the rescaling calls (RS: a.d01 and a.result set by the caller; l >= 2): sources S, and the limb l - 1 with RS;
+// targets the data limbs, all but the limb l - 1 with RS
+template <int LOGN, int LOGE, int LAZY, bool RS>
 static int hks_stage_down(hexl_hks* h, const HksArgs& a) {
     using G = Geom<LOGN, LOGE>;
+    constexpr HksConv MODE = RS ? HKS_CONV_RS : HKS_CONV_DOWN;
     hexl_ks_plan* p = h->plan;
     if (int rc = hks_optin<LOGN, LOGE, LAZY>(h)) return rc;
     hipStream_t st = p->ctx->stream;
     const dim3 wg(G::T), ww(HKS_THREADS);
-    const u32 nb = a.nb, np = a.K - a.L;
-    hipLaunchKernelGGL((k_hks_intt_sp<LOGN, LOGE, LAZY>), dim3(np * 2 * nb), wg, G::LDS_USED, st, a);
+    const u32 nb = a.nb, nsrc = a.K - a.L + RS, ntgt = a.l - RS;
     HksArgs dn = a;
-    dn.src = h->d_src + size_t(HKS_DOWN_ROW) * HKS_MAX_LIMBS;
-    dn.wt = h->d_wt + size_t(HKS_DOWN_ROW) * HKS_MAX_LIMBS * HKS_MAX_LIMBS;
-    hks_with_max(np, [&](auto M) {
-        hipLaunchKernelGGL((k_hks_conv<HKS_CONV_DOWN, decltype(M)::value>), dim3(hks_piece_grid(p, size_t(nb) * 2)), ww, 0, st, dn);
-    });
-    hipLaunchKernelGGL((k_hks_down<LOGN, LOGE, LAZY>), dim3(a.l * 2 * nb), wg, G::LDS_USED, st, a);
-    return (int)hipGetLastError();
-}
-
-// step 4' in place of step 4 (a.rs, a.d01 and a.result set by the caller; l >= 2)
-template <int LOGN, int LOGE, int LAZY>
-static int hks_stage_down_rs(hexl_hks* h, const HksArgs& a) {
-    using G = Geom<LOGN, LOGE>;
-    hexl_ks_plan* p = h->plan;
-    if (int rc = hx_lds_optin<k_hks_rs_intt<LOGN, LOGE, LAZY>, k_hks_rs_down<LOGN, LOGE, LAZY>>(p->ctx->device, G::LDS_USED)) return rc;
-    hipStream_t st = p->ctx->stream;
-    const dim3 wg(G::T), ww(HKS_THREADS);
-    const u32 nb = a.nb, nsrc = a.K - a.L + 1;
-    hipLaunchKernelGGL((k_hks_rs_intt<LOGN, LOGE, LAZY>), dim3(nsrc * 2 * nb), wg, G::LDS_USED, st, a);
-    HksArgs dn = a;
-    dn.src = h->d_rs_src + size_t(a.l - 1) * HKS_MAX_LIMBS;
-    dn.wt = h->d_rs_wt + size_t(a.l - 1) * HKS_MAX_LIMBS * HKS_MAX_LIMBS;
+    hks_point_rows(h, MODE, a.l, dn);
+    hipLaunchKernelGGL((k_hks_down_intt<LOGN, LOGE, LAZY, RS>), dim3(nsrc * 2 * nb), wg, G::LDS_USED, st, dn);
     hks_with_max(nsrc, [&](auto M) {
-        hipLaunchKernelGGL((k_hks_conv<HKS_CONV_RS, decltype(M)::value>), dim3(hks_piece_grid(p, size_t(nb) * 2)), ww, 0, st, dn);
+        hipLaunchKernelGGL((k_hks_conv<MODE, decltype(M)::value>), dim3(hks_piece_grid(p, size_t(nb) * 2)), ww, 0, st, dn);
     });
-    hipLaunchKernelGGL((k_hks_rs_down<LOGN, LOGE, LAZY>), dim3((a.l - 1) * 2 * nb), wg, G::LDS_USED, st, a);
+    hipLaunchKernelGGL((k_hks_down<LOGN, LOGE, LAZY, RS>), dim3(ntgt * 2 * nb), wg, G::LDS_USED, st, dn);
     return (int)hipGetLastError();
 }
 
@@ -664,29 +580,38 @@ template <int LOGN, int LOGE, int LAZY>
 static int hks_run_chunk(hexl_hks* h, const HksArgs& a) {
     if (int rc = hks_stage_up<LOGN, LOGE, LAZY>(h, a)) return rc;
     if (int rc = hks_stage_mac(h, a)) return rc;
-    return a.d01 ? hks_stage_down_rs<LOGN, LOGE, LAZY>(h, a) : hks_stage_down<LOGN, LOGE, LAZY>(h, a);
+    return a.d01 ? hks_stage_down<LOGN, LOGE, LAZY, true>(h, a) : hks_stage_down<LOGN, LOGE, LAZY, false>(h, a);
 }
 
 static size_t hks_chunk_of(const hexl_hks* h, size_t batch) { return hx_ks_chunk_of(h->plan, batch); }
-static size_t hks_words_per_instance(const hexl_hks* h) {         // in units of n 64-bit words, at the full level
-    return size_t(h->plan->L) + size_t(h->dnum) * h->plan->K + 2 * size_t(h->plan->K);
+// THE scratch account: rows of n 64-bit words per instance of a chunk, at the full level, buffer by buffer. Every reserve and every
+// hexl_hks_*_scratch_bytes reads it.
+struct HksRows {
+    size_t coef, ext, acc;            // the key switch: L, dnum K, 2 K
+    size_t w1;                        // the hoisted callers: + L
+    size_t t;                         // hexl_hks_linear_transform_bsgs: + 2 L beside w1
+    size_t slice, d01;                // the slice of rotate / relinearize / the tensor calls: L; the rescaling tensor call: + 2 L beside it
+    size_t ks() const { return coef + ext + acc; }
+};
+static HksRows hks_rows(const hexl_hks* h) {
+    const size_t L = h->plan->L, K = h->plan->K;
+    return HksRows{L, size_t(h->dnum) * K, 2 * K, L, 2 * L, L, 2 * L};
 }
+static size_t hks_row_bytes(const hexl_hks* h) { return h->plan->n * sizeof(u64); }
 
 // the scratch of chunks of `chunk` instances and a chunk's kernel arguments at level l, all but the per-chunk pointers and nb
 static int hks_reserve(hexl_hks* h, size_t chunk) {
-    const size_t n = h->plan->n, L = h->plan->L, K = h->plan->K;
-    if (int rc = h->d_coef.reserve(chunk * L * n)) return rc;
-    if (int rc = h->d_ext.reserve(chunk * h->dnum * K * n)) return rc;
-    return h->d_acc.reserve(chunk * 2 * K * n);
+    const size_t n = h->plan->n;
+    const HksRows r = hks_rows(h);
+    if (int rc = h->d_coef.reserve(chunk * r.coef * n)) return rc;
+    if (int rc = h->d_ext.reserve(chunk * r.ext * n)) return rc;
+    return h->d_acc.reserve(chunk * r.acc * n);
 }
 static HksArgs hks_args(const hexl_hks* h, u32 l) {
     const hexl_ks_plan* p = h->plan;
     HksArgs a{};
     a.mods = p->d_mods_f64; a.tables = p->d_tables_f64;
-    a.src = h->d_src + size_t(l - 1) * HKS_MAX_LIMBS;
-    a.wt = h->d_wt + size_t(l - 1) * HKS_MAX_LIMBS * HKS_MAX_LIMBS;
-    a.down = h->d_down;
-    a.rs = h->d_rs + size_t(l - 1) * HKS_MAX_LIMBS;
+    hks_point_rows(h, HKS_CONV_UP, l, a);
     a.keys = h->d_keys;
     a.coef = h->d_coef; a.ext = h->d_ext; a.acc = h->d_acc;
     a.L = p->L; a.K = p->K; a.l = l; a.T = l + h->np;
@@ -697,29 +622,40 @@ static HksArgs hks_args(const hexl_hks* h, u32 l) {
     return a;
 }
 
-// the key switch of `batch` instances at level l: d_result[batch][2][l][n] += KS(d_t[batch][l][n]), chunk by chunk on the context's stream
-static int hks_launch(hexl_hks* h, u64* d_result, const u64* d_t, size_t batch, u32 l) {
+// The key switch of `batch` instances at level l, chunk by chunk on the context's stream. feed(b0, nb, a) points the chunk's arguments:
+// a.t / a.tstride at its input and a.result at its output -- [nb][2][l][n], ADDED into -- and, for the rescaling mod-down, a.d01 /
+// a.d01_stride at its (d0, d1), with a.result [nb][2][l - 1][n] WRITTEN; it launches what fills them.
+template <class F>
+static int hks_launch(hexl_hks* h, size_t batch, u32 l, F feed) {
     hexl_ks_plan* p = h->plan;
-    const size_t n = p->n;
     const size_t chunk = hks_chunk_of(h, batch);
     if (int rc = hks_reserve(h, chunk)) return rc;
     HksArgs a = hks_args(h, l);
     const int lazy = hks_level_tier(p, l);
     return hx_for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
-        a.t = d_t + b0 * l * n;
-        a.result = d_result + b0 * 2 * l * n;
         a.nb = (u32)nb;
+        if (int rc = feed(b0, nb, a)) return rc;
         return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return hks_run_chunk<N, E, Z>(h, a); });
     });
 }
+// d_result[batch][2][l][n] += KS(d_t[batch][l][n]), the caller's arrays
+static int hks_keyswitch(hexl_hks* h, u64* d_result, const u64* d_t, size_t batch, u32 l) {
+    const size_t n = h->plan->n;
+    return hks_launch(h, batch, l, [&](size_t b0, size_t, HksArgs& a) {
+        a.t = d_t + b0 * l * n;
+        a.result = d_result + b0 * 2 * l * n;
+        return 0;
+    });
+}
 
-// conversion constants for every level, exact integer work: per (level, digit, limb) the two weights, and the mod-down's
+// conversion constants for every level, exact integer work: per (conversion row, source limb, target limb) the two weights, and per
+// (divisor row, limb) the mod-down's
 static int hks_constants(hexl_hks* h) {
     const hexl_ks_plan* p = h->plan;
     const u32 L = p->L, K = p->K, alpha = h->alpha;
     const std::vector<u64>& q = p->moduli;
-    std::vector<HksSrc> src(size_t(HKS_DOWN_ROW + 1) * HKS_MAX_LIMBS, HksSrc{0.0, 0.0});
-    std::vector<HksWt> wt(size_t(HKS_DOWN_ROW + 1) * HKS_MAX_LIMBS * HKS_MAX_LIMBS, HksWt{0.0, 0.0});
+    std::vector<HksSrc> src(size_t(HKS_CONV_ROWS) * HKS_MAX_LIMBS, HksSrc{0.0, 0.0});
+    std::vector<HksWt> wt(size_t(HKS_CONV_ROWS) * HKS_MAX_LIMBS * HKS_MAX_LIMBS, HksWt{0.0, 0.0});
     // the limbs of `sources` convert into the targets of `targets` (a target that is a source is skipped): (D / q_i)^-1 mod q_i and
     // (D / q_i) mod q_j, D the sources' product
     auto fill = [&](std::vector<HksSrc>& src, std::vector<HksWt>& wt, u32 row, const std::vector<u32>& sources, const std::vector<u32>& targets) {
@@ -749,60 +685,45 @@ static int hks_constants(hexl_hks* h) {
         for (u32 i = lo; i < hi; ++i) v.push_back(i);
         return v;
     };
+    fill(src, wt, hks_conv_row(HKS_CONV_DOWN, 0), limbs(L, K), limbs(0, L));
     for (u32 l = 1; l <= L; ++l) {
-        std::vector<u32> basis;
-        for (u32 j = 0; j < l; ++j) basis.push_back(j);
-        for (u32 s = L; s < K; ++s) basis.push_back(s);
-        for (u32 lo = 0; lo < l; lo += alpha) fill(src, wt, l - 1, limbs(lo, lo + alpha < l ? lo + alpha : l), basis);
+        std::vector<u32> basis = limbs(0, l), B = limbs(L, K);
+        basis.insert(basis.end(), B.begin(), B.end());
+        for (u32 lo = 0; lo < l; lo += alpha) fill(src, wt, hks_conv_row(HKS_CONV_UP, l), limbs(lo, lo + alpha < l ? lo + alpha : l), basis);
+        if (l < 2) continue;
+        B.push_back(l - 1);                                       // the rescaling mod-down: sources S + {l - 1}, targets i < l - 1
+        fill(src, wt, hks_conv_row(HKS_CONV_RS, l), B, limbs(0, l - 1));
     }
-    fill(src, wt, HKS_DOWN_ROW, limbs(L, K), limbs(0, L));
-    std::vector<HksDown> down(K, HksDown{0.0, 0.0, 0.0, 0.0});
+    // Per limb P mod q_i once, and from it every divisor row: row 0 is Q = P (sources S, targets every data limb), row l - 1 is
+    // Q = R = P q_(l-1) of level l >= 2 (sources S and the limb l - 1, targets i < l - 1; the limbs l ... L - 1 are not in its basis).
+    std::vector<HksDiv> div(size_t(HKS_MAX_LIMBS) * HKS_MAX_LIMBS, HksDiv{0.0, 0.0, 0.0, 0.0, 0.0, 0.0});
     for (u32 i = 0; i < K; ++i) {
-        u64 P = 1 % q[i];
-        for (u32 s = L; s < K; ++s) P = hxnt::mulmod(P, q[s] % q[i], q[i]);
-        // floor(P / 2) = (P - 1) / 2 for an odd P: ((P mod q) - 1) (q + 1) / 2 mod q
-        const u64 half = hxnt::mulmod((P + q[i] - 1) % q[i], (q[i] + 1) / 2, q[i]);
-        if (i < L) {
-            const double pinv = hx_centre(hxnt::invmod(P, q[i]), q[i]);
-            down[i] = HksDown{pinv, pinv / (double)q[i], (double)(q[i] - half), 0.0};
-        } else {
-            down[i].half = (double)half;
-        }
-    }
-    // the rescaling mod-down of every level l >= 2 (row l - 1): R = P q_(l-1), sources B = S + {l - 1}, targets i < l - 1
-    std::vector<HksSrc> rs_src(size_t(HKS_MAX_LIMBS) * HKS_MAX_LIMBS, HksSrc{0.0, 0.0});
-    std::vector<HksWt> rs_wt(size_t(HKS_MAX_LIMBS) * HKS_MAX_LIMBS * HKS_MAX_LIMBS, HksWt{0.0, 0.0});
-    std::vector<HksRs> rs(size_t(HKS_MAX_LIMBS) * HKS_MAX_LIMBS, HksRs{0.0, 0.0, 0.0, 0.0, 0.0, 0.0});
-    for (u32 l = 2; l <= L; ++l) {
-        std::vector<u32> B = limbs(L, K);
-        B.push_back(l - 1);
-        fill(rs_src, rs_wt, l - 1, B, limbs(0, l - 1));
-        for (u32 i = 0; i < K; ++i) {
-            if (i >= l && i < L) continue;
-            u64 P = 1 % q[i];
-            for (u32 s = L; s < K; ++s) P = hxnt::mulmod(P, q[s] % q[i], q[i]);
-            const u64 R = hxnt::mulmod(P, q[l - 1] % q[i], q[i]);
-            // floor(R / 2) = (R - 1) / 2 for the odd R, as floor(P / 2) above (R = 0 modulo a source limb)
-            const u64 half = hxnt::mulmod((R + q[i] - 1) % q[i], (q[i] + 1) / 2, q[i]);
-            HksRs& c = rs[size_t(l - 1) * HKS_MAX_LIMBS + i];
-            c.half = (double)half;
-            if (i < l) {
-                c.pm = hx_centre(P, q[i]);
-                c.pm_p = c.pm / (double)q[i];
+        const u64 qi = q[i];
+        u64 P = 1 % qi;
+        for (u32 s = L; s < K; ++s) P = hxnt::mulmod(P, q[s] % qi, qi);
+        for (u32 l = 1; l <= L; ++l) {
+            const bool rs = l >= 2;
+            if (rs && i >= l && i < L) continue;
+            const u64 Q = rs ? hxnt::mulmod(P, q[l - 1] % qi, qi) : P;
+            // floor(Q / 2) = (Q - 1) / 2 for the odd Q: ((Q mod q) - 1) (q + 1) / 2 mod q (Q = 0 modulo a source limb)
+            const u64 half = hxnt::mulmod((Q + qi - 1) % qi, (qi + 1) / 2, qi);
+            HksDiv& c = div[hks_div_row(rs ? HKS_CONV_RS : HKS_CONV_DOWN, l) * HKS_MAX_LIMBS + i];
+            if (i >= L || (rs && i == l - 1)) {
+                c.half = (double)half;
+            } else {
+                c.inv = hx_centre(hxnt::invmod(Q, qi), qi);
+                c.inv_p = c.inv / (double)qi;
+                c.fix = (double)(qi - half);
             }
-            if (i < l - 1) {
-                c.rinv = hx_centre(hxnt::invmod(R, q[i]), q[i]);
-                c.rinv_p = c.rinv / (double)q[i];
-                c.fix = (double)(q[i] - half);
+            if (rs && i < l) {
+                c.pm = hx_centre(P, qi);
+                c.pm_p = c.pm / (double)qi;
             }
         }
     }
-    if (int rc = h->d_rs_src.upload_once(rs_src.data(), rs_src.size())) return rc;
-    if (int rc = h->d_rs_wt.upload_once(rs_wt.data(), rs_wt.size())) return rc;
-    if (int rc = h->d_rs.upload_once(rs.data(), rs.size())) return rc;
     if (int rc = h->d_src.upload_once(src.data(), src.size())) return rc;
     if (int rc = h->d_wt.upload_once(wt.data(), wt.size())) return rc;
-    return h->d_down.upload_once(down.data(), down.size());
+    return h->d_div.upload_once(div.data(), div.size());
 }
 
 // ---- entry points of include/hexl_mi355x.h ----
@@ -814,7 +735,7 @@ static bool hks_call_ok(const hexl_hks* h, size_t batch, u64 n_limbs, u64 comps,
     if (!hx_words_bytes(batch, comps, n_limbs, p->n, bytes)) return false;
     const size_t chunk = hks_chunk_of(h, batch);
     size_t scratch;
-    if (!hx_words_bytes(chunk, 1, hks_words_per_instance(h), p->n, &scratch)) return false;
+    if (!hx_words_bytes(chunk, 1, hks_rows(h).ks(), p->n, &scratch)) return false;
     // the largest grids of a chunk: one workgroup per (row of T_l, digit, instance), one per (instance, 3 l rows, piece)
     return hx_wg_grid_ok(chunk, u64(p->K) * h->dnum) && chunk <= HX_MAX_GRID / (size_t(3 * p->L) << (p->logn - HKS_LOG_PIECE));
 }
@@ -861,7 +782,7 @@ extern "C" int hexl_hks_keyswitch(hexl_hks* h, uint64_t* d_result, const uint64_
     if (!h->have_keys) return HEXL_E_NOKEYS;
     if (!batch) return 0;
     HX_CHECK(hipSetDevice(h->plan->ctx->device));
-    return hks_launch(h, d_result, d_t_target, batch, (u32)n_limbs);
+    return hks_keyswitch(h, d_result, d_t_target, batch, (u32)n_limbs);
 }
 
 // The slice loop of hexl_rotate / hexl_relinearize: fill(b0, nb, out, t) writes what the key switch adds into to `out` and its input to
@@ -870,11 +791,11 @@ template <class F>
 static int hks_slices(hexl_hks* h, u64* d_out, size_t batch, u32 l, F fill) {
     const size_t n = h->plan->n;
     const size_t slice = hks_chunk_of(h, batch);
-    if (int rc = h->d_slice.reserve(slice * h->plan->L * n)) return rc;
+    if (int rc = h->d_slice.reserve(slice * hks_rows(h).slice * n)) return rc;
     return hx_for_chunks(batch, slice, [&](size_t b0, size_t nb) {
         u64* out = d_out + b0 * 2 * l * n;
         if (int rc = fill(b0, nb, out, (u64*)h->d_slice)) return rc;
-        return hks_launch(h, out, h->d_slice, nb, l);
+        return hks_keyswitch(h, out, h->d_slice, nb, l);
     });
 }
 
@@ -914,7 +835,7 @@ extern "C" int hexl_hks_rotate(hexl_hks* h, uint64_t* d_out, const uint64_t* d_c
 
 extern "C" size_t hexl_hks_scratch_bytes(const hexl_hks* h, size_t batch) {
     if (!h) return 0;
-    return hks_chunk_of(h, batch) * hks_words_per_instance(h) * h->plan->n * sizeof(u64);
+    return hks_chunk_of(h, batch) * hks_rows(h).ks() * hks_row_bytes(h);
 }
 
 // ---- the hybrid multiply: the tensor sum, the key switch of its component 2 and -- the rescaling calls -- ONE mod-down
@@ -930,7 +851,7 @@ static bool hks_mul_ok(const hexl_hks* h, const u64* d_out, const u64* const* d_
     const hexl_ks_plan* p = h->plan;
     // the largest operand has K limbs: if that size fits, every other one does; the slice and d01 buffers; the tensor kernel's grid
     if (!hx_words_bytes(batch, 2, p->K, p->n, &bytes) || !hx_words_bytes(batch, 2, out_limbs, p->n, &out_bytes) ||
-        !hx_words_bytes(hks_chunk_of(h, batch), 3, p->L, p->n, &buffers) || !hx_ww_grid_ok(p, hks_chunk_of(h, batch), n_limbs) ||
+        !hx_words_bytes(hks_chunk_of(h, batch), 1, hks_rows(h).slice + hks_rows(h).d01, p->n, &buffers) || !hx_ww_grid_ok(p, hks_chunk_of(h, batch), n_limbs) ||
         !hx_wg_grid_ok(hks_chunk_of(h, batch), 2 * u64(p->K)))
         return false;
     return hx_tensor_operands(p, d_as, d_bs, in_limbs, n_terms, batch, n_limbs, d_out, out_bytes, s) == 0;
@@ -961,24 +882,6 @@ extern "C" int hexl_hks_multiply_sum_relinearize(hexl_hks* h, uint64_t* d_out, c
     return hks_slices(h, d_out, batch, (u32)n_limbs, [&](size_t b0, size_t nb, u64* out, u64* t) { return hks_mul_tensor(p, s, b0, nb, out, t); });
 }
 
-// The rescaling key switch of `batch` instances at level l >= 2, chunk by chunk on the context's stream: d_out[batch][2][l - 1][n] WRITTEN.
-// feed(b0, nb, a) points a.t / a.tstride at the chunk's d2 and a.d01 / a.d01_stride at its (d0, d1), launching what fills them.
-template <class F>
-static int hks_launch_rs(hexl_hks* h, u64* d_out, size_t batch, u32 l, F feed) {
-    hexl_ks_plan* p = h->plan;
-    const size_t n = p->n;
-    const size_t chunk = hks_chunk_of(h, batch);
-    if (int rc = hks_reserve(h, chunk)) return rc;
-    HksArgs a = hks_args(h, l);
-    const int lazy = hks_level_tier(p, l);
-    return hx_for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
-        a.result = d_out + b0 * 2 * (l - 1) * n;
-        a.nb = (u32)nb;
-        if (int rc = feed(b0, nb, a)) return rc;
-        return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return hks_run_chunk<N, E, Z>(h, a); });
-    });
-}
-
 extern "C" int hexl_hks_relinearize_rescale(hexl_hks* h, uint64_t* d_out, const uint64_t* d_ct3, size_t batch, uint64_t n_limbs) {
     size_t in_bytes;
     if (!d_out || !d_ct3 || n_limbs < 2 || !hks_call_ok(h, batch, n_limbs, 3, &in_bytes)) return HEXL_E_BADARG;
@@ -989,7 +892,8 @@ extern "C" int hexl_hks_relinearize_rescale(hexl_hks* h, uint64_t* d_out, const 
     HX_CHECK(hipSetDevice(h->plan->ctx->device));
     const size_t n = h->plan->n, l = n_limbs;
     // d2 and (d0, d1) are read where they lie: no split copy
-    return hks_launch_rs(h, d_out, batch, (u32)l, [&](size_t b0, size_t, HksArgs& a) {
+    return hks_launch(h, batch, (u32)l, [&](size_t b0, size_t, HksArgs& a) {
+        a.result = d_out + b0 * 2 * (l - 1) * n;
         a.d01 = d_ct3 + b0 * 3 * l * n;
         a.d01_stride = 3ull * l * n;
         a.t = a.d01 + 2 * l * n;
@@ -1007,10 +911,11 @@ extern "C" int hexl_hks_multiply_sum_rescale(hexl_hks* h, uint64_t* d_out, const
     hexl_ks_plan* p = h->plan;
     HX_CHECK(hipSetDevice(p->ctx->device));
     const size_t n = p->n, l = n_limbs, chunk = hks_chunk_of(h, batch);
-    if (int rc = h->d_slice.reserve(chunk * p->L * n)) return rc;
-    if (int rc = h->d_d01.reserve(chunk * 2 * p->L * n)) return rc;
+    if (int rc = h->d_slice.reserve(chunk * hks_rows(h).slice * n)) return rc;
+    if (int rc = h->d_d01.reserve(chunk * hks_rows(h).d01 * n)) return rc;
     // one lane: the next chunk's tensor kernel overwrites the two buffers behind this chunk's last kernel that reads them
-    return hks_launch_rs(h, d_out, batch, (u32)l, [&](size_t b0, size_t nb, HksArgs& a) {
+    return hks_launch(h, batch, (u32)l, [&](size_t b0, size_t nb, HksArgs& a) {
+        a.result = d_out + b0 * 2 * (l - 1) * n;
         a.d01 = h->d_d01;
         a.d01_stride = 2ull * l * n;
         a.t = h->d_slice;
@@ -1021,7 +926,8 @@ extern "C" int hexl_hks_multiply_sum_rescale(hexl_hks* h, uint64_t* d_out, const
 
 extern "C" size_t hexl_hks_mul_scratch_bytes(const hexl_hks* h, size_t batch) {
     if (!h) return 0;
-    return hexl_hks_scratch_bytes(h, batch) + hks_chunk_of(h, batch) * 3 * h->plan->L * h->plan->n * sizeof(u64);
+    const HksRows r = hks_rows(h);
+    return hks_chunk_of(h, batch) * (r.ks() + r.slice + r.d01) * hks_row_bytes(h);
 }
 
 // ---- the hoisted callers: many rotations of one ciphertext batch share steps 1-2 (hexl_hks_rotate_hoisted), and step 4 as well
@@ -1038,7 +944,7 @@ struct HksHoist {
     // hks[0]'s key switch scratch and w of component 1 in a buffer of its own: ext has to survive step 4 for the next rotation
     int reserve() {
         if (int rc = hks_reserve(h0, chunk)) return rc;
-        if (int rc = h0->d_w1.reserve(chunk * p->L * p->n)) return rc;
+        if (int rc = h0->d_w1.reserve(chunk * hks_rows(h0).w1 * p->n)) return rc;
         a.coef = h0->d_coef; a.ext = h0->d_ext; a.acc = h0->d_acc; a.w1 = h0->d_w1;
         a.tstride = 2 * a.l;
         return 0;
@@ -1060,24 +966,32 @@ struct HksHoist {
     // step 4 on acc, ADDED into d_out
     int down(u64* d_out) {
         a.result = d_out;
-        return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return hks_stage_down<N, E, Z>(h0, a); });
+        return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return hks_stage_down<N, E, Z, false>(h0, a); });
     }
 };
 
-// What the two hoisted entry points check alike, in the house order (everything here decides HEXL_E_BADARG): the objects share hks[0]'s
-// plan and alpha, the level, the Galois elements, sizes and grids. s: bytes of a batch of ciphertexts, of one plaintext [K][n], of the
-// rows of an identity plaintext that are read.
+// What the three hoisted entry points check alike (everything here decides HEXL_E_BADARG). hks_hoist_ok: plan, level, sizes and grids of
+// a run in h0's scratch. s: bytes of a batch of ciphertexts, of one plaintext [K][n], of the rows of an identity plaintext that are read.
+// hks_hoist_list_ok: the objects of one list share h0's plan and alpha, and the list's Galois elements. A NULL object passes: the BSGS
+// call allows one where it is unused, the other two have refused it before they come here. The BSGS call did not run hks_hoist_ok's
+// overflow check of the key switch's rows + w1 at the key switch's chunk before it shared this function; it is a new
+// refusal there, reachable only with scratch sizes near 2^64 bytes, and gives the HEXL_E_BADARG that call's own size check gives.
 struct HksHoistBytes { size_t ct, pt, id; };
-static bool hks_hoist_ok(hexl_hks* const* hks, const u64* galois_elts, size_t n_rot, size_t batch, u64 n_limbs, HksHoistBytes* s) {
-    const hexl_hks* h0 = hks[0];
+static bool hks_hoist_ok(const hexl_hks* h0, size_t batch, u64 n_limbs, HksHoistBytes* s) {
     if (!hks_call_ok(h0, batch, n_limbs, 2, &s->ct)) return false;
     const hexl_ks_plan* p = h0->plan;
-    size_t scratch;                                               // with w of component 1: L more rows per instance
-    if (!hx_words_bytes(hks_chunk_of(h0, batch), 1, hks_words_per_instance(h0) + p->L, p->n, &scratch)) return false;
+    const HksRows r = hks_rows(h0);
+    size_t scratch;                                               // with w of component 1
+    if (!hx_words_bytes(hks_chunk_of(h0, batch), 1, r.ks() + r.w1, p->n, &scratch)) return false;
     s->pt = size_t(p->K) * p->n * sizeof(u64);
     s->id = size_t(n_limbs) * p->n * sizeof(u64);
-    for (size_t r = 0; r < n_rot; ++r)
-        if (hks[r]->plan != p || hks[r]->alpha != h0->alpha || !hks_galois_elt_ok(galois_elts[r], p->n)) return false;
+    return true;
+}
+static bool hks_hoist_list_ok(const hexl_hks* h0, hexl_hks* const* hks, const u64* galois_elts, size_t count) {
+    for (size_t r = 0; r < count; ++r) {
+        if (hks[r] && (hks[r]->plan != h0->plan || hks[r]->alpha != h0->alpha)) return false;
+        if (!hks_galois_elt_ok(galois_elts[r], h0->plan->n)) return false;
+    }
     return true;
 }
 
@@ -1088,7 +1002,7 @@ extern "C" int hexl_hks_rotate_hoisted(hexl_hks* const* hks, const uint64_t* gal
     for (size_t r = 0; r < n_rot; ++r)
         if (!hks[r] || !d_outs[r]) return HEXL_E_BADARG;
     HksHoistBytes s;
-    if (!hks_hoist_ok(hks, galois_elts, n_rot, batch, n_limbs, &s)) return HEXL_E_BADARG;
+    if (!hks_hoist_ok(hks[0], batch, n_limbs, &s) || !hks_hoist_list_ok(hks[0], hks, galois_elts, n_rot)) return HEXL_E_BADARG;
     for (size_t r = 0; r < n_rot; ++r) {
         if (hx_ranges_overlap(d_outs[r], s.ct, d_ct, s.ct)) return HEXL_E_BADARG;
         for (size_t q = 0; q < r; ++q)
@@ -1124,7 +1038,7 @@ extern "C" int hexl_hks_linear_transform(hexl_hks* const* hks, const uint64_t* g
     for (size_t r = 0; r < n_rot; ++r)
         if (!hks[r] || !d_pts[r]) return HEXL_E_BADARG;
     HksHoistBytes s;
-    if (!hks_hoist_ok(hks, galois_elts, n_rot, batch, n_limbs, &s)) return HEXL_E_BADARG;
+    if (!hks_hoist_ok(hks[0], batch, n_limbs, &s) || !hks_hoist_list_ok(hks[0], hks, galois_elts, n_rot)) return HEXL_E_BADARG;
     if (hx_ranges_overlap(d_out, s.ct, d_ct, s.ct)) return HEXL_E_BADARG;
     if (d_pt_identity && hx_ranges_overlap(d_out, s.ct, d_pt_identity, s.id)) return HEXL_E_BADARG;
     for (size_t r = 0; r < n_rot; ++r)
@@ -1157,13 +1071,14 @@ extern "C" int hexl_hks_linear_transform(hexl_hks* const* hks, const uint64_t* g
 
 extern "C" size_t hexl_hks_hoisted_scratch_bytes(const hexl_hks* h, size_t batch) {
     if (!h) return 0;
-    return hks_chunk_of(h, batch) * (hks_words_per_instance(h) + h->plan->L) * h->plan->n * sizeof(u64);
+    const HksRows r = hks_rows(h);
+    return hks_chunk_of(h, batch) * (r.ks() + r.w1) * hks_row_bytes(h);
 }
 
 // ---- baby-step/giant-step linear transform on the hybrid gadget (hexl_hks_linear_transform_bsgs):
 //      out = sum_j Rot_{G_j}( sum_i pt_{j,i} . Rot_{g_i}(ct) + pt_id_j . ct ),  hx_launch_linear_transform_bsgs (keyswitch_f64.hip) stage by
 // stage on the hybrid stages. Per chunk, in h0's scratch (h0: the first non-NULL object, baby objects first):
-//   the mod-up of c1 once; one k_hks_mac_galois<., STORE> per baby step that some row uses, its sums pointed at that step's slice of the
+//   the mod-up of c1 once; one k_hks_mac<., STORE> per baby step that some row uses, its sums pointed at that step's slice of the
 //   baby store (coef and ext are free after the last of them);
 //   per giant step j: the key-free part of row j into t_j (hx_launch_galois_c0_pt), the weighted sum of the stored products into acc
 //   (k_hks_bsgs_sum) and the mod-down ONCE, added into t_j -- hexl_hks_linear_transform's words for row j; then t_j rotated by G_j as
@@ -1185,10 +1100,10 @@ static size_t hks_bsgs_chunk(const hexl_hks* h, size_t n_baby, size_t batch) {
 
 extern "C" size_t hexl_hks_bsgs_scratch_bytes(const hexl_hks* h, size_t n_baby, size_t batch) {
     if (!h) return 0;
-    const hexl_ks_plan* p = h->plan;
     const size_t chunk = hks_bsgs_chunk(h, n_baby, batch);
     // per instance: the hoisted callers' scratch and t_j
-    const size_t fixed = (hks_words_per_instance(h) + p->L) * p->n * sizeof(u64) + 2 * size_t(p->L) * p->n * sizeof(u64);
+    const HksRows r = hks_rows(h);
+    const size_t fixed = (r.ks() + r.w1 + r.t) * hks_row_bytes(h);
     if (chunk && (fixed > SIZE_MAX / chunk || n_baby > (SIZE_MAX / chunk - fixed) / hks_bsgs_slice_bytes(h))) return SIZE_MAX;
     return chunk * (n_baby * hks_bsgs_slice_bytes(h) + fixed);
 }
@@ -1204,32 +1119,23 @@ extern "C" int hexl_hks_linear_transform_bsgs(hexl_hks* const* baby_hks, const u
     for (size_t i = 0; i < n_baby && !h0; ++i) h0 = baby_hks[i];
     for (size_t j = 0; j < n_giant && !h0; ++j) h0 = giant_hks[j];
     if (!h0) return HEXL_E_BADARG;
-    // in the order of the header: the rows, the objects against the first one, the level, the elements, the overlaps, the sizes
-    auto matches = [&](const hexl_hks* h) { return !h || (h->plan == h0->plan && h->alpha == h0->alpha); };
+    // the rows and the objects a term needs, then what the hoisted callers check too (at the key switch's chunk, which this call's never
+    // exceeds), then the overlaps and the sizes of the baby store
     for (size_t j = 0; j < n_giant; ++j) {
         bool any = d_pt_identity && d_pt_identity[j];
         for (size_t i = 0; i < n_baby && !any; ++i) any = d_pts[j * n_baby + i] != nullptr;
         if (!any) return HEXL_E_BADARG;                             // a giant row with no term at all
     }
-    for (size_t i = 0; i < n_baby; ++i)
-        if (!matches(baby_hks[i])) return HEXL_E_BADARG;
-    for (size_t j = 0; j < n_giant; ++j)
-        if (!matches(giant_hks[j])) return HEXL_E_BADARG;
     for (size_t j = 0; j < n_giant; ++j)
         for (size_t i = 0; i < n_baby; ++i)
             if (d_pts[j * n_baby + i] && !baby_hks[i]) return HEXL_E_BADARG;
     for (size_t j = 0; j < n_giant; ++j)
         if (!giant_hks[j] && giant_elts[j] != 1) return HEXL_E_BADARG;
     HksHoistBytes s;
-    // plan, level, sizes and grids at the key switch's chunk, which this call's never exceeds
-    if (!hks_call_ok(h0, batch, n_limbs, 2, &s.ct)) return HEXL_E_BADARG;
+    if (!hks_hoist_ok(h0, batch, n_limbs, &s) || !hks_hoist_list_ok(h0, baby_hks, baby_elts, n_baby) ||
+        !hks_hoist_list_ok(h0, giant_hks, giant_elts, n_giant))
+        return HEXL_E_BADARG;
     hexl_ks_plan* p = h0->plan;
-    s.pt = size_t(p->K) * p->n * sizeof(u64);
-    s.id = size_t(n_limbs) * p->n * sizeof(u64);
-    for (size_t i = 0; i < n_baby; ++i)
-        if (!hks_galois_elt_ok(baby_elts[i], p->n)) return HEXL_E_BADARG;
-    for (size_t j = 0; j < n_giant; ++j)
-        if (!hks_galois_elt_ok(giant_elts[j], p->n)) return HEXL_E_BADARG;
     if (hx_ranges_overlap(d_out, s.ct, d_ct, s.ct)) return HEXL_E_BADARG;
     for (size_t j = 0; j < n_giant; ++j) {
         const u64* pt_id = d_pt_identity ? d_pt_identity[j] : nullptr;
@@ -1255,7 +1161,7 @@ extern "C" int hexl_hks_linear_transform_bsgs(hexl_hks* const* baby_hks, const u
     const size_t chunk = run.chunk, n = p->n, slice = chunk * 2 * p->K * n;     // doubles of one baby step's slice
     if (n_baby)
         if (int rc = h0->d_bsgs_b.reserve(n_baby * slice)) return rc;
-    if (int rc = h0->d_bsgs_t.reserve(chunk * 2 * p->L * n)) return rc;
+    if (int rc = h0->d_bsgs_t.reserve(chunk * hks_rows(h0).t * n)) return rc;
     // the per-call tables, row after row: what the c0 kernel walks (plaintext, Galois element) and what the sum kernel walks (plaintext,
     // baby slice). Pageable sources, stream-ordered behind the previous call's readers, as hexl_hks_linear_transform's table
     std::vector<HxLtRot> rots;

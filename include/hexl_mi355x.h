@@ -570,8 +570,9 @@ int hexl_ks_gen_keys(hexl_ks_plan* plan, const uint64_t* d_secret, int from_kind
  * HEXL_E_BADARG: a null handle or pointer (batch == 0 does not excuse it), a plan on the integer kernels or with K = L, alpha outside
  * 1 ... L, n_limbs outside 1 ... L, a galois_elt that is even or >= 2n, an output that overlaps an input, a size or a grid that
  * overflows; then HEXL_E_NOKEYS before hexl_hks_set_keys_device; then batch == 0 returns 0.
- * Device memory, owned by the object: the keys (dnum*2*K*n doubles), 154 KiB of constants for all levels (computed at create time: 74 KiB
- * for the key switch, 80 KiB for the rescaling mod-down of the hybrid multiply below), and
+ * Device memory, owned by the object: the keys (dnum*2*K*n doubles), 148 KiB of constants for all levels (computed at create time: 8 KiB of
+ * source inverses and 128 KiB of target weights for the 32 base conversions -- 16 mod-ups, the mod-down, 15 rescaling mod-downs of the
+ * hybrid multiply below -- and 12 KiB of per-limb constants of their 16 divisors), and
  * grow-only scratch for one chunk of min(batch, chunk) instances, chunk as for hexl_keyswitch (256 at n = 16384, the same number of
  * coefficients at other n; HEXL_KS_CHUNK): per instance L*n coefficient words, dnum*K*n extended doubles and 2*K*n accumulator doubles.
  * hexl_hks_scratch_bytes(hks, batch) is that sum at the full level (a lower level uses less of it). hexl_hks_relinearize and

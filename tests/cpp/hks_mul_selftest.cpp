@@ -1,5 +1,5 @@
 // hks_mul_selftest.cpp -- host replay of the scalar chains the hybrid multiply adds (hexl-fpga_amd/csrc/f64_arith.hpp hks_acc_pd /
-// hks_down_rs, called by keyswitch_hybrid.hip k_hks_rs_intt / k_hks_rs_down) against unsigned __int128: IEEE-754 double mul / add / fma /
+// hks_down_rs, called by keyswitch_hybrid.hip k_hks_down_intt<., true> / k_hks_down<., true>) against unsigned __int128: IEEE-754 double mul / add / fma /
 // rint round the same way on x86 (-mfma) and on gfx950, so the kernels' own source is checked here at operands no GPU test enumerates.
 // A stand-alone program (tests/test_hks_mul_selftest.py builds it with -fsanitize=address,undefined).
 //   usage: hks_mul_selftest <draws> <modulus>...

@@ -127,6 +127,46 @@ def test_word_identities_on_the_device(hx, ctx, dev, orc, l):
     s.close()
 
 
+def test_plain_and_rescaling_mod_downs_alternate_on_one_object(hx, ctx, dev, orc):
+    """The two mod-downs share their constants tables and their stage function. One object, calls back to back without recreating it:
+    keyswitch l = 3, relinearize_rescale l = 3, keyswitch l = 3, relinearize_rescale l = 2 (the smallest level with a rescaling row),
+    relinearize l = 1 (row 0 of the mod-up beside row 0 of the divisor table), relinearize_rescale l = 3. Every output word against the
+    models, and the repeated calls bit-equal to their first occurrence: a row mix-up, or a row pointer left over from the call before."""
+    torch = torch_()
+    n, L, K, batch = 1024, 3, 5, 3
+    s = Setup(hx, ctx, orc, n, L, K, 2, orc.primes(K, 51, n))
+    hm = mul_model(orc, s)
+    keys = s.keys()
+    s.hks.set_keys_device(up(hx, dev, keys))
+    ts, rs = [s.words(1, 3, b, 1) for b in range(batch)], [s.words(2, 3, b, 2) for b in range(batch)]
+    ct3 = {l: [s.words(3, l, b, 4) for b in range(batch)] for l in (1, 2, 3)}
+    d_t = up(hx, dev, np.stack(ts))
+    d_ct3 = {l: up(hx, dev, np.stack(ct3[l])) for l in ct3}
+
+    def keyswitch():
+        d_r = up(hx, dev, np.stack(rs))
+        s.hks.keyswitch(d_r, d_t, batch, 3)
+        return d_r
+
+    def rescale(l):
+        out = minus_one(dev, batch * 2 * (l - 1) * n)
+        s.hks.relinearize_rescale(out, d_ct3[l], batch, l)
+        return out
+
+    ks_a, rs3_a, ks_b, rs2 = keyswitch(), rescale(3), keyswitch(), rescale(2)
+    relin1 = minus_one(dev, batch * 2 * 1 * n)
+    s.hks.relinearize(relin1, d_ct3[1], batch, 1)
+    rs3_b = rescale(3)
+    ctx.sync()
+    assert_instances(hx.to_u64(ks_a), [s.model.keyswitch(keys, ts[b], rs[b], 3) for b in range(batch)], batch, NAMES, (2, 3, n), "keyswitch level 3")
+    assert_instances(hx.to_u64(rs3_a), [hm.relinearize_rescale(keys, c, 3) for c in ct3[3]], batch, NAMES, (2, 2, n), "relinearize_rescale level 3")
+    assert_instances(hx.to_u64(rs2), [hm.relinearize_rescale(keys, c, 2) for c in ct3[2]], batch, NAMES, (2, 1, n), "relinearize_rescale level 2")
+    assert_instances(hx.to_u64(relin1), [s.model.relinearize(keys, c, 1) for c in ct3[1]], batch, NAMES, (2, 1, n), "relinearize level 1")
+    assert torch.equal(ks_b, ks_a), "the second keyswitch at level 3 differs from the first"
+    assert torch.equal(rs3_b, rs3_a), "the second relinearize_rescale at level 3 differs from the first"
+    s.close()
+
+
 def test_multiply_sum_relinearize_takes_level_one(hx, ctx, dev, orc):
     n, L, K = 1024, 3, 5
     s = Setup(hx, ctx, orc, n, L, K, 2, orc.primes(K, 51, n))

@@ -26,7 +26,7 @@ def test_entry_points_are_declared_exported_and_bound(hx):
         assert hasattr(lib, name), f"{name} not exported by {hx.LIB_PATH.name}"
     for text in ("R = P q_(l-1)", "out_k = round(X_k / R) - e with e an integer in [0, n_p]", "NOT word for word hexl_hks_relinearize",
                  "21 n sum_d |G_d| D_d / (P q_(l-1)) + (n_p + 1/2)(n + 1)", "the lower bound is 2 for the two rescaling calls",
-                 "154 KiB of constants"):
+                 "148 KiB of constants"):
         assert text in header, text
 
 

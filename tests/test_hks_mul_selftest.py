@@ -1,5 +1,5 @@
 """CPU: the scalar chains the hybrid multiply adds (hexl-fpga_amd/csrc/f64_arith.hpp hks_acc_pd and hks_down_rs, and hks_round at the
-rescaling mod-down's halves -- what keyswitch_hybrid.hip compiles into k_hks_rs_intt and k_hks_rs_down) built for the host and run
+rescaling mod-down's halves -- what keyswitch_hybrid.hip compiles into k_hks_down_intt<., true> and k_hks_down<., true>) built for the host and run
 against unsigned __int128 on the eleven selftest moduli, 27 bits to just below 2^52: canonical words 0 and q - 1, accumulators and
 transform outputs at +-(q/2 + 2), with the intermediate bounds the header states asserted on the way -- tests/cpp/hks_mul_selftest.cpp.
 The program is stand-alone, with its own main, and is built with -fsanitize=address,undefined."""

@@ -9,7 +9,7 @@ replaces, at N = 16384 on 51-bit primes, for (n_baby, n_giant) = (4, 4) and (8, 
     bsgs_sparse  the same call with ONE plaintext per row (every baby column still used): the difference to `bsgs`, divided by the
                  n_giant (n_baby - 1) terms left out, is the cost of one more term of a row -- k_hks_bsgs_sum's two stored vectors and
                  k_galois_c0_pt's gather of c0 together -- beside the flat route's own cost of one more term at this batch,
-                 (flat 8 x 8 - flat 4 x 4) / 48, which is k_hks_mac_galois<., PT_ACC> and the same gather (DESIGN.md 4.6.11 measured
+                 (flat 8 x 8 - flat 4 x 4) / 48, which is k_hks_mac<., PT_ACC> and the same gather (DESIGN.md 4.6.11 measured
                  0.40 ms per term at batch 128)
 The batch is 64: the baby store of 8 steps at K = 16 is 32 MiB per instance, so 64 instances fill its 2 GiB and run as one chunk.
 Every (shape, grid) runs in a child process of its own under a time limit, all its routes in that one process; this process never opens
