@@ -91,6 +91,9 @@ C_ABI = {
     "hexl_hks_linear_transform_bsgs": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz, ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz,
                                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _sz, _u64],
     "hexl_hks_bsgs_scratch_bytes": [_vp, _sz, _sz],
+    "hexl_hks_linear_transform_bsgs_ext": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz, ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz,
+                                           ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp, _sz, _u64, _i],
+    "hexl_hks_bsgs_ext_scratch_bytes": [_vp, _sz, _sz, _i],
     "hexl_hks_multiply_sum_relinearize": [_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _sz, _sz, _u64],
     "hexl_hks_relinearize_rescale": [_vp, _vp, _vp, _sz, _u64],
     "hexl_hks_multiply_sum_rescale": [_vp, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _sz, _sz, _u64],
@@ -136,7 +139,8 @@ def lib() -> ctypes.CDLL:
             fn = getattr(_lib, name)
             fn.argtypes = args
             fn.restype = _sz if name in ("hexl_ks_scratch_bytes", "hexl_lt_bsgs_scratch_bytes", "hexl_hks_scratch_bytes",
-                                      "hexl_hks_hoisted_scratch_bytes", "hexl_hks_bsgs_scratch_bytes", "hexl_hks_mul_scratch_bytes") else _i
+                                      "hexl_hks_hoisted_scratch_bytes", "hexl_hks_bsgs_scratch_bytes", "hexl_hks_bsgs_ext_scratch_bytes",
+                                      "hexl_hks_mul_scratch_bytes") else _i
     return _lib
 
 
@@ -531,6 +535,11 @@ class HybridKeySwitch:
         """device bytes an hks_linear_transform_bsgs call with this object first holds on it: hoisted scratch, baby store and t_j"""
         return lib().hexl_hks_bsgs_scratch_bytes(self.h, n_baby, batch)
 
+    def bsgs_ext_scratch_bytes(self, n_baby: int, batch: int, rescale: int) -> int:
+        """device bytes an hks_linear_transform_bsgs_ext call with this object first holds on it: bsgs_scratch_bytes at the same chunk, the
+        extended-basis accumulator A and, with rescale = 1, the key-free sums F"""
+        return lib().hexl_hks_bsgs_ext_scratch_bytes(self.h, n_baby, batch, rescale)
+
     def multiply_sum_relinearize(self, out, a_s, b_s, batch: int, n_limbs: int, in_limbs=None):
         """out[batch][2][n_limbs][n] = relinearize(plan.ct_tensor_sum(a_s, b_s, n_limbs)) on the hybrid key, word for word, without the
         three-component sum ever existing in memory; operands as KeySwitchPlan.ct_tensor_sum, in_limbs entries in n_limbs ... K"""
@@ -625,6 +634,23 @@ def hks_linear_transform_bsgs(baby_hks, baby_elts, giant_hks, giant_elts, pts, p
                                                 _ptr(ct), batch, n_limbs), "hexl_hks_linear_transform_bsgs")
 
 
+def hks_linear_transform_bsgs_ext(baby_hks, baby_elts, giant_hks, giant_elts, pts, pt_identity, out, ct, batch: int, n_limbs: int, rescale: int):
+    """The sum of hks_linear_transform_bsgs with the giant steps kept in the extended basis and ONE division per call
+    (hexl_hks_linear_transform_bsgs_ext): out[batch][2][n_limbs][n] for rescale = 0; rescale = 1 divides by P q_(l-1) in the same mod-down
+    and writes out[batch][2][n_limbs - 1][n], the rescaled result. Arguments as hks_linear_transform_bsgs. Not word for word that call
+    when some G_j != 1 (one rounding instead of one per row and per rotated giant step); both decrypt alike."""
+    n_baby, n_giant = len(baby_hks), len(giant_hks)
+    if len(baby_elts) != n_baby or len(giant_elts) != n_giant or len(pts) != n_giant or any(len(row) != n_baby for row in pts):
+        raise ValueError("hks_linear_transform_bsgs_ext: one element per object and n_giant rows of n_baby plaintexts")
+    if pt_identity is not None and len(pt_identity) != n_giant:
+        raise ValueError("hks_linear_transform_bsgs_ext: one identity plaintext (or None) per giant step")
+    flat = [p for row in pts for p in row]
+    _check(lib().hexl_hks_linear_transform_bsgs_ext(_handles(baby_hks), _u64_array(baby_elts), n_baby, _handles(giant_hks),
+                                                    _u64_array(giant_elts), n_giant, _opt_ptrs(flat),
+                                                    None if pt_identity is None else _opt_ptrs(pt_identity), _ptr(out), _ptr(ct), batch,
+                                                    n_limbs, rescale), "hexl_hks_linear_transform_bsgs_ext")
+
+
 def _opt_ptrs(items):
     """ctypes array of pointers with None entries as NULL"""
     return (_vp * len(items))(*[None if a is None else _ptr(a) for a in items])
@@ -655,6 +681,6 @@ def lt_bsgs_scratch_bytes(plan, n_baby: int, batch: int) -> int:
 
 from .host_api import HexlFpga  # noqa: E402  (mirror of host/inc/hexl-fpga.h)
 
-__all__ = ["Context", "KeySwitchPlan", "HybridKeySwitch", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform", "hks_rotate_hoisted", "hks_linear_transform", "hks_linear_transform_bsgs",
+__all__ = ["Context", "KeySwitchPlan", "HybridKeySwitch", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform", "hks_rotate_hoisted", "hks_linear_transform", "hks_linear_transform_bsgs", "hks_linear_transform_bsgs_ext",
            "linear_transform_bsgs", "lt_bsgs_scratch_bytes", "C_ABI", "SAMPLE_UNIFORM", "SAMPLE_TERNARY", "SAMPLE_CBD21", "KEY_FROM_POLY", "KEY_FROM_SQUARE", "KEY_FROM_GALOIS", "seed_words",
            "LIB_PATH", "ROOT"]

@@ -215,6 +215,13 @@ HX_HD double hks_acc_pd(double acc, double d, double pm, double pm_p, const Mod 
 HX_HD double hks_down_rs(double d, double acc, double w, double pm, double pm_p, double rinv, double rinv_p, const Mod m) {
     return lift(reduce(mul_shoup(hks_acc_pd(acc, d, pm, pm_p, m) - w, rinv, rinv_p, m), m), m);
 }
+// ---- the accumulation in the extended basis of hexl_hks_linear_transform_bsgs_ext (keyswitch_hybrid.hip k_hks_mac<., HKS_MAC_ACC>,
+// k_hks_ext_add), replayed by tests/cpp/hks_bsgs_ext_selftest.cpp.
+// A' = (A + x) mod p, centred: A the accumulator as this function leaves it (0 in front of the first addend), x a reduce output -- the
+// sum of hks_mac_term over the digits (the giant step's W), or a word of a row's inner sum as lt_mac / lt_mac_acc left it, permuted.
+// Both |.| <= p/2 + 2: |A + x| <= p + 4 < 2^53, an exact integer inside reduce's domain, and |A'| <= p/2 + 2 again -- what
+// k_hks_down_intt and k_hks_down take from an accumulator. EVERY addend is followed by a reduce: inner and W are two calls, not one sum.
+HX_HD double hks_ext_acc(double acc, double x, const Mod m) { return reduce(acc + x, m); }
 
 // The STRICT butterflies (every value reduced after every operation) leave room above 2^52: the largest intermediate is the
 // inverse butterfly's |h - k p| <= (1.31 + 0.22) p for |d| = |X - Y| <= p + 4 (quotient from the product: three roundings of a

@@ -18,6 +18,11 @@
 // The hoisted callers (hexl_hks_rotate_hoisted, hexl_hks_linear_transform) run steps 1-2 ONCE per chunk on c1 of the
 // ciphertexts, read in place, and step 3 per rotation with sigma_g applied to ext on the way in and the keys of that rotation's object:
 //   3g  acc[k][j] = sum_d sigma_g(ext_d[j]) key_r[d][k][j]   (stored, or weighted by a plaintext and summed over the rotations)   k_hks_mac, a mode with HksRot
+// The double-hoisted BSGS (hexl_hks_linear_transform_bsgs_ext) keeps the giant steps in the extended basis as well: per
+// rotated row ONE half mod-down (steps 4a-4c on component 1 alone: the C1 forms of the three kernels), a second mod-up, and
+//   3G  A[k][j] += sum_d sigma_G(ext'_d[j]) key_G[d][k][j]                                                              k_hks_mac, HKS_MAC_ACC
+//   3s  A[0][j] += sigma_G(inner[0][j]) on every row of T_l, the special rows included                                 k_hks_ext_add
+// and ONE mod-down of A per call, by P or -- with the rescale folded in -- by R with d_k = F_k, the key-free sums.
 // The transforms are one workgroup per polynomial on WgNttF64, limb-major, as k_rns_fwd / k_rns_inv (rns_ops.hip) and k_rs_intt /
 // k_rs_down (ckks_ops.hip); every intermediate lies at its LOGICAL index (coefficients in natural order, NTT form in the transforms'
 // output order), so the word-wise kernels between them need no index map and the keys keep the caller's order. The scalar chains
@@ -34,7 +39,7 @@ constexpr u32 HKS_MAX_LIMBS = 16;                                 // hexl_ks_pla
 //   row 16           the mod-down by P, the same at every level (sources S; targets the data limbs)
 //   row 16 + (l - 1) the rescaling mod-down of level l >= 2 (sources S and the limb l - 1; targets i < l - 1)
 // and one DIVISOR ROW of the third table per divisor of a mod-down: row 0 for P, row l - 1 for R = P q_(l-1).
-enum HksConv : int { HKS_CONV_UP, HKS_CONV_DOWN, HKS_CONV_RS };
+enum HksConv : int { HKS_CONV_UP, HKS_CONV_DOWN, HKS_CONV_RS, HKS_CONV_DOWN1 };   // DOWN1: the mod-down by P of component 1 alone
 constexpr u32 HKS_CONV_ROWS = 2 * HKS_MAX_LIMBS;
 struct HksSrc { double hinv, hinv_p; };                           // (D / q_i)^-1 mod q_i centred, and fl(. / q_i)
 struct HksWt { double w, wp; };                                   // (D / q_i) mod q_j centred, and fl(. / q_j)
@@ -44,7 +49,7 @@ struct HksDiv {                                                   // per (diviso
     double half;             // a source limb s: floor(Q/2) mod q_s
     double pm, pm_p;         // Q = R, i < l: P mod q_i centred, fl(. / q_i)
 };
-static size_t hks_conv_row(HksConv mode, u32 l) { return mode == HKS_CONV_UP ? l - 1 : mode == HKS_CONV_DOWN ? HKS_MAX_LIMBS : HKS_MAX_LIMBS + (l - 1); }
+static size_t hks_conv_row(HksConv mode, u32 l) { return mode == HKS_CONV_UP ? l - 1 : mode == HKS_CONV_RS ? HKS_MAX_LIMBS + (l - 1) : HKS_MAX_LIMBS; }
 static size_t hks_div_row(HksConv mode, u32 l) { return mode == HKS_CONV_RS ? l - 1 : 0; }
 
 struct hexl_hks {
@@ -67,9 +72,12 @@ struct hexl_hks {
     HxDevBuf<u64> d_bsgs_t;           // one giant step's inner sum t_j: [chunk][2][L][n] canonical words ([nb][2][l][n] of it used)
     HxDevBuf<u64> d_d01;              // hexl_hks_multiply_sum_rescale: (d0, d1) of one chunk's tensor sums, [chunk][2][L][n] (grow-only,
                                       // [nb][2][l][n] of it used; allocated at its first call)
+                                      // hexl_hks_linear_transform_bsgs_ext with rescale = 1: F, the key-free sums of one chunk, the same shape
+    HxDevBuf<double> d_ext_a;         // hexl_hks_linear_transform_bsgs_ext: A, the giant steps' sum in the extended basis, [chunk][2][K][n]
+                                      // ([nb][2][T][n] of it used; grow-only, allocated at its first call)
     explicit hexl_hks(hexl_ks_plan* p)
         : plan(p), d_keys(p->ctx), d_src(p->ctx), d_wt(p->ctx), d_div(p->ctx), d_coef(p->ctx), d_ext(p->ctx), d_acc(p->ctx), d_slice(p->ctx),
-          d_w1(p->ctx), d_bsgs_b(p->ctx), d_bsgs_t(p->ctx), d_d01(p->ctx) {}
+          d_w1(p->ctx), d_bsgs_b(p->ctx), d_bsgs_t(p->ctx), d_d01(p->ctx), d_ext_a(p->ctx) {}
 };
 
 struct HksArgs {
@@ -163,13 +171,16 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_fwd(HksArgs a) {
 // step 4a, one workgroup per (source row, instance, component), in place: b_s = (INTT_s(acc[k][s]) + floor(Q/2)) mod q_s, canonical.
 // The sources are the rows of S; RS: one more per (instance, component), the data limb l - 1, which takes (P mod q) d_k on the way in
 // (step 3'). That row of acc is dead for everything else: the rescaled output has no limb l - 1.
-template <int LOGN, int LOGE, int LAZY, bool RS>
+// C1 (with the divisor P only): component 1 alone, one workgroup per (source row, instance) -- the half mod-down that forms u_j of a
+// rotated row of hexl_hks_linear_transform_bsgs_ext; component 0 of acc is neither read nor written.
+template <int LOGN, int LOGE, int LAZY, bool RS, bool C1 = false>
 __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_down_intt(HksArgs a) {
+    static_assert(!(RS && C1), "the half mod-down divides by P");
     using G = Geom<LOGN, LOGE>;
     extern __shared__ __attribute__((aligned(16))) double ldsd[];
     const int tid = threadIdx.x;
     const u32 np = a.K - a.L;
-    const u32 si = blockIdx.x / (2 * a.nb), bk = blockIdx.x - si * 2 * a.nb;
+    const u32 si = blockIdx.x / (C1 ? a.nb : 2 * a.nb), bk = C1 ? 2 * (blockIdx.x - si * a.nb) + 1 : blockIdx.x - si * 2 * a.nb;
     const bool data = RS && si == np;                            // (uniform)
     const u32 s = data ? a.l - 1 : a.L + si, jT = data ? a.l - 1 : a.l + si;
     const KsModF64 md = a.mods[s];
@@ -197,12 +208,14 @@ __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_down_intt(HksArgs a)
 // step 4c, one workgroup per (target limb i, instance, component): k_rs_down's shape -- the transform of w, then the epilogue on acc and
 // a second word, both requested behind the transform (k_rs_down's LAZY < 0 form). The second word is the one `result` holds, and the
 // output is accumulated onto it, [2][l][n]; RS: it is d_k, which enters as (P mod q_i) d_k, and the output is WRITTEN, [2][l - 1][n].
-template <int LOGN, int LOGE, int LAZY, bool RS>
+// C1: component 1 alone, one workgroup per (target limb, instance); component 0 of `result` keeps its words.
+template <int LOGN, int LOGE, int LAZY, bool RS, bool C1 = false>
 __global__ __launch_bounds__(1 << (LOGN - LOGE)) void k_hks_down(HksArgs a) {
+    static_assert(!(RS && C1), "the half mod-down divides by P");
     using G = Geom<LOGN, LOGE>;
     extern __shared__ __attribute__((aligned(16))) double ldsd[];
     const int tid = threadIdx.x;
-    const u32 i = blockIdx.x / (2 * a.nb), bk = blockIdx.x - i * 2 * a.nb;
+    const u32 i = blockIdx.x / (C1 ? a.nb : 2 * a.nb), bk = C1 ? 2 * (blockIdx.x - i * a.nb) + 1 : blockIdx.x - i * 2 * a.nb;
     const u32 b = bk >> 1, k = bk & 1;
     const Mod m = a.mods[i].m;
     const HksDiv dv = a.div[i];
@@ -247,6 +260,7 @@ static_assert(HKS_THREADS == HX_WW_THREADS, "hx_ww_grid(., ., ., HKS_LOG_PIECE) 
 // into its own range before the products (hks_conv_term). Moduli and weights of a target are wave-uniform: scalar loads.
 // HKS_CONV_RS is the mod-down of the rescaling calls: one more source per component, the row l - 1 of acc (limb l - 1, not contiguous
 // with the special rows), one target fewer. a.src / a.wt / a.div are the rows of the launch's conversion and divisor (hks_point_rows).
+// HKS_CONV_DOWN1 is HKS_CONV_DOWN on component 1 alone: one group per instance, w into d_w1 (hks_w with k = 1), coef untouched.
 template <HksConv MODE, int MAXS>
 __global__ __launch_bounds__(HKS_THREADS) void k_hks_conv(HksArgs a) {
     typedef double d2 __attribute__((ext_vector_type(2)));
@@ -254,8 +268,9 @@ __global__ __launch_bounds__(HKS_THREADS) void k_hks_conv(HksArgs a) {
     constexpr bool DOWN = MODE != HKS_CONV_UP, RS = MODE == HKS_CONV_RS;
     const u32 lp = a.logn - HKS_LOG_PIECE;
     const u32 grp = blockIdx.x >> lp, piece = blockIdx.x - (grp << lp);
-    const u32 ng = DOWN ? 2u : a.dl;
-    const u32 b = grp / ng, g = grp - b * ng;
+    constexpr bool ONE = MODE == HKS_CONV_DOWN1;
+    const u32 ng = ONE ? 1u : DOWN ? 2u : a.dl;
+    const u32 b = grp / ng, g = ONE ? 1u : grp - b * ng;
     const size_t n = size_t(1) << a.logn, c = (size_t(piece) << HKS_LOG_PIECE) + 2 * threadIdx.x;
     const u32 s0 = DOWN ? a.L : g * a.alpha;                      // first source limb (plan index)
     const u32 ns = RS ? a.K - a.L + 1 : DOWN ? a.K - a.L : (a.l - s0 < a.alpha ? a.l - s0 : a.alpha);
@@ -317,8 +332,10 @@ __global__ __launch_bounds__(HKS_THREADS) void k_hks_conv(HksArgs a) {
 //   HKS_MAC_PT_ACC    ... its later rotations: acc = acc + pt . sum (hxf::lt_mac_acc), the old words requested in front of the gather
 // pt is [K][n] canonical words in the transforms' output order: the lane's pair is converted once (hxf::lt_pt) and serves every instance
 // it walks. acc never leaves the extended basis between rotations, so step 4 runs once for all of them.
+//   HKS_MAC_ACC       hexl_hks_linear_transform_bsgs_ext, a rotated giant step: acc = acc + sum (hxf::hks_ext_acc), no plaintext --
+//                     PT_ACC's read-modify-write without the weight; a.acc points at A
 struct HksRot { const double* keys; const u64* pt; u32 g; };      // the rotation's object's keys [dnum][2][K][n]; pt: the plaintext modes
-enum HksMacMode : int { HKS_MAC_PLAIN, HKS_MAC_STORE, HKS_MAC_PT_FIRST, HKS_MAC_PT_ACC };
+enum HksMacMode : int { HKS_MAC_PLAIN, HKS_MAC_STORE, HKS_MAC_PT_FIRST, HKS_MAC_PT_ACC, HKS_MAC_ACC };
 
 // ONE kernel template for both: ROT is empty for HKS_MAC_PLAIN -- the kernel's arguments are (HksArgs) alone, as the key switch's always
 // were -- and {HksRot} for the other modes, (HksArgs, HksRot). `(rot, ...)` is that one HksRot; it is named only where MODE has one.
@@ -363,7 +380,7 @@ __global__ __launch_bounds__(HKS_THREADS) void k_hks_mac(HksArgs a, ROT... rot) 
         d2* p0 = MODE == HKS_MAC_PLAIN ? nullptr : reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 0) * a.T + jT) * n + c);
         d2* p1 = MODE == HKS_MAC_PLAIN ? nullptr : reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 1) * a.T + jT) * n + c);
         d2 prev0 = {0.0, 0.0}, prev1 = {0.0, 0.0};
-        if constexpr (MODE == HKS_MAC_PT_ACC) { prev0 = *p0; prev1 = *p1; }
+        if constexpr (MODE == HKS_MAC_PT_ACC || MODE == HKS_MAC_ACC) { prev0 = *p0; prev1 = *p1; }
         d2 acc0 = {0.0, 0.0}, acc1 = {0.0, 0.0};
 #pragma unroll
         for (int d = 0; d < MAXD; ++d)
@@ -381,6 +398,13 @@ __global__ __launch_bounds__(HKS_THREADS) void k_hks_mac(HksArgs a, ROT... rot) 
             for (int e = 0; e < 2; ++e) {
                 acc0[e] = MODE == HKS_MAC_PT_FIRST ? hxf::lt_mac(acc0[e], w[e], m) : hxf::lt_mac_acc(acc0[e], w[e], prev0[e], m);
                 acc1[e] = MODE == HKS_MAC_PT_FIRST ? hxf::lt_mac(acc1[e], w[e], m) : hxf::lt_mac_acc(acc1[e], w[e], prev1[e], m);
+            }
+        }
+        if constexpr (MODE == HKS_MAC_ACC) {
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                acc0[e] = hxf::hks_ext_acc(prev0[e], acc0[e], m);
+                acc1[e] = hxf::hks_ext_acc(prev1[e], acc1[e], m);
             }
         }
         if constexpr (MODE == HKS_MAC_PLAIN) p0 = reinterpret_cast<d2*>(a.acc + ((size_t(b) * 2 + 0) * a.T + jT) * n + c);
@@ -439,6 +463,34 @@ __global__ __launch_bounds__(HKS_THREADS) void k_hks_bsgs_sum(HksArgs a, const H
         *reinterpret_cast<d2*>(a.acc + o0) = acc0;
         *reinterpret_cast<d2*>(a.acc + o1) = acc1;
     }
+}
+
+// step 3s of hexl_hks_linear_transform_bsgs_ext: A[b][k][jT] += sigma_g(src[b][k][jT]) for k < n_comp, on EVERY row
+// of T_l -- the special rows are permuted like the data rows: sigma_g acts on the polynomial, whatever modulus it is reduced by. src is
+// a row's inner sum as k_hks_bsgs_sum left it in acc, A what a.acc points at here; both [nb][2][T][n] doubles, reduce outputs, at the
+// logical index. k_hks_mac's lane layout and gather: the written side is 16-byte accesses at c, the read side ONE 16-byte load at the
+// aligned pair that holds the sources of c and c + 1, swapped when the source of c is odd. A rotated row adds component 0 alone
+// (n_comp = 1: its component 1 went through the half mod-down and the giant key), a row with G = 1 both with g = 1 (no permutation).
+__global__ __launch_bounds__(HKS_THREADS) void k_hks_ext_add(HksArgs a, const double* src, u32 g, u32 n_comp) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    const u32 n = 1u << a.logn, pairs = n >> 1;
+    const u32 gid = blockIdx.x * blockDim.x + threadIdx.x;        // (row of T_l, pair)
+    const u32 jT = gid / pairs;
+    if (jT >= a.T) return;
+    const u32 c = (gid - jT * pairs) * 2;
+    const u32 s = galois_src(c, a.logn, g);                       // the source of c; that of c + 1 is s ^ 1
+    const u32 sp = s & ~1u;
+    const bool swap = s & 1u;
+    const Mod m = a.mods[hks_limb(a, jT)].m;
+    for (u32 b = blockIdx.y; b < a.nb; b += gridDim.y)
+        for (u32 k = 0; k < n_comp; ++k) {
+            const size_t row = ((size_t(b) * 2 + k) * a.T + jT) * n;
+            d2* p = reinterpret_cast<d2*>(a.acc + row + c);
+            const d2 prev = *p;
+            const d2 v = *reinterpret_cast<const d2*>(src + row + sp);
+            const d2 o = {hxf::hks_ext_acc(prev.x, swap ? v.y : v.x, m), hxf::hks_ext_acc(prev.y, swap ? v.x : v.y, m)};
+            *p = o;
+        }
 }
 
 // the key install: the caller's [dnum][2][K][n] canonical words as centred doubles at the same place, one workgroup per (row, piece)
@@ -504,7 +556,8 @@ static u32 hks_piece_grid(const hexl_ks_plan* p, size_t rows) { return (u32)(row
 template <int LOGN, int LOGE, int LAZY>
 static int hks_optin(hexl_hks* h) {
     return hx_lds_optin<k_hks_intt<LOGN, LOGE, LAZY>, k_hks_fwd<LOGN, LOGE, LAZY>, k_hks_down_intt<LOGN, LOGE, LAZY, false>,
-                        k_hks_down<LOGN, LOGE, LAZY, false>, k_hks_down_intt<LOGN, LOGE, LAZY, true>, k_hks_down<LOGN, LOGE, LAZY, true>>(
+                        k_hks_down<LOGN, LOGE, LAZY, false>, k_hks_down_intt<LOGN, LOGE, LAZY, true>, k_hks_down<LOGN, LOGE, LAZY, true>,
+                        k_hks_down_intt<LOGN, LOGE, LAZY, false, true>, k_hks_down<LOGN, LOGE, LAZY, false, true>>(
         h->plan->ctx->device, Geom<LOGN, LOGE>::LDS_USED);
 }
 // the rows of the constants a launch reads: the conversion `mode` at level l, and the divisor of that mod-down
@@ -544,6 +597,7 @@ static int hks_stage_mac_galois(hexl_hks* h, const HksArgs& a, const HksRot& rot
     hks_with_max(a.dl, [&](auto M) {
         constexpr int D = decltype(M)::value;
         if (mode == HKS_MAC_STORE)         hipLaunchKernelGGL((k_hks_mac<D, HKS_MAC_STORE, HksRot>), grid, ww, 0, st, a, rot);
+        else if (mode == HKS_MAC_ACC)      hipLaunchKernelGGL((k_hks_mac<D, HKS_MAC_ACC, HksRot>), grid, ww, 0, st, a, rot);
         else if (mode == HKS_MAC_PT_FIRST) hipLaunchKernelGGL((k_hks_mac<D, HKS_MAC_PT_FIRST, HksRot>), grid, ww, 0, st, a, rot);
         else                               hipLaunchKernelGGL((k_hks_mac<D, HKS_MAC_PT_ACC, HksRot>), grid, ww, 0, st, a, rot);
     });
@@ -576,6 +630,30 @@ static int hks_stage_down(hexl_hks* h, const HksArgs& a) {
     return (int)hipGetLastError();
 }
 
+// step 4 on component 1 alone (a.w1 set): half the workgroups of each of the three launches, nothing of component 0 read or written
+template <int LOGN, int LOGE, int LAZY>
+static int hks_stage_down_c1(hexl_hks* h, const HksArgs& a) {
+    using G = Geom<LOGN, LOGE>;
+    hexl_ks_plan* p = h->plan;
+    if (int rc = hks_optin<LOGN, LOGE, LAZY>(h)) return rc;
+    hipStream_t st = p->ctx->stream;
+    const dim3 wg(G::T), ww(HKS_THREADS);
+    const u32 nb = a.nb, nsrc = a.K - a.L;
+    HksArgs dn = a;
+    hks_point_rows(h, HKS_CONV_DOWN1, a.l, dn);
+    hipLaunchKernelGGL((k_hks_down_intt<LOGN, LOGE, LAZY, false, true>), dim3(nsrc * nb), wg, G::LDS_USED, st, dn);
+    hks_with_max(nsrc, [&](auto M) {
+        hipLaunchKernelGGL((k_hks_conv<HKS_CONV_DOWN1, decltype(M)::value>), dim3(hks_piece_grid(p, nb)), ww, 0, st, dn);
+    });
+    hipLaunchKernelGGL((k_hks_down<LOGN, LOGE, LAZY, false, true>), dim3(a.l * nb), wg, G::LDS_USED, st, dn);
+    return (int)hipGetLastError();
+}
+
+static int hks_stage_ext_add(hexl_hks* h, const HksArgs& a, const double* src, u32 g, u32 n_comp) {
+    hipLaunchKernelGGL(k_hks_ext_add, hks_mac_grid(a), dim3(HKS_THREADS), 0, h->plan->ctx->stream, a, src, g, n_comp);
+    return (int)hipGetLastError();
+}
+
 template <int LOGN, int LOGE, int LAZY>
 static int hks_run_chunk(hexl_hks* h, const HksArgs& a) {
     if (int rc = hks_stage_up<LOGN, LOGE, LAZY>(h, a)) return rc;
@@ -591,11 +669,12 @@ struct HksRows {
     size_t w1;                        // the hoisted callers: + L
     size_t t;                         // hexl_hks_linear_transform_bsgs: + 2 L beside w1
     size_t slice, d01;                // the slice of rotate / relinearize / the tensor calls: L; the rescaling tensor call: + 2 L beside it
+    size_t ext_a;                     // hexl_hks_linear_transform_bsgs_ext: + 2 K beside the BSGS call's, and d01 with rescale = 1
     size_t ks() const { return coef + ext + acc; }
 };
 static HksRows hks_rows(const hexl_hks* h) {
     const size_t L = h->plan->L, K = h->plan->K;
-    return HksRows{L, size_t(h->dnum) * K, 2 * K, L, 2 * L, L, 2 * L};
+    return HksRows{L, size_t(h->dnum) * K, 2 * K, L, 2 * L, L, 2 * L, 2 * K};
 }
 static size_t hks_row_bytes(const hexl_hks* h) { return h->plan->n * sizeof(u64); }
 
@@ -968,6 +1047,30 @@ struct HksHoist {
         a.result = d_out;
         return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return hks_stage_down<N, E, Z, false>(h0, a); });
     }
+    // ---- hexl_hks_linear_transform_bsgs_ext: A is the sum of the giant steps in the extended basis, [nb][2][T][n] ----
+    // step 4 on component 1 of acc alone, ADDED into component 1 of d_t[nb][2][l][n]; w in d_w1, coef and component 0 untouched
+    int down_c1(u64* d_t) {
+        a.result = d_t;
+        return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) { return hks_stage_down_c1<N, E, Z>(h0, a); });
+    }
+    // A += sigma_g of the first n_comp components of acc, every row of T_l
+    int ext_add(double* A, u32 g, u32 n_comp) const {
+        HksArgs m = a;
+        m.acc = A;
+        return hks_stage_ext_add(h0, m, a.acc, g, n_comp);
+    }
+    // the one mod-down of A: by P, ADDED into d_out[nb][2][l][n] (F == nullptr: the key-free sums lie there), or by R = P q_(l-1) with
+    // d_k = F_k ([nb][2][l][n]), WRITTEN to d_out[nb][2][l - 1][n]
+    int down_ext(double* A, u64* d_out, const u64* F) const {
+        HksArgs m = a;
+        m.acc = A;
+        m.result = d_out;
+        m.d01 = F;
+        m.d01_stride = per;
+        return hx_with_f64_geom(p->logn, lazy, [&](auto N, auto E, auto Z) {
+            return F ? hks_stage_down<N, E, Z, true>(h0, m) : hks_stage_down<N, E, Z, false>(h0, m);
+        });
+    }
 };
 
 // What the three hoisted entry points check alike (everything here decides HEXL_E_BADARG). hks_hoist_ok: plan, level, sizes and grids of
@@ -1098,20 +1201,28 @@ static size_t hks_bsgs_chunk(const hexl_hks* h, size_t n_baby, size_t batch) {
     return fit >= chunk ? chunk : fit ? fit : 1;
 }
 
-extern "C" size_t hexl_hks_bsgs_scratch_bytes(const hexl_hks* h, size_t n_baby, size_t batch) {
-    if (!h) return 0;
+// ext: hexl_hks_linear_transform_bsgs_ext, which holds A as well, and F with rescale = 1
+static size_t hks_bsgs_scratch(const hexl_hks* h, size_t n_baby, size_t batch, bool ext, int rescale) {
     const size_t chunk = hks_bsgs_chunk(h, n_baby, batch);
     // per instance: the hoisted callers' scratch and t_j
     const HksRows r = hks_rows(h);
-    const size_t fixed = (r.ks() + r.w1 + r.t) * hks_row_bytes(h);
+    const size_t fixed = (r.ks() + r.w1 + r.t + (ext ? r.ext_a : 0) + (ext && rescale ? r.d01 : 0)) * hks_row_bytes(h);
     if (chunk && (fixed > SIZE_MAX / chunk || n_baby > (SIZE_MAX / chunk - fixed) / hks_bsgs_slice_bytes(h))) return SIZE_MAX;
     return chunk * (n_baby * hks_bsgs_slice_bytes(h) + fixed);
 }
+extern "C" size_t hexl_hks_bsgs_scratch_bytes(const hexl_hks* h, size_t n_baby, size_t batch) {
+    return h ? hks_bsgs_scratch(h, n_baby, batch, false, 0) : 0;
+}
+extern "C" size_t hexl_hks_bsgs_ext_scratch_bytes(const hexl_hks* h, size_t n_baby, size_t batch, int rescale) {
+    return h ? hks_bsgs_scratch(h, n_baby, batch, true, rescale) : 0;
+}
 
-extern "C" int hexl_hks_linear_transform_bsgs(hexl_hks* const* baby_hks, const uint64_t* baby_elts, size_t n_baby,
-                                              hexl_hks* const* giant_hks, const uint64_t* giant_elts, size_t n_giant,
-                                              const uint64_t* const* d_pts, const uint64_t* const* d_pt_identity, uint64_t* d_out,
-                                              const uint64_t* d_ct, size_t batch, uint64_t n_limbs) {
+// What the two BSGS entry points check alike and in this order: HEXL_E_BADARG, then HEXL_E_NOKEYS for an object that is USED. out_limbs:
+// the limbs of d_out[batch][2][out_limbs][n] (n_limbs, or n_limbs - 1 behind the folded rescale). *h0_out: the scratch owner.
+static int hks_bsgs_check(hexl_hks* const* baby_hks, const uint64_t* baby_elts, size_t n_baby, hexl_hks* const* giant_hks,
+                          const uint64_t* giant_elts, size_t n_giant, const uint64_t* const* d_pts, const uint64_t* const* d_pt_identity,
+                          const uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t n_limbs, uint64_t out_limbs, bool ext,
+                          int rescale, hexl_hks** h0_out) {
     if (!baby_hks || !baby_elts || !giant_hks || !giant_elts || !d_pts || !d_out || !d_ct || !n_giant) return HEXL_E_BADARG;
     if (n_giant > SIZE_MAX / sizeof(HxLtRot) / 2 || (n_baby && n_giant > SIZE_MAX / sizeof(HxLtRot) / 2 / n_baby)) return HEXL_E_BADARG;
     // the object that lends its scratch and buffers: baby_hks[0] whenever there is one
@@ -1135,67 +1246,106 @@ extern "C" int hexl_hks_linear_transform_bsgs(hexl_hks* const* baby_hks, const u
     if (!hks_hoist_ok(h0, batch, n_limbs, &s) || !hks_hoist_list_ok(h0, baby_hks, baby_elts, n_baby) ||
         !hks_hoist_list_ok(h0, giant_hks, giant_elts, n_giant))
         return HEXL_E_BADARG;
-    hexl_ks_plan* p = h0->plan;
-    if (hx_ranges_overlap(d_out, s.ct, d_ct, s.ct)) return HEXL_E_BADARG;
+    // the output's real size: the overlap checks of hexl_hks_linear_transform_bsgs_ext with rescale = 1 see [batch][2][n_limbs - 1][n]
+    const size_t out_bytes = s.ct / n_limbs * out_limbs;
+    if (hx_ranges_overlap(d_out, out_bytes, d_ct, s.ct)) return HEXL_E_BADARG;
     for (size_t j = 0; j < n_giant; ++j) {
         const u64* pt_id = d_pt_identity ? d_pt_identity[j] : nullptr;
-        if (pt_id && hx_ranges_overlap(d_out, s.ct, pt_id, s.id)) return HEXL_E_BADARG;
+        if (pt_id && hx_ranges_overlap(d_out, out_bytes, pt_id, s.id)) return HEXL_E_BADARG;
         for (size_t i = 0; i < n_baby; ++i)
             if (const u64* pt = d_pts[j * n_baby + i])
-                if (hx_ranges_overlap(d_out, s.ct, pt, s.pt)) return HEXL_E_BADARG;
+                if (hx_ranges_overlap(d_out, out_bytes, pt, s.pt)) return HEXL_E_BADARG;
     }
     if (n_baby > HX_LT_BSGS_STORE_BYTES / hks_bsgs_slice_bytes(h0)) return HEXL_E_BADARG;   // not one instance would fit the baby store
-    if (hexl_hks_bsgs_scratch_bytes(h0, n_baby, batch) == SIZE_MAX) return HEXL_E_BADARG;
+    if (hks_bsgs_scratch(h0, n_baby, batch, ext, rescale) == SIZE_MAX) return HEXL_E_BADARG;
     for (size_t j = 0; j < n_giant; ++j) {
         if (giant_elts[j] != 1 && !giant_hks[j]->have_keys) return HEXL_E_NOKEYS;
         for (size_t i = 0; i < n_baby; ++i)
             if (d_pts[j * n_baby + i] && !baby_hks[i]->have_keys) return HEXL_E_NOKEYS;
     }
+    *h0_out = h0;
+    return 0;
+}
+
+// What the two BSGS entry points run alike in h0's scratch: the hoisted callers' buffers at the BSGS chunk, the baby store, t_j, and the
+// per-call tables, row after row: what the c0 kernel walks (plaintext, Galois element) and what the sum kernel walks (plaintext, baby
+// slice). Pageable sources, stream-ordered behind the previous call's readers, as hexl_hks_linear_transform's table
+struct HksBsgsRun {
+    HksHoist run;
+    size_t slice = 0, total = 0;                                  // doubles of one baby step's slice; terms of all rows
+    std::vector<size_t> off;                                      // row j's terms: off[j] ... off[j + 1] - 1
+    std::vector<char> used;                                       // baby step i is used by some row
+    const HxLtRot* d_rots = nullptr;
+    const HksBsgsTerm* d_terms = nullptr;
+    HksBsgsRun(hexl_hks* h0, size_t n_baby, size_t n_giant, size_t batch, u32 l) : run(h0, batch, l), off(n_giant + 1), used(n_baby, 0) {
+        run.chunk = hks_bsgs_chunk(h0, n_baby, batch);
+    }
+    int prepare(const uint64_t* baby_elts, const uint64_t* const* d_pts) {
+        hexl_hks* h0 = run.h0;
+        hexl_ctx* c = run.p->ctx;
+        const size_t n_baby = used.size(), n_giant = off.size() - 1, n = run.p->n;
+        if (int rc = run.reserve()) return rc;
+        slice = run.chunk * 2 * run.p->K * n;
+        if (n_baby)
+            if (int rc = h0->d_bsgs_b.reserve(n_baby * slice)) return rc;
+        if (int rc = h0->d_bsgs_t.reserve(run.chunk * hks_rows(h0).t * n)) return rc;
+        std::vector<HxLtRot> rots;
+        std::vector<HksBsgsTerm> terms;
+        for (size_t j = 0; j < n_giant; ++j) {
+            off[j] = rots.size();
+            for (size_t i = 0; i < n_baby; ++i)
+                if (const u64* pt = d_pts[j * n_baby + i]) {
+                    rots.push_back(HxLtRot{pt, baby_elts[i]});
+                    terms.push_back(HksBsgsTerm{pt, h0->d_bsgs_b + i * slice});
+                    used[i] = 1;
+                }
+        }
+        total = off[n_giant] = rots.size();
+        static_assert(sizeof(HxLtRot) == 16 && sizeof(HksBsgsTerm) == 16, "the two tables share one 16-byte-aligned reservation");
+        if (total) {
+            if (int rc = c->d_shared.reserve(total * (sizeof(HxLtRot) + sizeof(HksBsgsTerm)))) return rc;
+            HX_CHECK(hipMemcpyAsync(c->d_shared, rots.data(), total * sizeof(HxLtRot), hipMemcpyHostToDevice, c->stream));
+            HX_CHECK(hipMemcpyAsync((HxLtRot*)c->d_shared.get() + total, terms.data(), total * sizeof(HksBsgsTerm), hipMemcpyHostToDevice, c->stream));
+        }
+        d_rots = (const HxLtRot*)c->d_shared.get();
+        d_terms = (const HksBsgsTerm*)(d_rots + total);
+        return 0;
+    }
+    // the mod-up of c1 and one stored multiply-accumulate per baby step that some row uses (coef and ext are free after the last of them)
+    int babies(hexl_hks* const* baby_hks, const uint64_t* baby_elts, const u64* ct, size_t nb) {
+        if (!total) return 0;
+        if (int rc = run.up(ct, nb)) return rc;
+        for (size_t i = 0; i < used.size(); ++i)
+            if (used[i])
+                if (int rc = run.mac(baby_hks[i], (u32)baby_elts[i], HKS_MAC_STORE, nullptr, run.h0->d_bsgs_b + i * slice)) return rc;
+        return 0;
+    }
+};
+
+extern "C" int hexl_hks_linear_transform_bsgs(hexl_hks* const* baby_hks, const uint64_t* baby_elts, size_t n_baby,
+                                              hexl_hks* const* giant_hks, const uint64_t* giant_elts, size_t n_giant,
+                                              const uint64_t* const* d_pts, const uint64_t* const* d_pt_identity, uint64_t* d_out,
+                                              const uint64_t* d_ct, size_t batch, uint64_t n_limbs) {
+    hexl_hks* h0 = nullptr;
+    if (int rc = hks_bsgs_check(baby_hks, baby_elts, n_baby, giant_hks, giant_elts, n_giant, d_pts, d_pt_identity, d_out, d_ct, batch, n_limbs,
+                                n_limbs, false, 0, &h0))
+        return rc;
     if (!batch) return 0;
+    hexl_ks_plan* p = h0->plan;
     hexl_ctx* c = p->ctx;
     HX_CHECK(hipSetDevice(c->device));
     const u32 l = (u32)n_limbs;
-    HksHoist run(h0, batch, l);
-    run.chunk = hks_bsgs_chunk(h0, n_baby, batch);
-    if (int rc = run.reserve()) return rc;
-    const size_t chunk = run.chunk, n = p->n, slice = chunk * 2 * p->K * n;     // doubles of one baby step's slice
-    if (n_baby)
-        if (int rc = h0->d_bsgs_b.reserve(n_baby * slice)) return rc;
-    if (int rc = h0->d_bsgs_t.reserve(chunk * hks_rows(h0).t * n)) return rc;
-    // the per-call tables, row after row: what the c0 kernel walks (plaintext, Galois element) and what the sum kernel walks (plaintext,
-    // baby slice). Pageable sources, stream-ordered behind the previous call's readers, as hexl_hks_linear_transform's table
-    std::vector<HxLtRot> rots;
-    std::vector<HksBsgsTerm> terms;
-    std::vector<size_t> off(n_giant + 1);
-    std::vector<char> used(n_baby, 0);
-    for (size_t j = 0; j < n_giant; ++j) {
-        off[j] = rots.size();
-        for (size_t i = 0; i < n_baby; ++i)
-            if (const u64* pt = d_pts[j * n_baby + i]) {
-                rots.push_back(HxLtRot{pt, baby_elts[i]});
-                terms.push_back(HksBsgsTerm{pt, h0->d_bsgs_b + i * slice});
-                used[i] = 1;
-            }
-    }
-    const size_t total = off[n_giant] = rots.size();
-    static_assert(sizeof(HxLtRot) == 16 && sizeof(HksBsgsTerm) == 16, "the two tables share one 16-byte-aligned reservation");
-    if (total) {
-        if (int rc = c->d_shared.reserve(total * (sizeof(HxLtRot) + sizeof(HksBsgsTerm)))) return rc;
-        HX_CHECK(hipMemcpyAsync(c->d_shared, rots.data(), total * sizeof(HxLtRot), hipMemcpyHostToDevice, c->stream));
-        HX_CHECK(hipMemcpyAsync((HxLtRot*)c->d_shared.get() + total, terms.data(), total * sizeof(HksBsgsTerm), hipMemcpyHostToDevice, c->stream));
-    }
-    const HxLtRot* d_rots = (const HxLtRot*)c->d_shared.get();
-    const HksBsgsTerm* d_terms = (const HksBsgsTerm*)(d_rots + total);
-    return hx_for_chunks(batch, chunk, [&](size_t b0, size_t nb) {
+    HksBsgsRun br(h0, n_baby, n_giant, batch, l);
+    if (int rc = br.prepare(baby_elts, d_pts)) return rc;
+    HksHoist& run = br.run;
+    const std::vector<size_t>& off = br.off;
+    const HxLtRot* d_rots = br.d_rots;
+    const HksBsgsTerm* d_terms = br.d_terms;
+    return hx_for_chunks(batch, run.chunk, [&](size_t b0, size_t nb) {
         const u64* ct = d_ct + b0 * run.per;
         u64* out = d_out + b0 * run.per;
         run.a.nb = (u32)nb;
-        if (total) {
-            if (int rc = run.up(ct, nb)) return rc;
-            for (size_t i = 0; i < n_baby; ++i)
-                if (used[i])
-                    if (int rc = run.mac(baby_hks[i], (u32)baby_elts[i], HKS_MAC_STORE, nullptr, h0->d_bsgs_b + i * slice)) return rc;
-        }
+        if (int rc = br.babies(baby_hks, baby_elts, ct, nb)) return rc;
         for (size_t j = 0; j < n_giant; ++j) {
             const size_t cnt = off[j + 1] - off[j];
             const u32 g = (u32)giant_elts[j];
@@ -1216,5 +1366,73 @@ extern "C" int hexl_hks_linear_transform_bsgs(hexl_hks* const* baby_hks, const u
             if (int rc = run.down(out)) return rc;                  // w1 in d_w1 again
         }
         return 0;
+    });
+}
+
+// ---- the double-hoisted BSGS (hexl_hks_linear_transform_bsgs_ext): the giant steps are summed in the extended basis
+// and divided ONCE. Per chunk, in h0's scratch: the babies as above; A (d_ext_a) and F -- d_out itself, or d_d01 with the rescale folded
+// in -- zeroed; per row j the key-free part kf_j into t_j and the weighted sum of the stored products into acc (an identity-only row
+// that rotates: zeros), then
+//   G_j = 1:  F += kf_j, A += inner_j (both components, no permutation);
+//   G_j != 1: the HALF mod-down of acc's component 1 added into t_j's component 1 (u_j; w in d_w1, coef and component 0 untouched),
+//             A[0] += sigma_G(inner_j[0]) on every row of T_l, the mod-up of u_j into coef / ext (the babies are stored: both are free),
+//             F[0] += sigma_G(kf_j[0]), A += the giant key's multiply-accumulate of sigma_G(ext');
+// and the mod-down of A: by P added into F, or by R = P q_(l-1) with d_k = F_k. One lane: every reader of t_j, acc, coef and ext is in
+// front of the next row's writer on the stream. ----
+extern "C" int hexl_hks_linear_transform_bsgs_ext(hexl_hks* const* baby_hks, const uint64_t* baby_elts, size_t n_baby,
+                                                  hexl_hks* const* giant_hks, const uint64_t* giant_elts, size_t n_giant,
+                                                  const uint64_t* const* d_pts, const uint64_t* const* d_pt_identity, uint64_t* d_out,
+                                                  const uint64_t* d_ct, size_t batch, uint64_t n_limbs, int rescale) {
+    if ((rescale != 0 && rescale != 1) || (rescale && n_limbs < 2)) return HEXL_E_BADARG;
+    hexl_hks* h0 = nullptr;
+    if (int rc = hks_bsgs_check(baby_hks, baby_elts, n_baby, giant_hks, giant_elts, n_giant, d_pts, d_pt_identity, d_out, d_ct, batch, n_limbs,
+                                n_limbs - rescale, true, rescale, &h0))
+        return rc;
+    if (!batch) return 0;
+    hexl_ks_plan* p = h0->plan;
+    hexl_ctx* c = p->ctx;
+    HX_CHECK(hipSetDevice(c->device));
+    const u32 l = (u32)n_limbs;
+    HksBsgsRun br(h0, n_baby, n_giant, batch, l);
+    if (int rc = br.prepare(baby_elts, d_pts)) return rc;
+    HksHoist& run = br.run;
+    const size_t n = p->n;
+    if (int rc = h0->d_ext_a.reserve(run.chunk * hks_rows(h0).ext_a * n)) return rc;
+    if (rescale)
+        if (int rc = h0->d_d01.reserve(run.chunk * hks_rows(h0).d01 * n)) return rc;
+    double* A = h0->d_ext_a;
+    return hx_for_chunks(batch, run.chunk, [&](size_t b0, size_t nb) {
+        const u64* ct = d_ct + b0 * run.per;
+        u64* out = d_out + b0 * 2 * (l - rescale) * n;
+        u64* F = rescale ? h0->d_d01.get() : out;
+        u64* t = h0->d_bsgs_t.get();
+        run.a.nb = (u32)nb;
+        const size_t row_words = size_t(run.a.T) * n, acc_bytes = nb * 2 * row_words * sizeof(double);   // one component of one instance; A
+        if (int rc = br.babies(baby_hks, baby_elts, ct, nb)) return rc;
+        HX_CHECK(hipMemsetAsync(A, 0, acc_bytes, c->stream));
+        HX_CHECK(hipMemsetAsync(F, 0, nb * run.per * sizeof(u64), c->stream));
+        for (size_t j = 0; j < n_giant; ++j) {
+            const size_t cnt = br.off[j + 1] - br.off[j];
+            const u32 g = (u32)giant_elts[j];
+            if (int rc = hx_launch_galois_c0_pt(p, t, ct, br.d_rots + br.off[j], cnt, d_pt_identity ? d_pt_identity[j] : nullptr, nb, l, nullptr)) return rc;
+            if (cnt)
+                if (int rc = run.sum(br.d_terms + br.off[j], cnt)) return rc;
+            if (g == 1) {
+                if (int rc = hx_launch_galois_add(p, F, t, nb, 1, 2, l)) return rc;
+                if (cnt)
+                    if (int rc = run.ext_add(A, 1, 2)) return rc;
+                continue;
+            }
+            // inner_j = 0: u_j = kf_j[1] + down_P(0), the overshoot alone. Component 1 of every instance is cleared (one strided fill);
+            // component 0 is neither read nor written for such a row
+            if (!cnt) HX_CHECK(hipMemset2DAsync(run.a.acc + row_words, 2 * row_words * sizeof(double), 0, row_words * sizeof(double), nb, c->stream));
+            if (int rc = run.down_c1(t)) return rc;
+            if (cnt)
+                if (int rc = run.ext_add(A, g, 1)) return rc;
+            if (int rc = run.up(t, nb)) return rc;
+            if (int rc = hx_launch_galois_add(p, F, t, nb, g, 1, l)) return rc;
+            if (int rc = run.mac(giant_hks[j], g, HKS_MAC_ACC, nullptr, A)) return rc;
+        }
+        return run.down_ext(A, out, rescale ? F : nullptr);
     });
 }

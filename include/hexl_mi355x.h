@@ -679,6 +679,47 @@ size_t hexl_hks_hoisted_scratch_bytes(const hexl_hks* hks, size_t batch);
  * hexl_hks_hoisted_scratch_bytes are unchanged. */
 int hexl_hks_linear_transform_bsgs(hexl_hks* const* baby_hks, const uint64_t* baby_elts, size_t n_baby, hexl_hks* const* giant_hks, const uint64_t* giant_elts, size_t n_giant, const uint64_t* const* d_pts, const uint64_t* const* d_pt_identity, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t n_limbs);
 size_t hexl_hks_bsgs_scratch_bytes(const hexl_hks* hks, size_t n_baby, size_t batch);
+/* The double-hoisted BSGS: the same sum with the giant steps kept in the extended basis and ONE division per call --
+ * by P, or with rescale = 1 by R = P q_(l-1), which folds the hexl_rescale that ends every linear layer into the same mod-down. Per
+ * instance U + #{G != 1} (D/2 + U) + D transforms (U = l + sum_d (l + n_p - |G_d|), D = 2 n_p + 2 l) where hexl_hks_linear_transform_bsgs
+ * runs U + n_giant D + #{G != 1} (U + D); the keys are the same n_baby + n_giant.
+ * Arguments, layouts and the scratch-owner rule are exactly those of hexl_hks_linear_transform_bsgs: objects on one plan with one alpha,
+ * plaintexts [K][n] that serve every level, diagonal (j, i) already rotated by G_j^-1, NULL entries where unused. d_ct is
+ * [batch][2][l][n]; d_out is WRITTEN, [batch][2][l][n] for rescale == 0 and [batch][2][l - 1][n] for rescale == 1 (l >= 2).
+ * Definition (normative), per instance, every line modulo its limb's modulus, every stored word canonical; rows r run over
+ * T_l = {0 .. l-1} + S, sigma_g is the word permutation of hexl_apply_galois, steps 1-4 and 3'-4' are those of hexl_hks_keyswitch and
+ * hexl_hks_relinearize_rescale:
+ *   1  ext = steps 1-2 applied to c1.
+ *   2  for every row j: inner_j[k][r] = sum_i pt_{j,i}[r] (sum_d sigma_{g_i}(ext_d[r]) key_i[d][k][r]) over row j's non-NULL terms (the acc
+ *      of hexl_hks_linear_transform; 0 for an identity-only row); kf_j[0][i] = sum_i pt_{j,i}[i] sigma_{g_i}(c0[i]) + pt_id_j[i] c0[i] and
+ *      kf_j[1][i] = pt_id_j[i] c1[i] for i < l.
+ *   3  A on T_l and F on the data limbs start at 0.
+ *      G_j = 1:  A[k] += inner_j[k], F[k] += kf_j[k].
+ *      G_j != 1: u_j[i] = kf_j[1][i] + down_P(inner_j[1])[i], canonical, down_P = step 4 on component 1 only (word for word component 1
+ *                of hexl_hks_linear_transform(row j)); W_j[k][r] = sum_d sigma_{G_j}(ext'_d[r]) key_{G_j}[d][k][r] with ext' = steps 1-2
+ *                applied to u_j; A[0] += sigma_{G_j}(inner_j[0]) + W_j[0] (sigma acts on every row of T_l, the special rows included);
+ *                A[1] += W_j[1]; F[0] += sigma_{G_j}(kf_j[0]).
+ *   4  rescale == 0: out[k][i] = F[k][i] + down_P(A[k])[i], step 4 with result = F.
+ *      rescale == 1: steps 3'-4' with d_k = F[k] and acc = A: X_k = P F_k + A_k modulo Q_l P is divided by R from the sources S + {l - 1}.
+ * Every output word is the canonical residue of an exactly defined class: the order of accumulation cannot change a word.
+ * Facts: with n_giant = 1, G = 1, rescale = 0 the call is word for word hexl_hks_linear_transform on row 0. A grid whose giant elements are
+ * all 1, rescale = 0, is word for word the flat hexl_hks_linear_transform over the concatenated non-NULL terms (objects and elements repeat
+ * per row; at most one row carries an identity term). With rescale = 1, per coefficient out_k = round(X_k / R) - e with an integer e in
+ * [0, n_p] (the argument of DESIGN.md 4.6.13). With some G_j != 1 the call is NOT word for word hexl_hks_linear_transform_bsgs: component 0
+ * of a row is no longer rounded before the giant step; with rescale = 1 it is NOT word for word that call followed by hexl_rescale. All of
+ * these decrypt alike.
+ * Noise, under the assumptions of the bounds above, with E = 21 n sum_d |G_d| D_d and S_j = sum_i ||pt_{j,i}||_1:
+ *   (sum_j S_j E + #{G != 1} (E + P (n_p + 1/2) n)) / P + (n_p + 1/2)(n + 1),  the first term divided by q_(l-1) as well with rescale = 1
+ * (then against the exact result divided by q_(l-1)). The term P (n_p + 1/2) n is the rounding of u_j carried through the giant switch.
+ * Errors: the checks of hexl_hks_linear_transform_bsgs in its order -- HEXL_E_BADARG, then HEXL_E_NOKEYS for an object that is USED, then
+ * batch == 0 -- and HEXL_E_BADARG also for rescale outside {0, 1} and for n_limbs < 2 with rescale == 1; the overlap checks use the
+ * output's real size. Asynchronous on the context's stream, on one lane; the host arrays may be reused on return; the call does NOT raise
+ * the input-range flag (hexl_ks_range_check).
+ * Device memory on the scratch owner, grow-only: what hexl_hks_linear_transform_bsgs holds at the same chunk, A (chunk x 2 x K x n
+ * doubles) and, for rescale == 1, F (chunk x 2 x L x n words, the buffer hexl_hks_multiply_sum_rescale keeps its (d0, d1) in).
+ * hexl_hks_bsgs_ext_scratch_bytes(hks, n_baby, batch, rescale) is that sum; the four older *_scratch_bytes figures are unchanged. */
+int hexl_hks_linear_transform_bsgs_ext(hexl_hks* const* baby_hks, const uint64_t* baby_elts, size_t n_baby, hexl_hks* const* giant_hks, const uint64_t* giant_elts, size_t n_giant, const uint64_t* const* d_pts, const uint64_t* const* d_pt_identity, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t n_limbs, int rescale);
+size_t hexl_hks_bsgs_ext_scratch_bytes(const hexl_hks* hks, size_t n_baby, size_t batch, int rescale);
 /* The hybrid multiply: a sum of ciphertext products, its relinearisation on the hybrid key and -- the two rescaling
  * calls -- the rescale, in one call. On the hybrid gadget a product is otherwise hexl_ct_tensor_sum, hexl_hks_relinearize and
  * hexl_rescale: the three-component sum and the un-rescaled ciphertext each pass through memory, and two mod-downs run (by P, then by
