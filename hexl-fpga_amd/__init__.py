@@ -85,6 +85,8 @@ C_ABI = {
     "hexl_hks_relinearize": [_vp, _vp, _vp, _sz, _u64],
     "hexl_hks_rotate": [_vp, _vp, _vp, _sz, _u64, _u64],
     "hexl_hks_scratch_bytes": [_vp, _sz],
+    "hexl_hks_keygen": [ctypes.POINTER(_vp), _sz, ctypes.POINTER(_i), ctypes.POINTER(_u64), ctypes.POINTER(_vp), _vp, _vp, _u64, _u64],
+    "hexl_hks_export_keys": [_vp, _vp],
     "hexl_hks_rotate_hoisted": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), _sz, ctypes.POINTER(_vp), _vp, _sz, _u64],
     "hexl_hks_linear_transform": [ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_vp), _sz, _vp, _vp, _vp, _sz, _u64],
     "hexl_hks_hoisted_scratch_bytes": [_vp, _sz],
@@ -512,6 +514,26 @@ class HybridKeySwitch:
         kernel on the context's stream, no host synchronisation -- an object in use may be re-keyed"""
         _check(lib().hexl_hks_set_keys_device(self.h, _ptr(keys)), "hexl_hks_set_keys_device")
 
+    def gen_keys(self, secret, from_kind: int, galois_elt: int = 1, from_poly=None, seed=None, stream: int = 0, first: int = 0) -> bytes:
+        """the hybrid switching key from s' to `secret` ([K][n], NTT form at all K limbs) generated into the object (hks_keygen with one
+        key): s' = from_poly [K][n] (KEY_FROM_POLY), secret^2 (KEY_FROM_SQUARE) or secret(X^galois_elt) (KEY_FROM_GALOIS). Word for word
+        plan.gen_hybrid_key -> set_keys_device; consumes polynomials first ... first + dnum - 1 of (seed, stream). Returns the seed's
+        bytes (None = os.urandom)."""
+        return hks_keygen([self], secret, [from_kind], galois_elts=[galois_elt], from_polys=[from_poly], seed=seed, stream=stream, first=first)
+
+    def gen_relin_keys(self, secret, seed=None, stream: int = 0, first: int = 0) -> bytes:
+        """the relinearisation key of `secret` (relinearize and the hybrid multiply)"""
+        return self.gen_keys(secret, KEY_FROM_SQUARE, seed=seed, stream=stream, first=first)
+
+    def gen_galois_keys(self, secret, g: int, seed=None, stream: int = 0, first: int = 0) -> bytes:
+        """the key rotate, the hoisted and the BSGS calls need for the Galois element g"""
+        return self.gen_keys(secret, KEY_FROM_GALOIS, galois_elt=g, seed=seed, stream=stream, first=first)
+
+    def export_keys(self, out):
+        """out[dnum][2][K][n] = the installed key as canonical words in the set_keys_device layout (hexl_hks_export_keys); one kernel on
+        the context's stream"""
+        _check(lib().hexl_hks_export_keys(self.h, _ptr(out)), "hexl_hks_export_keys")
+
     def keyswitch(self, result, t_target, batch: int, n_limbs: int):
         """result[batch][2][n_limbs][n] += KeySwitch(t_target[batch][n_limbs][n]) mod q_i, as KeySwitchPlan.keyswitch"""
         _check(lib().hexl_hks_keyswitch(self.h, _ptr(result), _ptr(t_target), batch, n_limbs), "hexl_hks_keyswitch")
@@ -591,6 +613,24 @@ def linear_transform(plans, galois_elts, pts, out, ct, batch: int, pt_identity=N
         raise ValueError("linear_transform: one plan, one Galois element and one plaintext per rotation")
     _check(lib().hexl_linear_transform(_handles(plans), _u64_array(galois_elts), ptr_array(pts), len(plans), None if pt_identity is None else _ptr(pt_identity), _ptr(out),
                                        _ptr(ct), batch), "hexl_linear_transform")
+
+
+def hks_keygen(hks_list, secret, from_kinds, galois_elts=None, from_polys=None, seed=None, stream: int = 0, first: int = 0) -> bytes:
+    """one hybrid switching key per object of hks_list, generated into the objects by ONE call (hexl_hks_keygen): key r switches from s'_r
+    to `secret` ([K][n], NTT form at all K limbs), s'_r = from_polys[r] (KEY_FROM_POLY), secret^2 (KEY_FROM_SQUARE) or
+    secret(X^galois_elts[r]) (KEY_FROM_GALOIS) by from_kinds[r]. Word for word plan.gen_hybrid_key(..., first=first_r) -> set_keys_device
+    per object with first_r = first + the dnum of the objects before r. The objects share one plan and may differ in alpha; at most 64.
+    WARNING (include/hexl_mi355x.h): it consumes the UNIFORM and CBD21 polynomials first ... first + sum dnum - 1 of (seed, stream).
+    galois_elts / from_polys: None, or one entry per key (entries of other kinds are ignored; from_polys entries may be None). Returns
+    the seed's bytes (None = os.urandom)."""
+    count = len(hks_list)
+    if len(from_kinds) != count or any(x is not None and len(x) != count for x in (galois_elts, from_polys)):
+        raise ValueError("hks_keygen: one kind (and one element / polynomial, where given) per object")
+    words, raw = seed_words(seed)
+    _check(lib().hexl_hks_keygen(_handles(hks_list), count, (_i * count)(*[int(k) for k in from_kinds]),
+                                 None if galois_elts is None else _u64_array(galois_elts), None if from_polys is None else _opt_ptrs(from_polys),
+                                 _ptr(secret), words, stream, first), "hexl_hks_keygen")
+    return raw
 
 
 def hks_rotate_hoisted(hks_list, galois_elts, outs, ct, batch: int, n_limbs: int):
@@ -681,6 +721,6 @@ def lt_bsgs_scratch_bytes(plan, n_baby: int, batch: int) -> int:
 
 from .host_api import HexlFpga  # noqa: E402  (mirror of host/inc/hexl-fpga.h)
 
-__all__ = ["Context", "KeySwitchPlan", "HybridKeySwitch", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform", "hks_rotate_hoisted", "hks_linear_transform", "hks_linear_transform_bsgs", "hks_linear_transform_bsgs_ext",
+__all__ = ["Context", "KeySwitchPlan", "HybridKeySwitch", "HexlFpga", "HexlError", "build", "lib", "as_i64", "to_u64", "rotate_hoisted", "linear_transform", "hks_keygen", "hks_rotate_hoisted", "hks_linear_transform", "hks_linear_transform_bsgs", "hks_linear_transform_bsgs_ext",
            "linear_transform_bsgs", "lt_bsgs_scratch_bytes", "C_ABI", "SAMPLE_UNIFORM", "SAMPLE_TERNARY", "SAMPLE_CBD21", "KEY_FROM_POLY", "KEY_FROM_SQUARE", "KEY_FROM_GALOIS", "seed_words",
            "LIB_PATH", "ROOT"]

@@ -370,6 +370,12 @@ int hx_ks_key_copies(hexl_ks_plan* p, HxKeyCopy out[HX_KEY_MAX_COPIES]);
 int hx_launch_ks_install(hexl_ks_plan*, const u64* d_keys);
 int hx_launch_ks_gen_keys(hexl_ks_plan*, const u64* d_secret, int from_kind, u32 g, const u64* d_from, const u32* seed, u64 stream, u64 first);
 u32 hx_ks_x_loge();
+// What hexl_hks_keygen (keygen.hip) needs of a hybrid object; keyswitch_hybrid.hip owns the struct. d_keys: [dnum][2][K][n] centred doubles,
+// the layout k_hks_install writes. p_mod: [K], P mod q_i canonical (exact as a double), P the product of the plan's moduli L ... K - 1,
+// computed when the object is created.
+struct HxHksKeys { hexl_ks_plan* plan; double* d_keys; const double* p_mod; u32 alpha, dnum; };
+HxHksKeys hx_hks_keys(hexl_hks*);
+void hx_hks_set_keyed(hexl_hks*);         // the keys were written on the context's stream: the object answers no HEXL_E_NOKEYS any more
 // index of coefficient held in register r of thread tid after a forward transform ("B layout")
 u32 hx_idxB(u32 logn, u32 r, u32 tid);
 u32 hx_loge_for(u32 logn);

@@ -57,6 +57,7 @@ struct hexl_hks {
     u32 alpha = 0, dnum = 0, np = 0;
     bool have_keys = false;
     HxDevBuf<double> d_keys;          // [dnum][2][K][n] centred, the caller's order
+    double p_mod[HKS_MAX_LIMBS] = {}; // [K]: P mod q_i canonical (host; hexl_hks_keygen's plaintext weight, keygen.hip)
     HxDevBuf<HksSrc> d_src;           // [32][16]: (conversion row, source limb)
     HxDevBuf<HksWt> d_wt;             // [32][16][16]: (conversion row, source limb, target limb)
     HxDevBuf<HksDiv> d_div;           // [16][16]: (divisor row, plan limb)
@@ -507,6 +508,20 @@ __global__ __launch_bounds__(HKS_THREADS) void k_hks_install(HksInstallArgs a) {
     *reinterpret_cast<d2*>(a.out + at) = o;
 }
 
+// the key export, the install's inverse: the centred doubles as canonical words at the same place of the caller's [dnum][2][K][n]
+struct HksExportArgs { const KsModF64* mods; const double* in; u64* out; u32 K, logn; };
+__global__ __launch_bounds__(HKS_THREADS) void k_hks_export(HksExportArgs a) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
+    const u32 lp = a.logn - HKS_LOG_PIECE;
+    const u32 row = blockIdx.x >> lp, piece = blockIdx.x - (row << lp);       // row = (d 2 + k) K + i
+    const double q = a.mods[row % a.K].m.p;
+    const size_t at = (size_t(row) << a.logn) + (size_t(piece) << HKS_LOG_PIECE) + 2 * threadIdx.x;
+    const d2 v = *reinterpret_cast<const d2*>(a.in + at);
+    const u2 o = {hxf::from_f64(v.x < 0.0 ? v.x + q : v.x), hxf::from_f64(v.y < 0.0 ? v.y + q : v.y)};
+    *reinterpret_cast<u2*>(a.out + at) = o;
+}
+
 // relinearize: ct3[nb][3][l][n] -> out[nb][2][l][n] (components 0-1) and t[nb][l][n] (component 2); words are moved, never interpreted
 struct HksMoveArgs { const u64* in; u64* out; u64* t; u32 l, logn; };
 __global__ __launch_bounds__(HKS_THREADS) void k_hks_split3(HksMoveArgs a) {
@@ -780,6 +795,7 @@ static int hks_constants(hexl_hks* h) {
         const u64 qi = q[i];
         u64 P = 1 % qi;
         for (u32 s = L; s < K; ++s) P = hxnt::mulmod(P, q[s] % qi, qi);
+        h->p_mod[i] = (double)P;
         for (u32 l = 1; l <= L; ++l) {
             const bool rs = l >= 2;
             if (rs && i >= l && i < L) continue;
@@ -852,6 +868,19 @@ extern "C" int hexl_hks_set_keys_device(hexl_hks* h, const uint64_t* d_keys) {
     if (int rc = (int)hipGetLastError()) return rc;
     h->have_keys = true;
     return 0;
+}
+
+HxHksKeys hx_hks_keys(hexl_hks* h) { return HxHksKeys{h->plan, h->d_keys, h->p_mod, h->alpha, h->dnum}; }
+void hx_hks_set_keyed(hexl_hks* h) { h->have_keys = true; }
+
+extern "C" int hexl_hks_export_keys(const hexl_hks* h, uint64_t* d_out) {
+    if (!h || !d_out) return HEXL_E_BADARG;
+    if (!h->have_keys) return HEXL_E_NOKEYS;
+    const hexl_ks_plan* p = h->plan;
+    HX_CHECK(hipSetDevice(p->ctx->device));
+    const HksExportArgs a{p->d_mods_f64, h->d_keys, d_out, p->K, p->logn};
+    hipLaunchKernelGGL(k_hks_export, dim3(hks_piece_grid(p, size_t(h->dnum) * 2 * p->K)), dim3(HKS_THREADS), 0, p->ctx->stream, a);
+    return (int)hipGetLastError();
 }
 
 extern "C" int hexl_hks_keyswitch(hexl_hks* h, uint64_t* d_result, const uint64_t* d_t_target, size_t batch, uint64_t n_limbs) {

@@ -400,6 +400,8 @@ int hexl_ckks_decode(hexl_ks_plan* plan, double* d_slots, const uint64_t* d_in, 
  * share both. Distinct kinds never collide (the kind is part of the block counter), distinct streams and distinct indices neither.
  * hexl_ks_gen_keys (below) is such a call: it consumes the UNIFORM and CBD21 polynomials first ... first + L - 1 of its (seed, stream),
  * exactly as the key-shaped hexl_rlwe_encrypt it replaces -- never give two keys of one secret the same triple.
+ * hexl_hks_keygen (further below) is such a call as well: it consumes the UNIFORM and CBD21 polynomials first ... first + sum_r dnum_r - 1
+ * of its (seed, stream), dnum_r per key in the order of its array -- advance `first` by that sum between calls that share both.
  * hexl_pk_encrypt is another: for every instance c = first + b it consumes the TERNARY polynomial c and the CBD21 polynomials 2c and
  * 2c + 1 of its (seed, stream). A (seed, stream) it uses must not be shared with hexl_sample, hexl_rlwe_encrypt or hexl_ks_gen_keys of
  * the same key material (their CBD21 index c is its index 2c' or 2c' + 1 for some c'), and `first` advances by `count` between calls.
@@ -585,6 +587,45 @@ int hexl_hks_keyswitch(hexl_hks* hks, uint64_t* d_result, const uint64_t* d_t_ta
 int hexl_hks_relinearize(hexl_hks* hks, uint64_t* d_out, const uint64_t* d_ct3, size_t batch, uint64_t n_limbs);
 int hexl_hks_rotate(hexl_hks* hks, uint64_t* d_out, const uint64_t* d_ct, size_t batch, uint64_t n_limbs, uint64_t galois_elt);
 size_t hexl_hks_scratch_bytes(const hexl_hks* hks, size_t batch);
+/* Hybrid keys made and read on the device.
+ *
+ * hexl_hks_keygen: one switching key per object, generated into the objects; key r switches from s'_r to s. Normative definition:
+ * afterwards object r is word for word what hexl_hks_set_keys_device leaves for the output of the Python wrapper
+ *   plan.gen_hybrid_key(out, secret, alpha_r, s'_r, seed, stream, first_r),   first_r = first + sum of dnum_r' over r' < r,
+ * that is, row (r, d) = (pt + e - a s, a) modulo all K limbs with a = the UNIFORM and e = the CBD21 polynomial first_r + d of
+ * (seed, stream), pt_i = (P mod q_i) s'_(r,i) for i in G_d and 0 at every other limb, the special primes included, P = the product of
+ * the plan's moduli L ... K - 1, and s'_r selected by from_kinds[r] with the constants and meanings of hexl_ks_gen_keys:
+ *   HEXL_KEY_FROM_POLY     s'_r = d_froms[r] [K][n], NTT form, every word below its modulus
+ *   HEXL_KEY_FROM_SQUARE   s'_(r,i) = s_i . s_i mod q_i: the key of hexl_hks_relinearize and the hybrid multiply
+ *   HEXL_KEY_FROM_GALOIS   s'_(r,i) = the hexl_apply_galois permutation of s_i for galois_elts[r]: the key of hexl_hks_rotate and the hoisted
+ *                          and BSGS calls for that element
+ * Every step is exact modular arithmetic, so "word for word" is well defined. d_secret is [K][n]: NTT_i(s) at ALL K limbs, every word
+ * below its modulus. galois_elts and d_froms may be NULL when no key's kind uses them; their entries for keys of other kinds are ignored.
+ * All objects are attached to ONE plan; they may have different alpha (the prefix sum above is what makes that work). The same object
+ * twice in one call is refused. n_keys <= HEXL_HKS_KEYGEN_MAX_KEYS = 64; a larger set takes several calls with `first` advanced by the
+ * rows of the calls before -- the words depend on (seed, stream, first_r + d) alone, never on the split.
+ * The call consumes polynomial indices first ... first + sum_r dnum_r - 1 of the UNIFORM and CBD21 kinds of (seed, stream): see the
+ * WARNING at hexl_sample. Asynchronous on the context's stream and ordered like hexl_hks_set_keys_device: generate, launch, generate,
+ * launch re-keys an object in use. The seed travels by value.
+ * Fused: the CBD21 errors of all sum_r dnum_r rows pass through the plan's encode scratch as in hexl_rlwe_encrypt (in chunks of 256 rows
+ * at n = 16384, the same number of coefficients at other n), then per chunk ONE kernel reads e and s (s' only in the rows i in G_d, whose
+ * plaintext is not zero -- read, squared in registers or gathered through the Galois index), draws `a`, forms c0 = pt + e - a s and
+ * stores c0 and `a` as centred doubles at their place in the object's keys. No [dnum][2][K][n] word buffer, no plaintext, no s^2 and no
+ * s(X^g) exists in memory; nothing key-sized is allocated (the encode scratch is the plan's, grow-only: a first call that grows it waits
+ * for the device).
+ * Everything is validated before anything is launched, and a refused call leaves every object as it was (without keys, if it had none:
+ * HEXL_E_NOKEYS from its callers). HEXL_E_BADARG: a null array, object, secret or seed; n_keys == 0 or above the limit; an unknown kind;
+ * HEXL_KEY_FROM_POLY with a null d_froms or a null entry; HEXL_KEY_FROM_GALOIS with a null galois_elts or an element that is even or >= 2n;
+ * objects on different plans; a repeated object; first + sum_r dnum_r > 2^40.
+ *
+ * hexl_hks_export_keys: the installed key as canonical words, the inverse of the install -- d_out [dnum][2][K][n] in the
+ * hexl_hks_set_keys_device layout, every word in [0, q_i). One kernel on the context's stream. hexl_hks_set_keys_device(X) then export
+ * gives X mod q exactly; export then hexl_hks_set_keys_device on another object of the same shape gives an identical object.
+ * HEXL_E_BADARG: a null handle or pointer; then HEXL_E_NOKEYS before any key is installed or generated (nothing is written). */
+#define HEXL_HKS_KEYGEN_MAX_KEYS 64
+int hexl_hks_keygen(hexl_hks* const* hks, size_t n_keys, const int* from_kinds, const uint64_t* galois_elts,
+                    const uint64_t* const* d_froms, const uint64_t* d_secret, const uint32_t seed[8], uint64_t stream, uint64_t first);
+int hexl_hks_export_keys(const hexl_hks* hks, uint64_t* d_out);   /* DEVICE [dnum][2][K][n] WRITTEN, canonical words */
 /* Hoisted rotations and the linear transform on the hybrid key switch: many plaintext-weighted rotations of ONE
  * ciphertext batch. R calls of hexl_hks_rotate repeat steps 1-2 of the definition above -- the l inverse transforms, the base
  * conversion and the sum_d (l + n_p - |G_d|) forward transforms -- which depend on c1 alone and not on the key. Per instance at the
